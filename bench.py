@@ -317,6 +317,41 @@ def timed_steps(model, x2d, x2f, steps, warmup, gen, gather, dev="cuda", telemet
     return dt, out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """`--dump-outputs DIR`: write what the timed path returned in its last step as DIR/<name>.npy (float32, or float64 for
+    integer outputs so that indices stay exact), at most `budget` bytes in all, .npy headers included.  An array that does
+    not fit in what is left of the budget is written as a fixed, seeded sample of whole poses (the trailing (J, 3) axes kept):
+    DIR/<name>_sample.npy holds the sampled poses, DIR/<name>_sample_index.npy their ascending flat indices over the
+    leading axes.  Returns {name: description} for the JSON line."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    # small arrays first, so that only the largest ones are ever sampled
+    items = sorted(((n, t.detach().cpu().numpy()) for n, t in arrays.items()), key=lambda kv: kv[1].size)
+    left, info = budget - 2 * 4096 * len(items), {}      # 4 KiB per .npy header, far more than one takes
+    for i, (name, a) in enumerate(items):
+        a = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+        share = left // (len(items) - i)
+        if a.nbytes <= share:
+            np.save(os.path.join(outdir, name + ".npy"), a)
+            left -= a.nbytes
+            info[name] = {"file": name + ".npy", "shape": list(a.shape), "dtype": str(a.dtype)}
+            continue
+        tail = a.shape[-2:] if a.ndim >= 3 else a.shape[-1:] if a.ndim == 2 else ()
+        rows = a.reshape((-1,) + tail)
+        n = share // (rows[0].nbytes + 8)                  # one pose + its float64 index per sampled row
+        idx = np.sort(np.random.default_rng(seed).choice(rows.shape[0], size=n, replace=False))
+        vals = rows[idx]
+        np.save(os.path.join(outdir, name + "_sample.npy"), vals)
+        np.save(os.path.join(outdir, name + "_sample_index.npy"), idx.astype(np.float64))
+        left -= vals.nbytes + idx.size * 8
+        info[name] = {"file": name + "_sample.npy", "index_file": name + "_sample_index.npy", "shape": list(a.shape),
+                      "dtype": str(a.dtype), "sampled_rows": int(n), "of_rows": int(rows.shape[0]), "sample_seed": seed}
+    return info
+
+
 def exchange_report(local_preds, x2d, world, dev, dry, reps=5):
     """The two forms of the hypothesis exchange + JPMA, timed side by side on this rank's sampler output (median of
     `reps`; barrier + device sync around each): (a) all-gather of the full stacks -> fused JPMA on the gathered layout,
@@ -861,7 +896,14 @@ def main():
     ap.add_argument("--dry-full-size", action="store_true",
                     help="with --dist-dry-run: keep --batch / --hyps / --ksteps and F=243, so that the exchange moves the real "
                          "message (158.6 MB per rank at the BASELINE configs[3] shape) over gloo; needs ~6 GB of host memory per rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline path returned in its last step as DIR/<name>.npy (rank 0; "
+                         "at most 64 MB in all, a fixed seeded sample of larger outputs); same arguments -> same inputs")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    if a.warmup < 0:
+        ap.error("--warmup must be >= 0")
     dry = a.dist_dry_run > 0
     if dry:
         a.gpus = a.dist_dry_run
@@ -904,6 +946,10 @@ def main():
     else:
         local_preds = out
     assert local_preds.shape == (B, K, H, frames, J_, 3) and bool(torch.isfinite(local_preds).all())
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, {"preds": local_preds, "aggregated": agg, "selected": sel} if multi
+                              else {"preds": local_preds})
     units = B * H * world * a.steps
     value = units / dt
     flop_per_unit = 2 * K * flops_per_denoiser_call()
@@ -926,6 +972,8 @@ def main():
                    "whole_path_frac_of_mfma_peak": value * flop_per_unit / 1e12 / (peak * world),
                    "mfma_peak_used_tflops": peak},
     }
+    if dumped is not None:
+        res["dump_outputs"] = {"dir": os.path.abspath(a.dump_outputs), "arrays": dumped}
     if tele is not None:
         tr = tele.report()
         # the three keys VERDICT r5 item 3 names, at the top level; the rest of the samples' summary beside them

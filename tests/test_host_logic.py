@@ -125,6 +125,31 @@ def test_bench_relaunches_itself_under_torchrun(monkeypatch):
     assert a[-6:] == ["--gpus", "8", "--steps", "2", "--warmup", "1"] and a[-7].endswith("bench.py")
 
 
+def test_bench_dump_outputs_is_bounded_and_repeatable(tmp_path):
+    """`--dump-outputs DIR`: small outputs are written whole; one larger than the 64 MB budget becomes a seeded sample of
+    whole poses whose flat indices, stored beside it, point back at the same values; the same input gives the same files."""
+    import importlib.util
+    import numpy as np
+    import torch
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = torch.randn(16, 10, 20, 243, 17, 3, generator=torch.Generator().manual_seed(3))      # 158.6 MB of fp32
+    arrays = {"preds": big, "aggregated": big[:, :, 0], "selected": torch.arange(16 * 10 * 243 * 17).reshape(16, 10, 243, 17)}
+    a, b = tmp_path / "a", tmp_path / "b"
+    info = bench.dump_outputs(str(a), arrays)
+    assert info == bench.dump_outputs(str(b), arrays)
+    assert sum(f.stat().st_size for f in a.iterdir()) <= bench.DUMP_BUDGET_BYTES == 64 << 20
+    for f in a.iterdir():
+        assert np.array_equal(np.load(f), np.load(b / f.name)) and np.load(f).dtype in (np.float32, np.float64)
+    assert np.array_equal(np.load(a / "aggregated.npy"), big[:, :, 0].numpy())
+    assert np.array_equal(np.load(a / "selected.npy"), arrays["selected"].numpy().astype(np.float64))
+    vals, idx = np.load(a / "preds_sample.npy"), np.load(a / "preds_sample_index.npy")
+    assert info["preds"]["shape"] == list(big.shape) and vals.shape == (idx.size, 17, 3) and idx.size > 100000
+    assert np.all(np.diff(idx) > 0) and np.array_equal(vals, big.numpy().reshape(-1, 17, 3)[idx.astype(np.int64)])
+
+
 def test_bench_reports_counter_traffic_only_for_the_build_it_was_measured_on(monkeypatch):
     """roofline.traffic comes from separate rocprofv3 --pmc passes stored in profiles/ next to the sha256 of the library
     they were measured on ('refuse to print it when it differs')."""
