@@ -411,7 +411,7 @@ const char* d3dp_profile_class_name(int32_t cls) {
 int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   if (!cfg || !out) return fail(D3DP_EINVAL, "d3dp_create: null argument");
   const d3dp_cfg& g = *cfg;
-  // (frames > 256: EXACT mode's temporal attention takes the chunked-key flash kernel; FAST / TRAIN contexts the fp32 row kernel)
+  // (frames > 256: EXACT and TRAIN contexts take chunked-key forms of their attention kernels, FAST contexts the fp32 row kernel)
   if (g.frames < 1 || g.frames > 1024) return fail(D3DP_ENOTSUP, "frames=%d not in [1,1024]", g.frames);
   // (more than 32 joints: the spatial axis takes the whole-sequence attention kernels the temporal axis runs on, round 6)
   if (g.joints < 1 || g.joints > 256) return fail(D3DP_ENOTSUP, "joints=%d not in [1,256]", g.joints);
@@ -523,6 +523,18 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   if (hipMalloc((void**)&c->d_flag, sizeof(unsigned)) != hipSuccess || hipMemset(c->d_flag, 0, sizeof(unsigned)) != hipSuccess) {
     delete c;
     return fail(D3DP_EHIP, "d3dp_create: cannot allocate the status word");
+  }
+  // The second stream of d3dp_train_backward and its events are made HERE, not on the first step: d3dp_train_backward then creates
+  // nothing, and even a context's first step keeps the header's "does not allocate" (tests/test_hip_streams.py).
+  // (exactly the contexts whose backward pass forks: split-fp16 Linears -- use_x2 there -- and D3DP_TRAIN_OVERLAP not 0)
+  if (g.mode == D3DP_MODE_TRAIN && c->train_x2 && c->train_overlap && g.channels % 32 == 0 && g.hidden % 32 == 0) {
+    bool ok = hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking) == hipSuccess &&
+              hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess;
+    for (hipEvent_t& e : c->ev_done) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+      (void)d3dp_destroy(c);
+      return fail(D3DP_EHIP, "d3dp_create: cannot create the training step's second stream and its events");
+    }
   }
   *out = c;
   return D3DP_OK;
@@ -1648,11 +1660,7 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
   // (under the per-kernel profile everything runs on the caller's stream: a class's time must not contain a wait for CUs that a
   //  product on the second stream holds -- same arithmetic, test_training_step_stream_switches_change_no_bit)
   const bool overlap = use_x2 && c->train_overlap && !c->prof;
-  if (overlap && !c->aux) {
-    HIP_TRY(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    for (hipEvent_t& e : c->ev_done) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
+  if (overlap && !c->aux) return fail(D3DP_ESTATE, "d3dp_train_backward: the second stream was not created (d3dp_create makes it)");
   // Up to two weight-gradient products are in flight on c->aux, each with its own operand / partial-tile set (X2Train::use_set):
   // product k takes set k & 1 and the caller's stream waits for product k - 2 before the operand pass overwrites that set -- not
   // for product k - 1, which goes on beside the dgrad product and the row kernels of this dY.  D3DP_TRAIN_OVERLAP=1: one set,

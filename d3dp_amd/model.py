@@ -365,7 +365,16 @@ class MixSTE2(nn.Module):
         st = self._state()
         if st.ws is None or st.ws.numel() < n.value:
             st.ws = torch.empty(n.value, dtype=torch.uint8, device=self._last_device)
+        self._used_on_current_stream(st.ws)
         return st.ws, n.value
+
+    @staticmethod
+    def _used_on_current_stream(ws: torch.Tensor) -> None:
+        """The workspaces outlive the stream they were allocated under: a later call may run in them on another stream, and
+        regrowth drops them while that call is still in flight.  The caching allocator hands a freed block back to its
+        ALLOCATION stream at once unless it knows of the other users, so every use is recorded (a no-op on the allocation
+        stream itself)."""
+        ws.record_stream(torch.cuda.current_stream(ws.device))
 
     def denoise(self, x_2d: torch.Tensor, x_3d: torch.Tensor, t: torch.Tensor, out: Optional[torch.Tensor] = None):
         """x_2d (B,F,J,2), x_3d (B,H,F,J,3), t (B,) int64 -> (B,H,F,J,3) fp32 (all on the GPU)."""
@@ -444,6 +453,7 @@ class MixSTE2(nn.Module):
         st = self._state()
         if st.train_ws is None or st.train_ws.numel() < n.value:
             st.train_ws = torch.empty(n.value, dtype=torch.uint8, device=self._last_device)
+        self._used_on_current_stream(st.train_ws)
         return (ctx, B, dev, n.value, x_2d.float().contiguous(), x_3d.float().contiguous(),
                 t.to(device=dev, dtype=torch.int64).contiguous())
 

@@ -8,9 +8,25 @@
  *
  * Conventions
  *  - plain C types only; every pointer is a DEVICE pointer to a contiguous buffer unless marked "host";
- *  - `stream` is a hipStream_t passed as void* (0 = the null stream); every call is asynchronous on it, does
- *    not allocate and does not synchronise (exceptions: d3dp_create/d3dp_set_weights/d3dp_destroy and the
- *    d3dp_profile_* calls);
+ *  - `stream` is a hipStream_t passed as void* (0 = the null stream); every call that takes one enqueues ALL of its work on it
+ *    (or orders it behind and before it, see the training step), returns without waiting for it, allocates nothing, creates
+ *    no stream or event and synchronises nothing -- tests/test_hip_streams.py holds every such function to this on a side
+ *    stream.  The exceptions, all of them:
+ *      d3dp_create, d3dp_destroy    allocate / free, create / destroy the context's second stream and its events (below);
+ *      d3dp_set_weights             allocates the packed weights and synchronises `stream`;
+ *      d3dp_status                  synchronises the DEVICE;
+ *      d3dp_profile_enable / _read  while enabled the timed calls create events as their pool grows; _read synchronises them;
+ *      d3dp_op_attention, impl 2    allocates and frees a temporary in stream order (hipMallocAsync / hipFreeAsync on `stream`);
+ *      d3dp_debug_train_linear      (test hook) allocates its operand buffers and synchronises `stream`.
+ *    There is no first-call set-up left in a hot call: what a context needs beyond its workspace exists after d3dp_create.
+ *  - d3dp_train_backward also uses a second, library-owned stream.  Every piece of work there is forked from `stream` with an
+ *    event and joined back into `stream` with an event before the call returns: ordering against `stream` alone is sufficient
+ *    for the caller (wait for `stream`, or enqueue behind it, and every gradient is there); the host is never blocked.
+ *  - the hot calls (d3dp_denoise, d3dp_train_forward, d3dp_train_backward, the sampler and caller-side kernels, the single
+ *    operators except the exceptions above) may be recorded into a HIP graph by stream capture and replayed (after one eager
+ *    call of the same shape); d3dp_status, d3dp_set_weights, d3dp_create and d3dp_destroy may not be called during capture;
+ *  - one context has one workspace and one set of internal buffers: calls on the SAME context issued on different streams must
+ *    be ordered by the caller (events between the streams); different contexts are independent and may run concurrently;
  *  - every function returns 0 on success, a negative D3DP_E* code otherwise; d3dp_last_error() returns a
  *    thread-local message for the last failure;
  *  - a context is bound to the HIP device current at d3dp_create and is not thread-safe (one ctx per rank).
@@ -126,10 +142,15 @@ D3DP_API const char* d3dp_last_error(void);
  *                         kernels (split-fp16 / bf16 operands) -- `-cs 512`, the width of every published checkpoint
  *                         (README.md:33-39), and its smaller powers of two;
  *   any other width the reference's 8 heads divide (common/arguments.py:49, mixste.py:46-62) with channels <= 1024,
- *                         head dim % 4 == 0 and <= 128, hidden % 4 == 0: D3DP_MODE_EXACT only, on the fp32 implementation
+ *                         head dim % 4 == 0 and <= 128, hidden % 4 == 0: D3DP_MODE_EXACT on the fp32 implementation
  *                         (fp32-MFMA Linears, fp32 row attention, run-time-width row kernels; d3dp_exact_scales reports
- *                         implementation 2): the same 1e-3 mm tolerance at roughly a fifth of the throughput.  FAST and TRAIN
- *                         contexts exist for the instantiated widths only. */
+ *                         implementation 2): the same 1e-3 mm tolerance at roughly a fifth of the throughput.  D3DP_MODE_TRAIN
+ *                         takes such a width too, on the fp32 path of the training step (what D3DP_TRAIN_IMPL=f32 selects for
+ *                         the instantiated widths), whose attention backward holds a whole sequence in LDS: max(frames,
+ *                         joints) <= 256 tokens, <= 153 at head dims above 64.  FAST contexts exist for the instantiated
+ *                         widths only.
+ * A D3DP_MODE_TRAIN context whose backward pass overlaps (split-fp16 Linears, D3DP_TRAIN_OVERLAP not 0) gets its second stream
+ * and three events here, so that d3dp_train_backward never creates anything. */
 D3DP_API int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out);
 D3DP_API int d3dp_destroy(d3dp_ctx* ctx);
 /* Replaces: load_state_dict (main.py:257).  Converts/packs weights for cfg.mode (synchronises `stream`).
@@ -231,8 +252,9 @@ D3DP_API int d3dp_jpma_ex(const float* pred, const float* traj, const float* cam
  * [2 branches (attention, MLP)][B*max(F,J)] floats; entry s of a spatial block is sample b*F+f, of a temporal block b*J+n.
  * d3dp_train_forward keeps every activation the backward needs in `workspace`; d3dp_train_backward must follow with the
  * same inputs/masks/workspace.  grads: device fp32 buffers shaped like the weights (zeroed, then filled, here).
- * d3dp_train_backward launches a block's weight-gradient product on a second, library-owned stream, forked from and joined
- * back to `stream` with events before it returns (the host is never synchronised; env D3DP_TRAIN_OVERLAP=0: one stream).
+ * d3dp_train_backward launches a block's weight-gradient product on a second, library-owned stream (made by d3dp_create), forked
+ * from and joined back to `stream` with events before it returns (the host is never synchronised; env D3DP_TRAIN_OVERLAP=0: one
+ * stream) -- see Conventions: the caller orders against `stream` alone.
  * No gradient is accumulated with float atomics: the same inputs give the same bits.
  * Clip length: any F <= 1024 like inference (reference common/arguments.py:58); beyond 256 frames the step needs head dim 64 and
  * its split-fp16 attention kernels (keys / queries through LDS in chunks) -- the fp32 cross-check implementations

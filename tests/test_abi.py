@@ -59,6 +59,51 @@ def test_exports_are_exactly_the_header(lib):
         ["d3dp_debug_train_linear", "d3dp_debug_x2_variants"]
 
 
+def stream_taking_functions():
+    """Every function of include/d3dp_hip.h with a `void* stream` parameter."""
+    src = open(os.path.join(REPO, "include", "d3dp_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return sorted(name for name, params in re.findall(r"\b(d3dp_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src)
+                  if re.search(r"\bvoid\s*\*\s*stream\b", params))
+
+
+def test_every_stream_taking_function_is_in_the_stream_suite():
+    """The header promises one stream contract for every call that takes a `stream`; tests/test_hip_streams.py runs each of them on
+    a side stream (a row of its sweep table, or one of its named tests).  A function added to the ABI later cannot skip that
+    suite: the set parsed from the header must equal the set the suite names."""
+    import importlib
+    suite = importlib.import_module("test_hip_streams")
+    declared = stream_taking_functions()
+    assert len(declared) >= 25, declared                                # 25 at ABI v4; functions are only ever added
+    assert set(declared) <= set(header_functions())
+    assert suite.stream_functions_covered() == declared
+    assert not set(suite.NAMED_TESTS) & {fn for _, fn, _ in suite.SWEEP}
+    for name in suite.NAMED_TESTS.values():                             # the named tests exist
+        for test in name.split(", "):
+            assert hasattr(suite, test), test
+    assert len({row[0] for row in suite.SWEEP}) == len(suite.SWEEP)     # unique ids
+
+
+def test_hip_trace_parser_finds_the_brackets_and_the_forbidden_calls():
+    """The reader of the traced step (tests/test_hip_streams.py, section 5) on a hand-made API trace: a bracket opens with three device
+    synchronisations in a row (torch's current-device queries in between do not count) and closes with the next one."""
+    import importlib
+    suite = importlib.import_module("test_hip_streams")
+    names = ["hipMalloc", "hipDeviceSynchronize", "hipGetDevice", "hipDeviceSynchronize", "hipDeviceSynchronize", "hipLaunchKernel",
+             "hipGetLastError", "hipModuleLaunchKernel", "hipEventRecord", "hipStreamWaitEvent", "hipDeviceSynchronize", "hipMalloc",
+             "hipDeviceSynchronize", "hipDeviceSynchronize", "hipDeviceSynchronize", "hipLaunchKernel", "hipStreamSynchronize",
+             "hipMemcpyAsync", "hipMallocAsync", "hipMemcpy", "hipEventCreateWithFlags", "hipDeviceSynchronize", "hipFree"]
+    rows = [{"Domain": "HIP_RUNTIME_API", "Function": n, "Start_Timestamp": str(100 + i), "End_Timestamp": str(101 + i)}
+            for i, n in enumerate(names)]
+    brackets, key = suite.parse_hip_trace(rows[::-1])                   # (any row order: sorted by start time)
+    assert len(brackets) == 2
+    counts, forbidden, streams = suite.summarise_bracket(brackets[0], key)
+    assert counts == {"hipLaunchKernel": 1, "hipModuleLaunchKernel": 1, "hipEventRecord": 1, "hipStreamWaitEvent": 1}
+    assert forbidden == {} and streams is None
+    _, forbidden, _ = suite.summarise_bracket(brackets[1], key)
+    assert forbidden == {"hipStreamSynchronize": 1, "hipMallocAsync": 1, "hipMemcpy": 1, "hipEventCreateWithFlags": 1}
+
+
 def make_model(frames=243, cs=512, dep=8, H=20, K=10, is_train=False):
     args = SimpleNamespace(number_of_frames=frames, test_time_augmentation=True, timestep=1000, scale=1.0, cs=cs, dep=dep)
     return D3DP(args, H36M_JOINTS_LEFT, H36M_JOINTS_RIGHT, is_train=is_train, num_proposals=H, sampling_timesteps=K)

@@ -744,16 +744,21 @@ def test_sampler_fast_mode_vs_bf16_emulating_oracle(frames, B, H, K):
 
 
 # ------------------------------------------------------------------------------------------------ BASELINE configs at full size
-def test_c2_full_size_vs_reference_fixture(golden_dir):
-    """BASELINE configs[1]: F=243, J=17, H=5, K=5, B=4, exact mode, against the REFERENCE run at full size
-    (fixture g13: every 10th frame in full + fp64 checksums of every (clip, step, hypothesis) over all frames)."""
+def c2_full_size_case(golden_dir):
+    """BASELINE configs[1] as fixture g13 recorded it: (fixture, model, x2d, flipped x2d, the K injected noises), all on the GPU."""
     g = load_g(golden_dir, "g13_sampler_c2")
     cs, dep, Fr, B, H, K = (int(g[k]) for k in ("cs", "dep", "frames", "B", "H", "K"))
     assert (Fr, B, H, K) == (243, 4, 5, 5)
     x2d = synthetic_inputs_2d(int(g["x2d_seed"]), B, Fr)
-    noises = [torch.from_numpy(synthetic_noise(int(g["noise_seed"]) + k, (B, H, Fr, 17, 3))) for k in range(K)]
+    noises = [torch.from_numpy(synthetic_noise(int(g["noise_seed"]) + k, (B, H, Fr, 17, 3))).cuda() for k in range(K)]
     m = make_model(Fr, cs, dep, H, K, "exact", int(g["seed"]))
-    out = m(torch.from_numpy(x2d).cuda(), None, input_2d_flip=torch.from_numpy(flip_2d(x2d)).cuda(), noise=noises).cpu()
+    return g, m, torch.from_numpy(x2d).cuda(), torch.from_numpy(flip_2d(x2d)).cuda(), noises
+
+
+def check_c2_against_fixture(g, out):
+    """The gate of test_c2_full_size_vs_reference_fixture on a sampler output `out` (host tensor): every 10th frame in full
+    within EXACT_TOL_MM of the reference run, all frames through the fp64 checksums."""
+    Fr, B, H, K = (int(g[k]) for k in ("frames", "B", "H", "K"))
     assert out.shape == (B, K, H, Fr, 17, 3)
     kept = torch.from_numpy(g["kept_frames"]).long()
     per_step = [orc.mpjpe_mm(out[:, k][:, :, kept], torch.from_numpy(g["out_kept"][:, k])) for k in range(K)]
@@ -768,6 +773,13 @@ def test_c2_full_size_vs_reference_fixture(golden_dir):
     d_sq = ((o * o).sum(-1) - torch.from_numpy(g["sumsq"])).abs().max().item() / n
     print(f"[c2 full size] checksum deviations per coordinate (m): sum {d_sum:.2e} weighted {d_w:.2e} squares {d_sq:.2e}")
     assert d_sum < 2e-7 and d_w < 3e-7 and d_sq < 2e-7        # 1e-3 mm = 1e-6 m per joint; these are means of signed errors
+
+
+def test_c2_full_size_vs_reference_fixture(golden_dir):
+    """BASELINE configs[1]: F=243, J=17, H=5, K=5, B=4, exact mode, against the REFERENCE run at full size
+    (fixture g13: every 10th frame in full + fp64 checksums of every (clip, step, hypothesis) over all frames)."""
+    g, m, x2d, x2f, noises = c2_full_size_case(golden_dir)
+    check_c2_against_fixture(g, m(x2d, None, input_2d_flip=x2f, noise=noises).cpu())
 
 
 def test_c3_full_size_slices_vs_oracle():
