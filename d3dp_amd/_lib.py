@@ -14,8 +14,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # D3DP_LIB=path: load another build of the library (A/B runs of differently compiled kernels; test-only)
 LIB_PATH = os.environ.get("D3DP_LIB") or os.path.join(_HERE, "lib", "libd3dp_hip.so")
 
-MODE_EXACT, MODE_FAST, MODE_TRAIN = 0, 1, 2
+MODE_EXACT, MODE_FAST, MODE_TRAIN, MODE_FAST16 = 0, 1, 2, 3
 MODE_SPLIT3 = 2   # d3dp_op_linear only: split-bf16 operands
+OP_FP16 = 4       # single operators only: IEEE fp16 operands / rows (d3dp_op_linear mode, d3dp_op_attention act_bf16, d3dp_op_layernorm out_bf16)
 EPI_BIAS, EPI_GELU, EPI_RESID, EPI_QKV_PACK = 0, 1, 2, 4     # (| D << 8: the skewed schedule of epi 1 / 4, include/d3dp_hip.h)
 PROFILE_CLASSES = 25
 
@@ -24,7 +25,7 @@ class AdamChunk(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int32),
                 ("pad", C.c_int32)]
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class Cfg(C.Structure):
@@ -102,6 +103,7 @@ PROTOTYPES = {
     "d3dp_exact_range_bound": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "d3dp_exact_scales": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "d3dp_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "d3dp_fast_operands": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "d3dp_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "d3dp_profile_class_name": (C.c_char_p, [C.c_int32]),
     # test hooks (include/d3dp_hip.h, last section)

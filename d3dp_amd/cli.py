@@ -60,7 +60,7 @@ def parse_args(argv=None):
     p.add_argument('--synthetic', action='store_true', help='seeded synthetic sequences instead of data/*.npz')
     p.add_argument('--synthetic-sequences', type=int, default=2)
     p.add_argument('--synthetic-frames', type=int, default=600)
-    p.add_argument('--numerics', default=None, choices=['exact', 'fast'])
+    p.add_argument('--numerics', default=None, choices=['exact', 'fast', 'fast16'])
     p.add_argument('--seed', type=int, default=1)
     a = p.parse_args(argv)
     a.test_time_augmentation = True          # arguments.py:112 (no flag turns it off in the reference)

@@ -47,6 +47,7 @@ __device__ __forceinline__ int seq_base(const SeqMap& m, int s) {
 template <typename T> struct Vec16;   // 16-byte vector of T
 template <> struct Vec16<float> { static constexpr int N = 4; };
 template <> struct Vec16<bf16> { static constexpr int N = 8; };
+template <> struct Vec16<f16> { static constexpr int N = 8; };
 
 template <typename T, int N>
 __device__ __forceinline__ void ld_vec(const T* p, float* v) {
@@ -54,7 +55,7 @@ __device__ __forceinline__ void ld_vec(const T* p, float* v) {
     float4 a = *reinterpret_cast<const float4*>(p);
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
   } else {
-    load8(reinterpret_cast<const bf16*>(p), v);
+    load8(p, v);                                       // (T: bf16 or f16)
   }
 }
 
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(256) void attn_rows_kernel(const T* __restrict__ qk
 #pragma unroll
         for (int e = 0; e < VN; ++e) { r[e] = o[c * VN + e] * inv; am = fmaxf(am, fabsf(r[e])); }
         if constexpr (VN == 4) *reinterpret_cast<float4*>(dst + c * 4) = make_float4(r[0], r[1], r[2], r[3]);
-        else store8(reinterpret_cast<bf16*>(dst) + c * 8, r);
+        else store8(dst + c * 8, r);
       }
     }
   }
@@ -313,40 +314,42 @@ __device__ __forceinline__ FragBases make_frag_bases(const char* KS, const char*
 }
 
 // V^T fragment (MFMA A operand) for output channels dn*16 + (lane&15), keys {32c + 4g + j} and {32c + 16 + 4g + j}
-template <int C0>
-__device__ __forceinline__ bf16x8 load_vt_frag(const char* vb) {
+// (E: the element type of the result; the transposing read moves 16-bit payloads whatever they mean, so the bf16 builtin
+//  serves both and the fp16 form is a bit cast of its result)
+template <int C0, typename E = bf16>
+__device__ __forceinline__ typename Op2<E>::x8 load_vt_frag(const char* vb) {
   const v4bf16 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) v4bf16*)(vb + C0 * 4096));
   const v4bf16 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) v4bf16*)(vb + C0 * 4096 + 2048));
-  typedef __bf16 raw8 __attribute__((ext_vector_type(8)));     // (16-bit payloads: whatever `bf16` is in this build, common.h D3DP_FAST_F16)
-  return __builtin_bit_cast(bf16x8, (raw8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]});
+  return __builtin_bit_cast(typename Op2<E>::x8, (bf16x8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]});
 }
 
-template <int NKT, int C0>
-__device__ __forceinline__ void pv_chunks(const FragBases& fb, const bf16x8 (&pf)[NKT / 2], f32x4 (&o)[4]) {
+template <typename E, int NKT, int C0>
+__device__ __forceinline__ void pv_chunks(const FragBases& fb, const typename Op2<E>::x8 (&pf)[NKT / 2], f32x4 (&o)[4]) {
   if constexpr (C0 < NKT / 2) {
 #pragma unroll
     for (int dn = 0; dn < 4; ++dn)
-      o[dn] = D3DP_MFMA_16x16x32_BF16(load_vt_frag<C0>(fb.v[dn]), pf[C0], o[dn]);
+      o[dn] = Op2<E>::mfma(load_vt_frag<C0, E>(fb.v[dn]), pf[C0], o[dn]);
     if (C0 & 1) __builtin_amdgcn_sched_barrier(0);
-    pv_chunks<NKT, C0 + 1>(fb, pf, o);
+    pv_chunks<E, NKT, C0 + 1>(fb, pf, o);
   }
 }
 
 // One 16-query tile against NKT 16-key tiles resident in LDS.  q0/q1: the tile's Q fragments (d 0..31 / 32..63).
 // Returns O^T accumulators (4 channel tiles) and the softmax denominator of query (lane & 15).
-template <int NKT>
-__device__ __forceinline__ void attn_tile(const FragBases& fb, bf16x8 q0, bf16x8 q1, int n, int lane, f32x4 (&o)[4],
-                                          float& denom) {
+template <typename E, int NKT>
+__device__ __forceinline__ void attn_tile(const FragBases& fb, typename Op2<E>::x8 q0, typename Op2<E>::x8 q1, int n, int lane,
+                                          f32x4 (&o)[4], float& denom) {
+  using e8 = typename Op2<E>::x8;
   const int fg = lane >> 4;
   const float cexp = 0.125f * 1.44269504088896340736f;   // hd^-0.5 * log2(e), hd = 64
   f32x4 s[NKT];
 #pragma unroll
   for (int t = 0; t < NKT; ++t) {
-    const bf16x8 k0 = *reinterpret_cast<const bf16x8*>(fb.k0 + t * 2048);
-    const bf16x8 k1 = *reinterpret_cast<const bf16x8*>(fb.k1 + t * 2048);
+    const e8 k0 = *reinterpret_cast<const e8*>(fb.k0 + t * 2048);
+    const e8 k1 = *reinterpret_cast<const e8*>(fb.k1 + t * 2048);
     f32x4 a = {0.f, 0.f, 0.f, 0.f};
-    a = D3DP_MFMA_16x16x32_BF16(k0, q0, a);
-    a = D3DP_MFMA_16x16x32_BF16(k1, q1, a);
+    a = Op2<E>::mfma(k0, q0, a);
+    a = Op2<E>::mfma(k1, q1, a);
     s[t] = a;
     if ((t & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // bound the ds_read hoisting window (VGPR pressure)
   }
@@ -365,14 +368,14 @@ __device__ __forceinline__ void attn_tile(const FragBases& fb, bf16x8 q0, bf16x8
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
   const float mc = mx * cexp;
   float sum = 0.f;
-  bf16x8 pf[NKT / 2];
+  e8 pf[NKT / 2];
 #pragma unroll
   for (int t = 0; t < NKT; ++t) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float p = __builtin_amdgcn_exp2f(fmaf(s[t][r], cexp, -mc));
       sum += p;
-      pf[t >> 1][(t & 1) * 4 + r] = (bf16)p;
+      pf[t >> 1][(t & 1) * 4 + r] = (E)p;
     }
   }
   sum += __shfl_xor(sum, 16, 64);
@@ -380,18 +383,18 @@ __device__ __forceinline__ void attn_tile(const FragBases& fb, bf16x8 q0, bf16x8
   denom = sum;
 #pragma unroll
   for (int dn = 0; dn < 4; ++dn) o[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  pv_chunks<NKT, 0>(fb, pf, o);
+  pv_chunks<E, NKT, 0>(fb, pf, o);
 }
 
 // rows [0, n) of K and V (128 B per row for this head) -> swizzled LDS images; rows [n, NK) of V zeroed.
-template <int NK, int NTHREADS>
-__device__ __forceinline__ void stage_kv(const bf16* __restrict__ kbase, size_t row_stride, int n, char* KS, char* VS,
+template <int NK, int NTHREADS, typename E>
+__device__ __forceinline__ void stage_kv(const E* __restrict__ kbase, size_t row_stride, int n, char* KS, char* VS,
                                          int tid, int C) {
   for (int idx = tid; idx < NK * 8; idx += NTHREADS) {
     const int row = idx >> 3, slot = idx & 7;
     float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
     if (row < n) {
-      const bf16* src = kbase + (size_t)row * row_stride + slot * 8;
+      const E* src = kbase + (size_t)row * row_stride + slot * 8;
       kv = *reinterpret_cast<const float4*>(src);
       vv = *reinterpret_cast<const float4*>(src + C);
     }
@@ -400,9 +403,11 @@ __device__ __forceinline__ void stage_kv(const bf16* __restrict__ kbase, size_t 
   }
 }
 
-template <int NKT>   // temporal axis: one workgroup per (sequence, head), 8 waves share the K/V images
-__global__ __launch_bounds__(512, 4) void attn_temporal2_bf16_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
+template <typename E, int NKT>   // temporal axis: one workgroup per (sequence, head), 8 waves share the K/V images
+__global__ __launch_bounds__(512, 4) void attn_temporal2_bf16_kernel(const E* __restrict__ qkv, E* __restrict__ out,
                                                                      SeqMap map, int C, int heads) {
+  using e4 = typename Op2<E>::x4;
+  using e8 = typename Op2<E>::x8;
   constexpr int NK = 16 * NKT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* KS = smem;
@@ -413,19 +418,19 @@ __global__ __launch_bounds__(512, 4) void attn_temporal2_bf16_kernel(const bf16*
   const int base = seq_base(map, seq);
   const int ts = map.tok_stride;
   const size_t ld = (size_t)3 * C;
-  const bf16* qbase = qkv + (size_t)base * ld + (size_t)head * 64;
+  const E* qbase = qkv + (size_t)base * ld + (size_t)head * 64;
   // This wave's Q fragments for ALL of its query tiles are requested before K/V staging, so their HBM latency
   // overlaps the staging loads instead of being paid once per tile in the compute loop.
   const int fi = lane & 15, fg = lane >> 4;
   const int n_qt = (n + 15) >> 4;
   constexpr int QPW = (NKT + 7) / 8;                 // query tiles per wave
-  bf16x8 qf[QPW][2];
+  e8 qf[QPW][2];
 #pragma unroll
   for (int i = 0; i < QPW; ++i) {
     const int q = min((wave + 8 * i) * 16 + fi, n - 1);
-    const bf16* qsrc = qbase + (size_t)q * ts * ld + fg * 8;
-    qf[i][0] = *reinterpret_cast<const bf16x8*>(qsrc);
-    qf[i][1] = *reinterpret_cast<const bf16x8*>(qsrc + 32);
+    const E* qsrc = qbase + (size_t)q * ts * ld + fg * 8;
+    qf[i][0] = *reinterpret_cast<const e8*>(qsrc);
+    qf[i][1] = *reinterpret_cast<const e8*>(qsrc + 32);
   }
   stage_kv<NK, 512>(qbase + C, (size_t)ts * ld, n, KS, VS, tid, C);
   const FragBases fb = make_frag_bases(KS, VS, lane);
@@ -437,14 +442,14 @@ __global__ __launch_bounds__(512, 4) void attn_temporal2_bf16_kernel(const bf16*
     const int q = qt * 16 + fi;
     f32x4 o[4];
     float denom;
-    attn_tile<NKT>(fb, qf[i][0], qf[i][1], n, lane, o, denom);
+    attn_tile<E, NKT>(fb, qf[i][0], qf[i][1], n, lane, o, denom);
     if (q < n) {
       const float inv = 1.0f / denom;
-      bf16* dst = out + (size_t)(base + q * ts) * C + head * 64 + fg * 4;
+      E* dst = out + (size_t)(base + q * ts) * C + head * 64 + fg * 4;
 #pragma unroll
       for (int dn = 0; dn < 4; ++dn) {
-        bf16x4 r = {(bf16)(o[dn][0] * inv), (bf16)(o[dn][1] * inv), (bf16)(o[dn][2] * inv), (bf16)(o[dn][3] * inv)};
-        *reinterpret_cast<bf16x4*>(dst + dn * 16) = r;
+        e4 r = {(E)(o[dn][0] * inv), (E)(o[dn][1] * inv), (E)(o[dn][2] * inv), (E)(o[dn][3] * inv)};
+        *reinterpret_cast<e4*>(dst + dn * 16) = r;
       }
     }
   }
@@ -452,8 +457,11 @@ __global__ __launch_bounds__(512, 4) void attn_temporal2_bf16_kernel(const bf16*
 
 // spatial axis (<= 32 tokens per sequence): one WAVE per (sequence, head) with a private 8 KiB K/V image;
 // a 256-thread workgroup covers 4 heads of one sequence.
-__global__ __launch_bounds__(256) void attn_spatial_bf16_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
+template <typename E>
+__global__ __launch_bounds__(256) void attn_spatial_bf16_kernel(const E* __restrict__ qkv, E* __restrict__ out,
                                                                 int n_prob, SeqMap map, int C, int heads) {
+  using e4 = typename Op2<E>::x4;
+  using e8 = typename Op2<E>::x8;
   __shared__ __attribute__((aligned(16))) char smem[4 * 8192];
   const int n = map.n_tok;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -463,19 +471,19 @@ __global__ __launch_bounds__(256) void attn_spatial_bf16_kernel(const bf16* __re
   const int base = seq_base(map, seq);
   const int ts = map.tok_stride;
   const size_t ld = (size_t)3 * C;
-  const bf16* qbase = qkv + (size_t)base * ld + (size_t)head * 64;
+  const E* qbase = qkv + (size_t)base * ld + (size_t)head * 64;
   char* KS = smem + wave * 8192;
   char* VS = KS + 4096;
   // the query fragments of both 16-row tiles are requested BEFORE the K/V staging so that their HBM latency overlaps
   // it (the kernel is latency/HBM-bound: one small problem per wave)
   const int fi = lane & 15, fg = lane >> 4;
   const int n_qt = (n + 15) >> 4;
-  bf16x8 qf[2][2];
+  e8 qf[2][2];
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
-    const bf16* qsrc = qbase + (size_t)min(qt * 16 + fi, n - 1) * ts * ld + fg * 8;
-    qf[qt][0] = *reinterpret_cast<const bf16x8*>(qsrc);
-    qf[qt][1] = *reinterpret_cast<const bf16x8*>(qsrc + 32);
+    const E* qsrc = qbase + (size_t)min(qt * 16 + fi, n - 1) * ts * ld + fg * 8;
+    qf[qt][0] = *reinterpret_cast<const e8*>(qsrc);
+    qf[qt][1] = *reinterpret_cast<const e8*>(qsrc + 32);
   }
   stage_kv<32, 64>(qbase + C, (size_t)ts * ld, n, KS, VS, lane, C);
   const FragBases fb = make_frag_bases(KS, VS, lane);
@@ -484,17 +492,17 @@ __global__ __launch_bounds__(256) void attn_spatial_bf16_kernel(const bf16* __re
   for (int qt = 0; qt < 2; ++qt) {
     if (qt >= n_qt) break;
     const int q = qt * 16 + fi;
-    const bf16x8 q0 = qf[qt][0], q1 = qf[qt][1];
+    const e8 q0 = qf[qt][0], q1 = qf[qt][1];
     f32x4 o[4];
     float denom;
-    attn_tile<2>(fb, q0, q1, n, lane, o, denom);
+    attn_tile<E, 2>(fb, q0, q1, n, lane, o, denom);
     if (q < n) {
       const float inv = 1.0f / denom;
-      bf16* dst = out + (size_t)(base + q * ts) * C + head * 64 + fg * 4;
+      E* dst = out + (size_t)(base + q * ts) * C + head * 64 + fg * 4;
 #pragma unroll
       for (int dn = 0; dn < 4; ++dn) {
-        bf16x4 r = {(bf16)(o[dn][0] * inv), (bf16)(o[dn][1] * inv), (bf16)(o[dn][2] * inv), (bf16)(o[dn][3] * inv)};
-        *reinterpret_cast<bf16x4*>(dst + dn * 16) = r;
+        e4 r = {(E)(o[dn][0] * inv), (E)(o[dn][1] * inv), (E)(o[dn][2] * inv), (E)(o[dn][3] * inv)};
+        *reinterpret_cast<e4*>(dst + dn * 16) = r;
       }
     }
   }
@@ -1893,39 +1901,46 @@ int launch_temporal_f32(const void* qkv, void* out, int n_seq, SeqMap map, int C
   return 0;
 }
 
-template <int NKT>
+template <typename E, int NKT>
 int launch_temporal2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
   constexpr int NK = 16 * NKT;
   const size_t lds = (size_t)NK * 256;
-  auto kern = attn_temporal2_bf16_kernel<NKT>;
+  auto kern = attn_temporal2_bf16_kernel<E, NKT>;
   static PerDeviceOnce once;                          // (one per template instantiation = per kernel)
   if (once.get([&](int) { return d3dp_lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024); }) < 0) return -3;
-  hipLaunchKernelGGL(kern, dim3(n_seq * heads), dim3(512), lds, st, (const bf16*)qkv, (bf16*)out, map, C, heads);
+  hipLaunchKernelGGL(kern, dim3(n_seq * heads), dim3(512), lds, st, (const E*)qkv, (E*)out, map, C, heads);
   return 0;
 }
 
 }  // namespace
 
-// act: 0 = fp32 in/out, 1 = bf16 in/out, 2 = fp32 in, split-bf16 planes out, 3 = fp32 in, split-fp16 planes out
+// act: 0 = fp32 in/out, 1 = bf16 in/out, 2 = fp32 in, split-bf16 planes out, 3 = fp32 in, split-fp16 planes out,
+//      4 = IEEE fp16 in/out
 // (amax: fp32 output only -- its absmax, see the kernel)
 int d3dp_launch_attn_rows(int act, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st,
                           unsigned* amax) {
   const size_t plane = (size_t)n_seq * map.n_tok * C;
   if (act != 0 && amax) return -1;
   if (act == 1) return dispatch_rows<bf16, 0>(qkv, out, n_seq, map, C, heads, plane, nullptr, st);
+  if (act == 4) return dispatch_rows<f16, 0>(qkv, out, n_seq, map, C, heads, plane, nullptr, st);
   if (act == 2) return dispatch_rows<float, 3>(qkv, out, n_seq, map, C, heads, plane, nullptr, st);
   if (act == 3) return dispatch_rows<float, 2>(qkv, out, n_seq, map, C, heads, plane, nullptr, st);
   return dispatch_rows<float, 0>(qkv, out, n_seq, map, C, heads, plane, amax, st);
 }
 
-int d3dp_launch_attn_temporal_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
-                                   hipStream_t st) {
-  if (C / heads != 64 || map.n_tok > 256 || map.n_tok < 1) return -2;
+template <typename E>
+static int attn_temporal2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
   const int n = map.n_tok;
-  if (n <= 32) return launch_temporal2<2>(qkv, out, n_seq, map, C, heads, st);
-  if (n <= 64) return launch_temporal2<4>(qkv, out, n_seq, map, C, heads, st);
-  if (n <= 128) return launch_temporal2<8>(qkv, out, n_seq, map, C, heads, st);
-  return launch_temporal2<16>(qkv, out, n_seq, map, C, heads, st);
+  if (n <= 32) return launch_temporal2<E, 2>(qkv, out, n_seq, map, C, heads, st);
+  if (n <= 64) return launch_temporal2<E, 4>(qkv, out, n_seq, map, C, heads, st);
+  if (n <= 128) return launch_temporal2<E, 8>(qkv, out, n_seq, map, C, heads, st);
+  return launch_temporal2<E, 16>(qkv, out, n_seq, map, C, heads, st);
+}
+// (f16: 0 = bf16 rows in and out, 1 = IEEE fp16)
+int d3dp_launch_attn_temporal_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
+                                   hipStream_t st, int f16) {
+  if (C / heads != 64 || map.n_tok > 256 || map.n_tok < 1) return -2;
+  return f16 ? attn_temporal2<_Float16>(qkv, out, n_seq, map, C, heads, st) : attn_temporal2<__bf16>(qkv, out, n_seq, map, C, heads, st);
 }
 
 // EXACT-mode temporal axis on the fp32 matrix cores (head dim 64); act 0 -> fp32 out, 2 -> split-bf16 planes out,
@@ -1990,12 +2005,16 @@ int d3dp_launch_attn_x2(int act, int axis, const void* qkv, void* out, int n_seq
 #undef X2_CASE
 }
 
-// spatial axis on MFMA (bf16, head dim 64, <= 32 tokens per sequence)
-int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
+// spatial axis on MFMA (bf16 or, f16 == 1, IEEE fp16 rows; head dim 64, <= 32 tokens per sequence)
+int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st, int f16) {
   if (C / heads != 64 || map.n_tok > 32 || map.n_tok < 1) return -2;
   const int n_prob = n_seq * heads;
-  hipLaunchKernelGGL(attn_spatial_bf16_kernel, dim3((n_prob + 3) / 4), dim3(256), 0, st, (const bf16*)qkv, (bf16*)out,
-                     n_prob, map, C, heads);
+  if (f16)
+    hipLaunchKernelGGL(attn_spatial_bf16_kernel<_Float16>, dim3((n_prob + 3) / 4), dim3(256), 0, st, (const _Float16*)qkv,
+                       (_Float16*)out, n_prob, map, C, heads);
+  else
+    hipLaunchKernelGGL(attn_spatial_bf16_kernel<__bf16>, dim3((n_prob + 3) / 4), dim3(256), 0, st, (const __bf16*)qkv, (__bf16*)out,
+                       n_prob, map, C, heads);
   return 0;
 }
 

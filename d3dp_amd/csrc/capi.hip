@@ -5,7 +5,7 @@
 // (sequence, frame, joint), channels fastest):
 //   x    [Tc, C]   fp32   residual stream -- stays fp32 in both modes
 //   (EXACT mode: bufA / the MLP hidden are three bf16 planes of the fp32 value, qkv and y are fp32)
-//   bufA [Tc, C]   act    normalised input of the next GEMM / attention output      (act = bf16 FAST, fp32 EXACT)
+//   bufA [Tc, C]   act    normalised input of the next GEMM / attention output      (act = bf16 FAST, fp16 FAST16, fp32 EXACT)
 //   bufB [Tc, 3C]  act    qkv; reused as the [Tc, 2C] MLP hidden
 //   y1,y [Tc, C]   act    outputs of the residual-feeding Linears (proj, fc2); the norm pair after the block forms
 //                          (x + y1) + y in registers, so x is read and written once per block
@@ -78,7 +78,7 @@ const char* kClassNames[D3DP_PROFILE_CLASSES] = {"gemm_qkv", "gemm_proj", "gemm_
 
 struct BlockDev {
   const float *n1w, *n1b, *n2w, *n2b, *qkv_b, *proj_b, *fc1_b, *fc2_b;
-  const void *qkv_w, *proj_w, *fc1_w, *fc2_w;   // bf16 (FAST); EXACT: 2 fp16 planes (default), 3 bf16 planes or fp32
+  const void *qkv_w, *proj_w, *fc1_w, *fc2_w;   // bf16 (FAST) or fp16 (FAST16); EXACT: 2 fp16 planes (default), 3 bf16 planes or fp32
   float qkv_u = 1.f, proj_u = 1.f, fc1_u = 1.f, fc2_u = 1.f;   // EXACT f16x2: 2^-s of the per-matrix pre-scale 2^s
   const float* fc1_c12 = nullptr;   // fold_ln: [c2 | c1] of norm2 folded into fc1 (fc1_w then holds W diag(gamma)); see run_block
   // EXACT f16x2: the power-of-two scales of this block's DATA-dependent split-fp16 operands -- q / k / v and the attention
@@ -88,16 +88,68 @@ struct BlockDev {
   float s_kv = kActScale, s_h = kActScale;
 };
 
-__global__ void to_bf16_kernel(const float* __restrict__ s, bf16* __restrict__ d, size_t n) {
+template <typename E>   // E: bf16 or f16 -- a plain cast, round to nearest even
+__global__ void to_bf16_kernel(const float* __restrict__ s, E* __restrict__ d, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) d[i] = (bf16)s[i];
+  for (; i < n; i += stride) d[i] = (E)s[i];
 }
 
-void launch_to_bf16(const float* s, void* d, size_t n, hipStream_t st) {
+void launch_to_bf16(const float* s, void* d, size_t n, hipStream_t st, int f16 = 0) {
   const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
-  hipLaunchKernelGGL(to_bf16_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, st, s, (bf16*)d, n);
+  if (f16) hipLaunchKernelGGL(to_bf16_kernel<_Float16>, dim3(blocks ? blocks : 1), dim3(256), 0, st, s, (_Float16*)d, n);
+  else hipLaunchKernelGGL(to_bf16_kernel<__bf16>, dim3(blocks ? blocks : 1), dim3(256), 0, st, s, (__bf16*)d, n);
 }
+
+// ---- the range proof of D3DP_MODE_FAST16 (d3dp_set_weights; include/d3dp_hip.h d3dp_fast_operands) ----------------------------
+// One wave per row n of W [N][K]:  s_n = sum_k |W[n,k]| in_k + |bias_n|  with  in_k = sq |gamma_k| + |beta_k|  (gamma given: the
+// Linear reads a LayerNorm over K channels, sq = sqrt(K - 1)) or the constant cin[0] (the Linear reads a tensor bounded by a
+// number an earlier launch of this kernel left on the device).  Products and sums run in fp64 -- the fp32 inputs' products are
+// exact there and the accumulated rounding of <= 2048 terms stays below 2^-40 -- and every result is rounded UP to fp32, so a
+// bound never under-states the formula and over-states it by less than 2^-22.  Results leave as the bit patterns of
+// non-negative floats under an integer max (`out` pre-zeroed); a nan weight gives a nan bound, whose pattern is above inf's.
+//   o_sum  = max_n s_n;   o_tail (optional) = max over rows n >= n_tail;   o_in (optional) = max_k in_k;   o_w = max |W|
+__device__ __forceinline__ unsigned f32_bits_up(double v) {
+  float f = (float)v;
+  if ((double)f < v) f = __uint_as_float(__float_as_uint(f) + 1u);        // (v >= 0: the next float up; FLT_MAX -> inf)
+  return __float_as_uint(f) & 0x7fffffffu;                                // (a nan may carry a sign bit)
+}
+__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)v, o, 64); v = t > v ? t : v; }
+  return v;
+}
+__global__ __launch_bounds__(256) void fast16_bound_kernel(const float* __restrict__ W, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, const unsigned* __restrict__ cin,
+                                                           const float* __restrict__ bias, int N, int K, double sq, int n_tail,
+                                                           unsigned* o_sum, unsigned* o_tail, unsigned* o_in, unsigned* o_w) {
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const double c = cin ? (double)__uint_as_float(cin[0]) : 0.0;
+  double a = 0.0;
+  unsigned inmax = 0u, wmax = 0u;
+  for (int k = lane; k < K; k += 64) {
+    const float w = fabsf(W[(size_t)n * K + k]);
+    const double in = gamma ? sq * (double)fabsf(gamma[k]) + (double)fabsf(beta[k]) : c;
+    const unsigned ib = f32_bits_up(in), wb = __float_as_uint(w);
+    inmax = ib > inmax ? ib : inmax;
+    wmax = wb > wmax ? wb : wmax;
+    a += (double)w * in;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+  inmax = wave_max_u(inmax);
+  wmax = wave_max_u(wmax);
+  if (lane == 0) {
+    const unsigned sb = f32_bits_up((a + (double)fabsf(bias[n])) * (1.0 + 0x1p-40));
+    atomicMax(o_sum, sb);
+    if (o_tail && n >= n_tail) atomicMax(o_tail, sb);
+    if (o_in) atomicMax(o_in, inmax);
+    atomicMax(o_w, wmax);
+  }
+}
+constexpr int kF16Slots = 11;   // per block: L1, b_qkv, b_v, b_proj, L2, b_h, b_fc2, max |w| of qkv / proj / fc1 / fc2
 
 constexpr size_t kAlign = 256;
 size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
@@ -125,7 +177,15 @@ struct d3dp_ctx {
   int64_t counts[D3DP_PROFILE_CLASSES] = {0};
   double total_ms[D3DP_PROFILE_CLASSES] = {0};
 
-  bool fast() const { return cfg.mode == D3DP_MODE_FAST; }
+  // FAST and FAST16 contexts are one dataflow (2-byte operands and branch outputs, fp32 residual stream, the streaming Linear
+  // and the MFMA attention kernels) in two element types.  fast_f16: the type this context's kernels are instantiated for --
+  // a FAST16 context has it set by d3dp_set_weights when the weights prove that no stored value can reach fp16's 65504
+  // (fast_bound) and runs the bf16 kernels otherwise; a plain FAST context proves nothing and is bf16 (the `make fastf16`
+  // library: fp16, D3DP_FAST_F16).
+  bool fast16() const { return cfg.mode == D3DP_MODE_FAST16; }
+  bool fast() const { return cfg.mode == D3DP_MODE_FAST || fast16(); }
+  int fast_f16 = 0;
+  float fast_bound = 0.f;
   // EXACT mode runs its Linears on split-fp16 operands (2 planes, 3 fp16-MFMA passes, gemm_x2.hip); activations that
   // feed a Linear are then two fp16 planes.  env D3DP_EXACT_IMPL=bf16x3 selects the round-1 six-pass split-bf16 kernels
   // and =f32 the plain fp32-MFMA kernels (bitwise an fp32 fmaf chain) -- both kept as cross-checks.
@@ -189,7 +249,7 @@ struct d3dp_ctx {
                                  // measured 1.5-2 % SLOWER on the whole step, gpurun c8); 2 = D3DP_X2_WIDE=1: the 256 x 256
                                  // tile form (bit-identical; ties with the default, profiles/r04_gemm_probes.md section 4)
   bool x3() const { return exact() && exact_impl == 1; }
-  int act() const { return fast() ? 1 : (x3() ? 2 : (x2() ? 3 : 0)); }   // code understood by the row-wise launchers
+  int act() const { return fast() ? (fast_f16 ? 4 : 1) : (x3() ? 2 : (x2() ? 3 : 0)); }   // code understood by the row-wise launchers
   size_t act_size() const { return fast() ? 2 : (x3() ? 6 : 4); }    // bytes per element of a Linear-input activation
   size_t wide_size() const { return fast() ? 2 : 4; }                // bytes per element of bufB (qkv fp32 = 12C; hidden planes <= 12C)
   size_t y_size() const { return fast() ? 2 : 4; }
@@ -285,7 +345,7 @@ int linear(d3dp_ctx* c, int cls, int epi, int out_f32, const void* A, const void
            int M, int N, int K, hipStream_t st, void* out2 = nullptr, float* aux = nullptr, float a_scale = kActScale,
            float o_scale = kActScale) {
   Scope s(c, cls, st);
-  if (c->fast()) return d3dp_launch_linear_bf16_stream(epi, out_f32, A, W, bias, out, M, N, K, st);
+  if (c->fast()) return d3dp_launch_linear_bf16_stream(epi, out_f32, A, W, bias, out, M, N, K, st, c->fast_f16);
   if (c->x2()) {
     // the qkv Linear writes the packed rows of the split-fp16 attention kernels (K and V already as fp16 planes)
     if (cls == P_QKV && c->x2_attn()) epi = EPI_QKV_PACK;
@@ -318,13 +378,13 @@ int attention(d3dp_ctx* c, int axis, const void* qkv, void* out, int n_bh, float
   if (axis == 0) {
     if (c->fast() && g.channels / g.heads == 64 && g.joints <= 32)
       return d3dp_launch_attn_spatial_bf16(qkv, out, n_bh * g.frames, spatial_map(g.frames, g.joints), g.channels,
-                                           g.heads, st);
+                                           g.heads, st, c->fast_f16);
     return d3dp_launch_attn_rows(c->act(), qkv, out, n_bh * g.frames, spatial_map(g.frames, g.joints), g.channels,
                                  g.heads, st);
   }
   if (c->fast() && g.channels / g.heads == 64 && g.frames <= 256)
     return d3dp_launch_attn_temporal_bf16(qkv, out, n_bh * g.joints, temporal_map(g.frames, g.joints), g.channels,
-                                          g.heads, st);
+                                          g.heads, st, c->fast_f16);
   if (c->exact() && g.channels / g.heads == 64 && g.frames <= 256)     // fp32 matrix cores
     return d3dp_launch_attn_temporal_f32(c->act(), qkv, out, n_bh * g.joints, temporal_map(g.frames, g.joints),
                                          g.channels, g.heads, st);
@@ -334,7 +394,7 @@ int attention(d3dp_ctx* c, int axis, const void* qkv, void* out, int n_bh, float
 
 // x = x + proj(attn(qkv(xn)));  x = x + fc2(gelu(fc1(LN2(x))))        (mixste.py:113-115)
 // The two residual adds are not done by the GEMMs: each residual-feeding Linear writes y = A W^T + b (fp32) and the
-// (activation type: bf16 in FAST mode -- one more bf16 rounding on the branch output, none on the fp32 residual
+// (activation type: bf16 in FAST mode, fp16 in FAST16 -- one more 2-byte rounding on the branch output, none on the fp32 residual
 // stream itself) and the next row-wise kernel (LN2 here; the norm pair / head in the caller) performs x += y while it has the row in
 // registers anyway.  On return y1 / y hold the proj / fc2 outputs that the CALLER's next kernel must add to x.
 int run_block(d3dp_ctx* c, const BlockDev& w, int axis, float* x, void* y1, void* y, void* bufA, void* bufB, float* lnst,
@@ -411,13 +471,14 @@ const char* d3dp_profile_class_name(int32_t cls) {
 int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   if (!cfg || !out) return fail(D3DP_EINVAL, "d3dp_create: null argument");
   const d3dp_cfg& g = *cfg;
-  // (frames > 256: EXACT and TRAIN contexts take chunked-key forms of their attention kernels, FAST contexts the fp32 row kernel)
+  // (frames > 256: EXACT and TRAIN contexts take chunked-key forms of their attention kernels, FAST / FAST16 contexts the row
+  //  kernel -- fp32 arithmetic on their 2-byte rows, keys through LDS in chunks of 256)
   if (g.frames < 1 || g.frames > 1024) return fail(D3DP_ENOTSUP, "frames=%d not in [1,1024]", g.frames);
   // (more than 32 joints: the spatial axis takes the whole-sequence attention kernels the temporal axis runs on, round 6)
   if (g.joints < 1 || g.joints > 256) return fail(D3DP_ENOTSUP, "joints=%d not in [1,256]", g.joints);
   if (g.heads < 1 || g.channels < 1 || g.channels % g.heads) return fail(D3DP_EINVAL, "heads=%d does not divide channels=%d", g.heads, g.channels);
   if (g.depth < 1) return fail(D3DP_EINVAL, "depth=%d", g.depth);
-  if (g.mode != D3DP_MODE_EXACT && g.mode != D3DP_MODE_FAST && g.mode != D3DP_MODE_TRAIN)
+  if (g.mode != D3DP_MODE_EXACT && g.mode != D3DP_MODE_FAST && g.mode != D3DP_MODE_TRAIN && g.mode != D3DP_MODE_FAST16)
     return fail(D3DP_EINVAL, "mode=%d", g.mode);
   const int hd = g.channels / g.heads;
   // The matrix-core kernels (split-fp16 / bf16 operands) and the row kernels around them are instantiated for the widths
@@ -436,6 +497,11 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
       return fail(D3DP_ENOTSUP, "channels=%d heads=%d hidden=%d: FAST contexts exist for channels in {64,128,256,512} with head dim in "
                                 "{8,16,32,64} and hidden a multiple of 64; other widths run in D3DP_MODE_EXACT / D3DP_MODE_TRAIN (fp32 implementation)",
                   g.channels, g.heads, g.hidden);
+    if (g.mode == D3DP_MODE_FAST16)
+      return fail(D3DP_ENOTSUP, "channels=%d heads=%d hidden=%d: FAST16 contexts exist for the shapes FAST contexts exist for -- channels in "
+                                "{64,128,256,512} with head dim in {8,16,32,64} and hidden a multiple of 64; other widths run in D3DP_MODE_EXACT / "
+                                "D3DP_MODE_TRAIN (fp32 implementation)",
+                  g.channels, g.heads, g.hidden);
     if (g.channels > 1024 || g.channels % 4 || hd % 4 || hd > 128 || g.hidden < 4 || g.hidden % 4)
       return fail(D3DP_ENOTSUP, "channels=%d heads=%d hidden=%d: the fp32 implementation takes channels <= 1024, head dim a multiple of 4 up to 128 "
                                 "and hidden a multiple of 4", g.channels, g.heads, g.hidden);
@@ -451,6 +517,7 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
     return fail(D3DP_EHIP, "no HIP device visible: libd3dp_hip has no CPU fallback");
   d3dp_ctx* c = new d3dp_ctx();
   c->cfg = g;
+  c->fast_f16 = c->fast16() ? 1 : (c->fast() ? D3DP_FAST_F16 : 0);   // (FAST16: until d3dp_set_weights has seen the weights)
   const char* xf = getenv("D3DP_EXACT_IMPL");
   c->exact_impl = c->exact_impl_req = (xf && !strcmp(xf, "bf16x3")) ? 1 : (xf && !strcmp(xf, "f32")) ? 2 : 0;
   if (!width_inst) {
@@ -627,7 +694,58 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
       std::fill(blk_scale.begin(), blk_scale.end(), kActScale);
     }
   }
-  const size_t ws = c->fast() ? 2 : (c->x3() ? 6 : 4);   // bytes per weight-matrix element (bf16 / 3 bf16 planes / fp32)
+  // ---- FAST16: the range the weights PROVE for every tensor the context stores in 2 bytes, per block (header: d3dp_fast_operands)
+  //   LayerNorm outputs      L1, L2  = max_k sqrt(C-1) |gamma_k| + |beta_k|
+  //   q, k, v                b_qkv   = max_n sum_k |Wqkv[n,k]| (sqrt(C-1) |gamma1_k| + |beta1_k|) + |bqkv_n|;  b_v: rows n >= 2C alone
+  //   attention output       <= b_v  (a convex combination of v rows; the probabilities themselves are <= 1)
+  //   proj output            b_proj  = max_n sum_k |Wproj[n,k]| b_v + |bproj_n|
+  //   MLP hidden             b_h     = the b_qkv form with Wfc1 / norm2  (|GELU(x)| <= |x|; it also bounds the pre-activation the
+  //                                    streaming Linear parks as fp16 in front of the GELU)
+  //   fc2 output             b_fc2   = max_n sum_k |Wfc2[n,k]| b_h + |bfc2_n|
+  //   the four matrices      max |w|
+  // The context's bound is the largest of these over all blocks.  Below 65504 and finite: fp16 operands, unscaled.  Otherwise
+  // (or with a non-finite weight): the bf16 kernels, i.e. exactly what a D3DP_MODE_FAST context launches on these weights --
+  // never an error, never an inf that FAST would not give.  Both types are 2 bytes, so nothing below depends on the outcome
+  // but the conversion kernel's and the launchers' type argument.
+  if (c->fast16()) {
+    const size_t nb = 2 * (size_t)g.depth;
+    unsigned* dbound = nullptr;
+    HIP_TRY(hipMalloc((void**)&dbound, nb * kF16Slots * sizeof(unsigned)));
+    struct Free { unsigned* p; ~Free() { (void)hipFree(p); } } free_dbound{dbound};
+    HIP_TRY(hipMemsetAsync(dbound, 0, nb * kF16Slots * sizeof(unsigned), st));
+    const double sq = std::sqrt((double)C - 1.0);
+    for (int kind = 0; kind < 2; ++kind)
+      for (int d = 0; d < g.depth; ++d) {
+        const d3dp_block_weights& b = (kind == 0 ? w->ste : w->tte)[d];
+        if (!b.norm1_w || !b.norm1_b || !b.qkv_w || !b.qkv_b || !b.proj_w || !b.proj_b || !b.norm2_w || !b.norm2_b || !b.fc1_w ||
+            !b.fc1_b || !b.fc2_w || !b.fc2_b) return fail(D3DP_EINVAL, "d3dp_set_weights: a weight pointer is null");
+        unsigned* o = dbound + ((size_t)kind * g.depth + d) * kF16Slots;
+        const dim3 blk(256);
+        hipLaunchKernelGGL(fast16_bound_kernel, dim3((3 * (unsigned)C + 3) / 4), blk, 0, st, b.qkv_w, b.norm1_w, b.norm1_b,
+                           (const unsigned*)nullptr, b.qkv_b, 3 * (int)C, (int)C, sq, 2 * (int)C, o + 1, o + 2, o + 0, o + 7);
+        hipLaunchKernelGGL(fast16_bound_kernel, dim3(((unsigned)C + 3) / 4), blk, 0, st, b.proj_w, (const float*)nullptr,
+                           (const float*)nullptr, (const unsigned*)(o + 2), b.proj_b, (int)C, (int)C, 0.0, 0, o + 3,
+                           (unsigned*)nullptr, (unsigned*)nullptr, o + 8);
+        hipLaunchKernelGGL(fast16_bound_kernel, dim3(((unsigned)Hd + 3) / 4), blk, 0, st, b.fc1_w, b.norm2_w, b.norm2_b,
+                           (const unsigned*)nullptr, b.fc1_b, (int)Hd, (int)C, sq, 0, o + 5, (unsigned*)nullptr, o + 4, o + 9);
+        hipLaunchKernelGGL(fast16_bound_kernel, dim3(((unsigned)C + 3) / 4), blk, 0, st, b.fc2_w, (const float*)nullptr,
+                           (const float*)nullptr, (const unsigned*)(o + 5), b.fc2_b, (int)C, (int)Hd, 0.0, 0, o + 6,
+                           (unsigned*)nullptr, (unsigned*)nullptr, o + 10);
+      }
+    HIP_TRY(hipGetLastError());
+    std::vector<float> hb(nb * kF16Slots);
+    HIP_TRY(hipMemcpyAsync(hb.data(), dbound, hb.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float worst = 0.f;
+    bool finite = true;
+    for (const float v : hb) {
+      if (!(v < INFINITY)) finite = false;               // (inf, or the nan a nan weight leaves)
+      else worst = std::max(worst, v);
+    }
+    c->fast_bound = finite ? worst : INFINITY;
+    c->fast_f16 = (finite && worst < 65504.0f) ? 1 : 0;
+  }
+  const size_t ws = c->fast() ? 2 : (c->x3() ? 6 : 4);   // bytes per weight-matrix element (bf16 or fp16 / 3 bf16 planes / fp32)
   // ---- arena layout ----
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
@@ -711,7 +829,7 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
   }
   for (size_t i = 0; i < items.size(); ++i) {
     auto& it = items[i];
-    if (it.mat && c->fast()) launch_to_bf16((const float*)it.src, c->arena + it.off, it.n, st);
+    if (it.mat && c->fast()) launch_to_bf16((const float*)it.src, c->arena + it.off, it.n, st, c->fast_f16);
     else if (it.mat && c->x3()) d3dp_launch_split3((const float*)it.src, c->arena + it.off, it.n, st);
     else if (it.mat && c->x2()) d3dp_launch_split2((const float*)it.src, c->arena + it.off, it.n, 1.0f / unscale[i], st);
     else HIP_TRY(hipMemcpyAsync(c->arena + it.off, it.src, it.n * 4, hipMemcpyDeviceToDevice, st));
@@ -830,7 +948,7 @@ int d3dp_denoise(d3dp_ctx* c, const float* x2d, const float* x_t, const int64_t*
     }
     {
       Scope s(c, P_HEAD, st);    // x += fc2 out; Temporal_norm; head LayerNorm; Linear(C,3)
-      LAUNCH_TRY(d3dp_launch_head(c->fast() ? 1 : 0, x, fold ? nullptr : y1, fold ? nullptr : y, c->tnw, c->tnb, g.eps_block, c->hnw, c->hnb, g.eps_head, c->hw, c->hb,
+      LAUNCH_TRY(d3dp_launch_head(c->fast() ? c->act() : 0, x, fold ? nullptr : y1, fold ? nullptr : y, c->tnw, c->tnb, g.eps_block, c->hnw, c->hnb, g.eps_head, c->hw, c->hb,
                                   out + (size_t)seq0 * FJ * 3, Tc, C, st, FJ, SP));
     }
     seq0 += n;
@@ -857,6 +975,14 @@ int d3dp_exact_scales(const d3dp_ctx* c, float* s_kv, float* s_hidden, int32_t* 
     if (s_hidden) s_hidden[i] = b.s_h;
   }
   if (implementation) *implementation = c->exact() ? c->exact_impl : -1;
+  return D3DP_OK;
+}
+
+int d3dp_fast_operands(const d3dp_ctx* c, int32_t* type, float* bound) {
+  if (!c || !type || !bound) return fail(D3DP_EINVAL, "d3dp_fast_operands: null argument");
+  if (!c->weights_set) return fail(D3DP_ESTATE, "d3dp_fast_operands: weights not set");
+  *type = c->fast() ? c->fast_f16 : -1;
+  *bound = c->fast16() ? c->fast_bound : 0.f;
   return D3DP_OK;
 }
 
@@ -949,11 +1075,11 @@ int d3dp_jpma_winners(const float* pred, const float* traj, const float* cam, co
 int d3dp_op_linear(int32_t mode, int32_t epi, const void* A, const void* W, const float* bias, void* out, int32_t M,
                    int32_t N, int32_t K, void* stream) {
   if (!A || !W || !bias || !out) return fail(D3DP_EINVAL, "d3dp_op_linear: null argument");
-  if (mode == D3DP_MODE_FAST) {
-    // epi 0/1: the persistent streaming kernel the denoiser uses (epi | 16 selects its fp32-output form)
+  if (mode == D3DP_MODE_FAST || mode == 4) {
+    // epi 0/1: the persistent streaming kernel the denoiser uses (epi | 16 selects its fp32-output form); mode 4: on fp16 operands
     const int e = epi & 3, f32 = (epi & 16) != 0;
     if (e == EPI_RESID || (epi & ~19)) return fail(D3DP_EINVAL, "d3dp_op_linear: FAST mode has epilogues 0, 1 and 0|16");
-    LAUNCH_TRY(d3dp_launch_linear_bf16_stream(e, f32, A, W, bias, out, M, N, K, (hipStream_t)stream));
+    LAUNCH_TRY(d3dp_launch_linear_bf16_stream(e, f32, A, W, bias, out, M, N, K, (hipStream_t)stream, mode == 4));
   }
   else if (mode == 2) {
     // split-bf16: A, W are three bf16 planes each (d3dp_op_split3); epi 0 -> fp32 out, epi 1 -> three bf16 planes out
@@ -1007,7 +1133,8 @@ int d3dp_op_attention(int32_t act_bf16, int32_t impl, int32_t axis, const void* 
                       int32_t J, int32_t C, int32_t heads, void* stream) {
   if (!qkv || !out || n_bh < 1) return fail(D3DP_EINVAL, "d3dp_op_attention: bad argument");
   hipStream_t st = (hipStream_t)stream;
-  if (act_bf16 != 0 && act_bf16 != 1) return fail(D3DP_EINVAL, "act_bf16 must be 0 or 1");
+  if (act_bf16 != 0 && act_bf16 != 1 && act_bf16 != 4) return fail(D3DP_EINVAL, "act_bf16 must be 0, 1 or 4 (fp16)");
+  const int f16 = act_bf16 == 4;
   if (impl == 2) {       // EXACT mode: split-fp16 operands on the fp16 matrix cores, fp32 in / fp32 out
     if (act_bf16) return fail(D3DP_EINVAL, "split-fp16 attention takes fp32 activations");
     // the kernels read the packed rows the EXACT qkv Linear writes: repack the fp32 rows into a stream-ordered temporary
@@ -1021,13 +1148,13 @@ int d3dp_op_attention(int32_t act_bf16, int32_t impl, int32_t axis, const void* 
     LAUNCH_TRY(rc);
   } else if (axis == 0 && impl == 1) {
     if (!act_bf16) return fail(D3DP_EINVAL, "MFMA spatial attention needs bf16 activations");
-    LAUNCH_TRY(d3dp_launch_attn_spatial_bf16(qkv, out, n_bh * F, spatial_map(F, J), C, heads, st));
+    LAUNCH_TRY(d3dp_launch_attn_spatial_bf16(qkv, out, n_bh * F, spatial_map(F, J), C, heads, st, f16));
   } else if (axis == 0) LAUNCH_TRY(d3dp_launch_attn_rows(act_bf16, qkv, out, n_bh * F, spatial_map(F, J), C, heads, st));
   else if (impl == 1 && !act_bf16) {
     LAUNCH_TRY(d3dp_launch_attn_temporal_f32(0, qkv, out, n_bh * J, temporal_map(F, J), C, heads, st));   // fp32 MFMA
   } else if (impl == 1) {
     if (!act_bf16) return fail(D3DP_EINVAL, "MFMA temporal attention needs bf16 activations");
-    LAUNCH_TRY(d3dp_launch_attn_temporal_bf16(qkv, out, n_bh * J, temporal_map(F, J), C, heads, st));
+    LAUNCH_TRY(d3dp_launch_attn_temporal_bf16(qkv, out, n_bh * J, temporal_map(F, J), C, heads, st, f16));
   } else LAUNCH_TRY(d3dp_launch_attn_rows(act_bf16, qkv, out, n_bh * J, temporal_map(F, J), C, heads, st));
   HIP_TRY(hipGetLastError());
   return D3DP_OK;

@@ -436,10 +436,12 @@ __device__ __forceinline__ int sperm(int q) {   // q = ni*16 + i in [0,64)
 // contention between compute waves, 0.375 instead of 0.5 LDS fragment reads per MFMA).
 // WIDE is a name tag only (same code): the qkv Linear (N = 3K) is instantiated as its own kernel symbol so that
 // rocprofv3 --stats reports it separately from the proj Linear, which shares EPI / OutT / NK with it.
-template <int EPI, typename OutT, int NK, int MI, int WIDE = 0>
-__global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(const bf16* __restrict__ A, const bf16* __restrict__ W,
+template <typename E, int EPI, typename OutT, int NK, int MI, int WIDE = 0>
+__global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(const E* __restrict__ A, const E* __restrict__ W,
                                                                const float* __restrict__ bias, OutT* __restrict__ out,
                                                                int M, int N, int tiles_n, int total_tiles) {
+  using e4 = typename Op2<E>::x4;
+  using e8 = typename Op2<E>::x8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sbias = reinterpret_cast<float*>(smem + SNSTAGE * SSTAGE);
   constexpr int K = NK * SBK;
@@ -470,7 +472,7 @@ __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(c
       for (int i = 0; i < 8; ++i) {
         const int row = lw * 64 + i * 8 + lrow;
         const int gr = min(m0 + row, M - 1);
-        const bf16* src = A + (size_t)gr * K + ks * SBK + swz(row, lslot) * 8;
+        const E* src = A + (size_t)gr * K + ks * SBK + swz(row, lslot) * 8;
         __builtin_amdgcn_global_load_lds(GPTR(src), LPTR(stage + (lw * 8 + i) * 1024), 16, 0, 0);
       }
 #pragma unroll
@@ -478,7 +480,7 @@ __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(c
         const int row = lw * 32 + i * 8 + lrow;                    // LDS row of the W slab
         const int wrow = (row & 64) + sperm(row & 63);              // output column it carries
         const int gr = min(n0 + wrow, N - 1);
-        const bf16* src = W + (size_t)gr * K + ks * SBK + swz(row, lslot) * 8;
+        const E* src = W + (size_t)gr * K + ks * SBK + swz(row, lslot) * 8;
         __builtin_amdgcn_global_load_lds(GPTR(src), LPTR(stage + SA_BYTES + (lw * 4 + i) * 1024), 16, 0, 0);
       }
     };
@@ -503,8 +505,8 @@ __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(c
   // instead of a per-tile burst in which every CU of the (phase-locked) persistent grid hits the HBM write path at once.
   // (GELU form: the parked pre-activation is fp16, not bf16 -- 11 significand bits, so the rounding in front of the
   //  nonlinearity is an eighth of the bf16 rounding behind it instead of a second rounding of the same size)
-  using pend_t = typename std::conditional<EPI == EPI_GELU, f16x4, bf16x4>::type;
-  using pelt_t = typename std::conditional<EPI == EPI_GELU, f16, bf16>::type;
+  using pend_t = typename std::conditional<EPI == EPI_GELU, f16x4, e4>::type;
+  using pelt_t = typename std::conditional<EPI == EPI_GELU, f16, E>::type;
   pend_t pend[NU];
   int pm0 = 0, pn0 = 0;
   bool have_pend = false;
@@ -514,11 +516,11 @@ __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(c
   auto drain_one = [&](int u) {
     const int m = pm0 + wr * (MI * 16) + (u >> 2) * 16 + 4 * fg + (u & 3);
     const int n = pn0 + wc * 64 + 4 * fi;
-    bf16x4 v;
+    e4 v;
     if constexpr (EPI == EPI_GELU) {
       const f16x4 pre = pend[0];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (bf16)gelu_fast((float)pre[e]);
+      for (int e = 0; e < 4; ++e) v[e] = (E)gelu_fast((float)pre[e]);
       // keep the activation OUT of the store's bounds branch (LLVM would sink it there, behind the MFMA block)
       asm volatile("" : "+v"(v));
     } else {
@@ -526,7 +528,7 @@ __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(c
     }
     if (m < M && n < N) {
       if constexpr (sizeof(OutT) == 2) {
-        *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(out) + (size_t)m * N + n) = v;
+        *reinterpret_cast<e4*>(reinterpret_cast<E*>(out) + (size_t)m * N + n) = v;
       } else {
         *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + (size_t)m * N + n) =
             make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
@@ -544,22 +546,22 @@ __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(c
     const char* sw = sa + SA_BYTES;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      bf16x8 af[MI], wf[4];
+      e8 af[MI], wf[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int rw = wc * 64 + i * 16 + fi;
-        wf[i] = *reinterpret_cast<const bf16x8*>(sw + rw * 128 + swz(rw, kk * 4 + fg) * 16);
+        wf[i] = *reinterpret_cast<const e8*>(sw + rw * 128 + swz(rw, kk * 4 + fg) * 16);
       }
 #pragma unroll
       for (int i = 0; i < MI; ++i) {
         const int ra = wr * (MI * 16) + i * 16 + fi;
-        af[i] = *reinterpret_cast<const bf16x8*>(sa + ra * 128 + swz(ra, kk * 4 + fg) * 16);
+        af[i] = *reinterpret_cast<const e8*>(sa + ra * 128 + swz(ra, kk * 4 + fg) * 16);
       }
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni)
-          acc[mi][ni] = D3DP_MFMA_16x16x32_BF16(af[mi], wf[ni], acc[mi][ni]);
+          acc[mi][ni] = Op2<E>::mfma(af[mi], wf[ni], acc[mi][ni]);
     }
   };
   __builtin_amdgcn_s_setprio(1);
@@ -620,54 +622,61 @@ __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(c
   }
 }
 
-template <int EPI, typename OutT, int NK, int MI>
+template <typename E, int EPI, typename OutT, int NK, int MI>
 int launch_stream_nk_mi(const void* A, const void* W, const float* bias, void* out, int M, int N, hipStream_t st) {
   const int tm = (M + SBM - 1) / SBM, tn = (N + SBN - 1) / SBN;
   const int total = tm * tn;
-  void (*kern)(const bf16*, const bf16*, const float*, OutT*, int, int, int, int) =
-      gemm_bf16_stream_kernel<EPI, OutT, NK, MI, 0>;
+  void (*kern)(const E*, const E*, const float*, OutT*, int, int, int, int) =
+      gemm_bf16_stream_kernel<E, EPI, OutT, NK, MI, 0>;
   if constexpr (EPI == EPI_BIAS && sizeof(OutT) == 2 && NK == 8) {
-    if (N == 3 * NK * SBK) kern = gemm_bf16_stream_kernel<EPI, OutT, NK, MI, 1>;
+    if (N == 3 * NK * SBK) kern = gemm_bf16_stream_kernel<E, EPI, OutT, NK, MI, 1>;
   }
   static PerDeviceOnce once[2];                       // per kernel variant: LDS opt-in, then the device's CU count
-  const int which = (kern == gemm_bf16_stream_kernel<EPI, OutT, NK, MI, 0>) ? 0 : 1;
+  const int which = (kern == gemm_bf16_stream_kernel<E, EPI, OutT, NK, MI, 0>) ? 0 : 1;
   const int n_cu = once[which].get([&](int dev) {
     return d3dp_lds_opt_in(reinterpret_cast<const void*>(kern), SLDS_BYTES) < 0 ? -3 : d3dp_cu_count(dev);
   });
   if (n_cu < 0) return -3;
   const int grid = total < n_cu ? total : n_cu;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(MI == 4 ? 768 : 512), SLDS_BYTES, st, (const bf16*)A, (const bf16*)W, bias,
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(MI == 4 ? 768 : 512), SLDS_BYTES, st, (const E*)A, (const E*)W, bias,
                      (OutT*)out, M, N, tn, total);
   return 0;
 }
 
-template <int EPI, typename OutT, int NK>
+template <typename E, int EPI, typename OutT, int NK>
 int launch_stream_nk(const void* A, const void* W, const float* bias, void* out, int M, int N, hipStream_t st) {
   // MI = 8 (four compute waves of 128x64, one per SIMD) was measured: slower on qkv (a lone wave cannot hide its own
   // ds_read latency), within noise elsewhere -- not instantiated.
-  return launch_stream_nk_mi<EPI, OutT, NK, 4>(A, W, bias, out, M, N, st);
+  return launch_stream_nk_mi<E, EPI, OutT, NK, 4>(A, W, bias, out, M, N, st);
 }
 
-template <int EPI, typename OutT>
+template <typename E, int EPI, typename OutT>
 int launch_stream(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, hipStream_t st) {
   switch (K / SBK) {
-    case 1: return launch_stream_nk<EPI, OutT, 1>(A, W, bias, out, M, N, st);
-    case 2: return launch_stream_nk<EPI, OutT, 2>(A, W, bias, out, M, N, st);
-    case 4: return launch_stream_nk<EPI, OutT, 4>(A, W, bias, out, M, N, st);
-    case 8: return launch_stream_nk<EPI, OutT, 8>(A, W, bias, out, M, N, st);
-    case 16: return launch_stream_nk<EPI, OutT, 16>(A, W, bias, out, M, N, st);
+    case 1: return launch_stream_nk<E, EPI, OutT, 1>(A, W, bias, out, M, N, st);
+    case 2: return launch_stream_nk<E, EPI, OutT, 2>(A, W, bias, out, M, N, st);
+    case 4: return launch_stream_nk<E, EPI, OutT, 4>(A, W, bias, out, M, N, st);
+    case 8: return launch_stream_nk<E, EPI, OutT, 8>(A, W, bias, out, M, N, st);
+    case 16: return launch_stream_nk<E, EPI, OutT, 16>(A, W, bias, out, M, N, st);
     default: return -1;
   }
 }
 
 }  // namespace
 
-// out[M,N] = epi(A W^T + bias); epi in {EPI_BIAS, EPI_GELU}; out bf16 or fp32.
-int d3dp_launch_linear_bf16_stream(int epi, int out_f32, const void* A, const void* W, const float* bias, void* out,
-                                   int M, int N, int K, hipStream_t st) {
-  if (K % SBK != 0 || N % 4 != 0 || N > SBIAS_MAX || M <= 0) return -1;
-  if (epi == EPI_BIAS && out_f32) return launch_stream<EPI_BIAS, float>(A, W, bias, out, M, N, K, st);
-  if (epi == EPI_BIAS && !out_f32) return launch_stream<EPI_BIAS, bf16>(A, W, bias, out, M, N, K, st);
-  if (epi == EPI_GELU && !out_f32) return launch_stream<EPI_GELU, bf16>(A, W, bias, out, M, N, K, st);
+// out[M,N] = epi(A W^T + bias); epi in {EPI_BIAS, EPI_GELU}; operands bf16 (f16 == 0) or IEEE fp16 (f16 == 1); out of the
+// operand type or fp32.
+template <typename E>
+static int linear_stream(int epi, int out_f32, const void* A, const void* W, const float* bias, void* out, int M, int N, int K,
+                         hipStream_t st) {
+  if (epi == EPI_BIAS && out_f32) return launch_stream<E, EPI_BIAS, float>(A, W, bias, out, M, N, K, st);
+  if (epi == EPI_BIAS && !out_f32) return launch_stream<E, EPI_BIAS, E>(A, W, bias, out, M, N, K, st);
+  if (epi == EPI_GELU && !out_f32) return launch_stream<E, EPI_GELU, E>(A, W, bias, out, M, N, K, st);
   return -1;
+}
+int d3dp_launch_linear_bf16_stream(int epi, int out_f32, const void* A, const void* W, const float* bias, void* out,
+                                   int M, int N, int K, hipStream_t st, int f16) {
+  if (K % SBK != 0 || N % 4 != 0 || N > SBIAS_MAX || M <= 0) return -1;
+  return f16 ? linear_stream<_Float16>(epi, out_f32, A, W, bias, out, M, N, K, st)
+             : linear_stream<__bf16>(epi, out_f32, A, W, bias, out, M, N, K, st);
 }

@@ -39,8 +39,9 @@ inline int d3dp_lds_opt_in(const void* kern, int bytes) {
 enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_PARTIAL = 3, EPI_QKV_PACK = 4, EPI_RESID_LN = 5, EPI_GELU_LN = 6 };
 
 // ---- gemm.hip ----------------------------------------------------------------------------------
+// (f16: the 2-byte type of A, W and a 2-byte out -- 0 = bf16, 1 = IEEE fp16)
 int d3dp_launch_linear_bf16_stream(int epi, int out_f32, const void* A, const void* W, const float* bias, void* out,
-                                   int M, int N, int K, hipStream_t st);
+                                   int M, int N, int K, hipStream_t st, int f16 = 0);
 int d3dp_launch_linear_bf16x3(int epi, const void* A3, const void* W3, const float* bias, float* outf, void* out3, int M,
                               int N, int K, hipStream_t st);
 void d3dp_launch_split3(const float* src, void* dst, size_t n, hipStream_t st);
@@ -161,8 +162,9 @@ struct SeqMap { int n_tok, inner, outer_stride, inner_stride, tok_stride; };
 // (any sequence length; amax: optional absmax slot of an fp32 output, one atomicMax per workgroup)
 int d3dp_launch_attn_rows(int act_bf16, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
                           hipStream_t st, unsigned* amax = nullptr);
+// (the MFMA kernels of the FAST modes -- f16: 0 = bf16 rows in and out, 1 = IEEE fp16; d3dp_launch_attn_rows: act 1 / act 4)
 int d3dp_launch_attn_temporal_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
-                                   hipStream_t st);
+                                   hipStream_t st, int f16 = 0);
 int d3dp_launch_attn_temporal_f32(int act, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
                                   hipStream_t st);
 // split-fp16 attention: `qkv` = PACKED rows of 12 C bytes (q fp32 | k hi | k lo | v hi | v lo), written by the qkv Linear
@@ -171,7 +173,8 @@ int d3dp_launch_attn_temporal_f32(int act, const void* qkv, void* out, int n_seq
 int d3dp_launch_attn_x2(int act, int axis, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
                         float act_scale, hipStream_t st);
 void d3dp_launch_qkv_pack_x2(const float* src, void* dst, size_t T, int C, float act_scale, hipStream_t st);
-int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st);
+int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st,
+                                  int f16 = 0);
 
 // ---- pointwise.hip -----------------------------------------------------------------------------
 int d3dp_launch_time_mlp(const int64_t* t, const float* freq, const float* w1, const float* b1, const float* w2,
@@ -183,7 +186,8 @@ int d3dp_launch_embed_ln(int act_bf16, const float* x2d, const float* x3d, const
 // (SP: rows per sequence in x / xn, >= F J; 0 = F J.  Rows F J .. SP - 1 of every sequence are finite filler.)
 // xn = LN(x)
 // (residual adds: ln normalises x + yadd (writing the sum back only if write_x); ln2 / head form (x + yadd0) + yadd;
-//  yadd has the activation type: bf16 in FAST mode, fp32 in EXACT mode)
+//  yadd has the activation type: bf16 in FAST mode, fp16 in FAST16 mode, fp32 in EXACT mode.
+//  act_bf16 is the activation code of the row launchers: 0 fp32, 1 bf16, 2 split-bf16 planes, 3 split-fp16 planes, 4 IEEE fp16)
 int d3dp_launch_ln(int act_bf16, float* x, const void* yadd, int write_x, const float* w, const float* b, float eps,
                    void* xn, int T, int C, hipStream_t st);
 // x = LN_a(x) (+ pos[f]) in place ; xn = LN_b(x)   (shared Spatial/Temporal norm fused with the next block's norm1)

@@ -9,6 +9,8 @@
 //   ln2_kernel      : x = LN_shared(x) [+ Temporal_pos[f]] ; xn = LN_next(x)   (mixste.py:243,250,257,269,273
 //                     fused with the following block's norm1)
 //   head_kernel     : Temporal_norm -> head LayerNorm(eps 1e-5) -> Linear(C,3) (mixste.py:257/273, :207-210)
+#include <type_traits>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -42,11 +44,12 @@ template <int C> struct Row {
       for (int i = 0; i < NV; ++i) v[i] = p[i * 64 + lane];
     }
   }
-  static __device__ __forceinline__ void load(const bf16* p, int lane, float* v) {
+  template <typename E, typename = typename std::enable_if<sizeof(E) == 2>::type>   // (the 2-byte activation types: bf16, f16)
+  static __device__ __forceinline__ void load(const E* p, int lane, float* v) {
     if constexpr (V4) {
 #pragma unroll
       for (int g = 0; g < NV / 4; ++g) {
-        bf16x4 a = *reinterpret_cast<const bf16x4*>(p + (g * 64 + lane) * 4);
+        typename Op2<E>::x4 a = *reinterpret_cast<const typename Op2<E>::x4*>(p + (g * 64 + lane) * 4);
         v[g * 4] = (float)a[0]; v[g * 4 + 1] = (float)a[1]; v[g * 4 + 2] = (float)a[2]; v[g * 4 + 3] = (float)a[3];
       }
     } else {
@@ -68,11 +71,12 @@ template <int C> struct Row {
       load(p, lane, v);
     }
   }
-  static __device__ __forceinline__ void load_nt(const bf16* p, int lane, float* v) {
+  template <typename E, typename = typename std::enable_if<sizeof(E) == 2>::type>
+  static __device__ __forceinline__ void load_nt(const E* p, int lane, float* v) {
     if constexpr (V4) {
 #pragma unroll
       for (int g = 0; g < NV / 4; ++g) {
-        const bf16x4 a = __builtin_nontemporal_load(reinterpret_cast<const bf16x4*>(p + (g * 64 + lane) * 4));
+        const typename Op2<E>::x4 a = __builtin_nontemporal_load(reinterpret_cast<const typename Op2<E>::x4*>(p + (g * 64 + lane) * 4));
         v[g * 4] = (float)a[0]; v[g * 4 + 1] = (float)a[1]; v[g * 4 + 2] = (float)a[2]; v[g * 4 + 3] = (float)a[3];
       }
     } else {
@@ -100,16 +104,24 @@ template <int C> struct Row {
       for (int i = 0; i < NV; ++i) p[i * 64 + lane] = v[i];
     }
   }
-  static __device__ __forceinline__ void store(bf16* p, int lane, const float* v) {
+  template <typename E, typename = typename std::enable_if<sizeof(E) == 2>::type>
+  static __device__ __forceinline__ void store(E* p, int lane, const float* v) {
     if constexpr (V4) {
 #pragma unroll
       for (int g = 0; g < NV / 4; ++g) {
-        bf16x4 a = {(bf16)v[g * 4], (bf16)v[g * 4 + 1], (bf16)v[g * 4 + 2], (bf16)v[g * 4 + 3]};
-        *reinterpret_cast<bf16x4*>(p + (g * 64 + lane) * 4) = a;
+        typename Op2<E>::x4 a = {(E)v[g * 4], (E)v[g * 4 + 1], (E)v[g * 4 + 2], (E)v[g * 4 + 3]};
+        *reinterpret_cast<typename Op2<E>::x4*>(p + (g * 64 + lane) * 4) = a;
       }
     } else {
 #pragma unroll
-      for (int i = 0; i < NV; ++i) p[i * 64 + lane] = (bf16)v[i];
+      for (int i = 0; i < NV; ++i) {
+        float t = v[i];
+        // fp16: keep the fp32 value a value of its own, so that the cast below stays the round-to-nearest-even convert of the
+        // fp32 result that every other store of this type is -- left alone, the compiler merges `(f16)fmaf(..)` of norm() into
+        // v_fma_mixlo_f16, which rounds the exact fma ONCE: other bits than the 4-wide path's at the fp16 ties
+        if constexpr (std::is_same<E, f16>::value) asm volatile("" : "+v"(t));
+        p[i * 64 + lane] = (E)t;
+      }
     }
   }
   // split-bf16 activation: three planes `plane` elements apart
@@ -192,7 +204,7 @@ template <int C> struct Row {
 // Residual adds (mixste.py:113-115) ride on the row-wise kernels.  ln_kernel normalises x + yadd; it writes the sum
 // back only if write_x (the denoiser does NOT: ln2/head re-form (x + yadd0) + yadd from the untouched x, which saves
 // one fp32 row write + read per token and block).
-// activation store: XN = float / bf16 (one plane) or b3 (three bf16 planes, `plane` elements apart)
+// activation store: XN = float / bf16 / f16 (one plane) or b3 (three bf16 planes, `plane` elements apart)
 template <int C, typename XN> struct ActOut {
   using ptr = XN*;
   static __device__ __forceinline__ void st(ptr base, size_t, size_t off, int lane, const float* v) {
@@ -605,7 +617,7 @@ int d3dp_launch_time_mlp(const int64_t* t, const float* freq, const float* w1, c
 }
 
 // `act`: 0 = fp32 activations (y fp32), 1 = bf16 activations (y bf16), 2 = split-bf16 activation planes (y fp32),
-//        3 = split-fp16 activation planes (y fp32)
+//        3 = split-fp16 activation planes (y fp32), 4 = IEEE fp16 activations (y fp16)
 int d3dp_launch_embed_ln(int act_bf16, const float* x2d, const float* x3d, const float* temb, const float* ew,
                          const float* eb, const float* spos, const float* lnw, const float* lnb, float eps, float* x,
                          void* xn, int seq0, int n_seq, int H, int F, int J, int C, hipStream_t st, int SP) {
@@ -622,6 +634,7 @@ int d3dp_launch_embed_ln(int act_bf16, const float* x2d, const float* x3d, const
   const dim3 gk((T + 4 * kRowTokens - 1) / (4 * kRowTokens));     // kRowTokens tokens per wave
   DISPATCH_C(C,
     if (act_bf16 == 1) hipLaunchKernelGGL((embed_ln_kernel<CC, bf16>), gk, blk, 0, st, x2d, x3d, temb, ew, eb, spos, lnw, lnb, eps, x, (bf16*)xn, plane, seq0, n_seq, H, F, J, SP);
+    else if (act_bf16 == 4) hipLaunchKernelGGL((embed_ln_kernel<CC, f16>), gk, blk, 0, st, x2d, x3d, temb, ew, eb, spos, lnw, lnb, eps, x, (f16*)xn, plane, seq0, n_seq, H, F, J, SP);
     else if (act_bf16 == 2) hipLaunchKernelGGL((embed_ln_kernel<CC, b3>), gk, blk, 0, st, x2d, x3d, temb, ew, eb, spos, lnw, lnb, eps, x, (bf16*)xn, plane, seq0, n_seq, H, F, J, SP);
     else if (act_bf16 == 3) hipLaunchKernelGGL((embed_ln_kernel<CC, h2>), gk, blk, 0, st, x2d, x3d, temb, ew, eb, spos, lnw, lnb, eps, x, (f16*)xn, plane, seq0, n_seq, H, F, J, SP);
     else hipLaunchKernelGGL((embed_ln_kernel<CC, float>), gk, blk, 0, st, x2d, x3d, temb, ew, eb, spos, lnw, lnb, eps, x, (float*)xn, plane, seq0, n_seq, H, F, J, SP))
@@ -639,6 +652,7 @@ int d3dp_launch_ln(int act_bf16, float* x, const void* yadd, int write_x, const 
   }
   DISPATCH_C(C,
     if (act_bf16 == 1) hipLaunchKernelGGL((ln_kernel<CC, bf16, bf16>), g, blk, 0, st, x, (const bf16*)yadd, w, b, eps, (bf16*)xn, plane, T, write_x);
+    else if (act_bf16 == 4) hipLaunchKernelGGL((ln_kernel<CC, f16, f16>), g, blk, 0, st, x, (const f16*)yadd, w, b, eps, (f16*)xn, plane, T, write_x);
     else if (act_bf16 == 2) hipLaunchKernelGGL((ln_kernel<CC, b3, float>), g, blk, 0, st, x, (const float*)yadd, w, b, eps, (bf16*)xn, plane, T, write_x);
     else if (act_bf16 == 3) hipLaunchKernelGGL((ln_kernel<CC, h2, float>), g, blk, 0, st, x, (const float*)yadd, w, b, eps, (f16*)xn, plane, T, write_x);
     else hipLaunchKernelGGL((ln_kernel<CC, float, float>), g, blk, 0, st, x, (const float*)yadd, w, b, eps, (float*)xn, plane, T, write_x))
@@ -657,6 +671,7 @@ int d3dp_launch_ln2(int act_bf16, float* x, const void* yadd0, const void* yadd,
   }
   DISPATCH_C(C,
     if (act_bf16 == 1) hipLaunchKernelGGL((ln2_kernel<CC, bf16, bf16>), g, blk, 0, st, x, (const bf16*)yadd0, (const bf16*)yadd, wa, ba, pos, wb, bb, eps, (bf16*)xn, plane, T, F, J, SP);
+    else if (act_bf16 == 4) hipLaunchKernelGGL((ln2_kernel<CC, f16, f16>), g, blk, 0, st, x, (const f16*)yadd0, (const f16*)yadd, wa, ba, pos, wb, bb, eps, (f16*)xn, plane, T, F, J, SP);
     else if (act_bf16 == 2) hipLaunchKernelGGL((ln2_kernel<CC, b3, float>), g, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, pos, wb, bb, eps, (bf16*)xn, plane, T, F, J, SP);
     else if (act_bf16 == 3) hipLaunchKernelGGL((ln2_kernel<CC, h2, float>), g, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, pos, wb, bb, eps, (f16*)xn, plane, T, F, J, SP);
     else hipLaunchKernelGGL((ln2_kernel<CC, float, float>), g, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, pos, wb, bb, eps, (float*)xn, plane, T, F, J, SP))
@@ -676,6 +691,7 @@ int d3dp_launch_head(int act_bf16, const float* x, const void* yadd0, const void
   const dim3 gk((T + 4 * kRowTokens - 1) / (4 * kRowTokens));     // kRowTokens tokens per wave
   DISPATCH_C(C,
     if (act_bf16 == 1) hipLaunchKernelGGL((head_kernel<CC, bf16>), gk, blk, 0, st, x, (const bf16*)yadd0, (const bf16*)yadd, wa, ba, eps_a, wh, bh, eps_h, w, b, out, T, FJ, SP);
+    else if (act_bf16 == 4) hipLaunchKernelGGL((head_kernel<CC, f16>), gk, blk, 0, st, x, (const f16*)yadd0, (const f16*)yadd, wa, ba, eps_a, wh, bh, eps_h, w, b, out, T, FJ, SP);
     else hipLaunchKernelGGL((head_kernel<CC, float>), gk, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, eps_a, wh, bh, eps_h, w, b, out, T, FJ, SP))
   return 0;
 }

@@ -8,8 +8,11 @@ goes through libd3dp_hip.so (include/d3dp_hip.h).  There is no PyTorch/CPU fallb
 
 Extensions over the reference API (default-off):
   * ``noise=[...]`` / ``generator=`` on the samplers for fixed-noise parity tests;
-  * ``numerics='exact'|'fast'`` (or ``args.numerics`` / env ``D3DP_NUMERICS``): exact = fp32 MFMA
-    (<= 1e-3 mm vs the reference), fast = bf16 MFMA with fp32 accumulation.
+  * ``numerics='exact'|'fast'|'fast16'|'train'`` (or ``args.numerics`` / env ``D3DP_NUMERICS``): exact = Linears on split-fp16
+    operands, three fp16-MFMA passes, fp32 everything else (<= 1e-3 mm vs the reference); fast = bf16 operands, one bf16-MFMA
+    pass, fp32 accumulation (2-6 mm); fast16 = fast's kernels on IEEE fp16 operands (0.3 mm at fast's rate) when the weights
+    prove that nothing can reach fp16's 65504, fast's bf16 kernels otherwise (``MixSTE2.fast_operands()``); train = fp32 weights
+    and activations, differentiable (the training step).
 """
 from __future__ import annotations
 
@@ -17,6 +20,7 @@ import ctypes as C
 import math
 import os
 import threading
+import warnings
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -41,9 +45,9 @@ def cosine_beta_schedule(timesteps: int, s: float = 0.008) -> torch.Tensor:
 
 def _resolve_mode(numerics: Optional[str]) -> int:
     name = (numerics or os.environ.get("D3DP_NUMERICS", "exact")).lower()
-    if name not in ("exact", "fast", "train"):
-        raise ValueError(f"numerics must be 'exact', 'fast' or 'train', got {name!r}")
-    return {"fast": _lib.MODE_FAST, "exact": _lib.MODE_EXACT, "train": _lib.MODE_TRAIN}[name]
+    if name not in ("exact", "fast", "fast16", "train"):
+        raise ValueError(f"numerics must be 'exact', 'fast', 'fast16' or 'train', got {name!r}")
+    return {"fast": _lib.MODE_FAST, "fast16": _lib.MODE_FAST16, "exact": _lib.MODE_EXACT, "train": _lib.MODE_TRAIN}[name]
 
 
 class _TrainStep(torch.autograd.Function):
@@ -165,7 +169,7 @@ class MixSTE2(nn.Module):
     # -- library context ------------------------------------------------------------------------
     @property
     def numerics(self) -> str:
-        return {_lib.MODE_FAST: "fast", _lib.MODE_EXACT: "exact", _lib.MODE_TRAIN: "train"}[self._mode]
+        return {_lib.MODE_FAST: "fast", _lib.MODE_FAST16: "fast16", _lib.MODE_EXACT: "exact", _lib.MODE_TRAIN: "train"}[self._mode]
 
     def set_numerics(self, numerics: str, chunk_seqs: Optional[int] = None) -> None:
         self._mode = _resolve_mode(numerics)
@@ -314,6 +318,18 @@ class MixSTE2(nn.Module):
         _lib.check(_lib.load().d3dp_exact_scales(self._state().ctx, kv, hd, C.byref(impl)), "d3dp_exact_scales")
         return list(kv), list(hd), {0: "f16x2", 1: "bf16x3", 2: "f32"}.get(impl.value)
 
+    FP16_MAX = 65504.0
+
+    def fast_operands(self):
+        """FAST / FAST16 numerics: ``(type, bound)`` -- the 2-byte operand type the context's kernels run on ('bf16' or 'fp16')
+        and the largest magnitude the current weights PROVE, for any input, for a value the context stores in 2 bytes (0.0 for
+        'fast', which proves nothing; inf for non-finite weights).  A 'fast16' model runs 'fp16' while the bound is below
+        ``FP16_MAX`` and falls back to 'bf16' -- bit for bit what 'fast' computes -- otherwise.  None in the other modes.
+        include/d3dp_hip.h: d3dp_fast_operands."""
+        t, b = C.c_int32(), C.c_float()
+        _lib.check(_lib.load().d3dp_fast_operands(self._state().ctx, C.byref(t), C.byref(b)), "d3dp_fast_operands")
+        return None if t.value < 0 else ("fp16" if t.value == 1 else "bf16", float(b.value))
+
     def refresh_weights(self) -> None:
         """Re-pack the library's weight copies on the next call.  Needed only after parameter writes that bypass
         PyTorch's version counter (``p.data.copy_()``, ``p.data.mul_()``, weight averaging through ``.data``):
@@ -358,6 +374,14 @@ class MixSTE2(nn.Module):
             else:
                 _lib.check(lib.d3dp_set_weights(st.ctx, C.byref(w), _lib.current_stream()), "d3dp_set_weights")
         st.keep = [freq_keep] if borrowed else None   # packed copies: originals may go; borrowed: keep the table
+        if self._mode == _lib.MODE_FAST16 and not self.__dict__.get("_fast16_warned", False):
+            t, b = C.c_int32(), C.c_float()
+            _lib.check(lib.d3dp_fast_operands(st.ctx, C.byref(t), C.byref(b)), "d3dp_fast_operands")
+            if t.value != 1:
+                self._fast16_warned = True               # (once per model, not once per weight push)
+                warnings.warn("numerics='fast16': these weights prove a bound of %g for the values stored in 2 bytes, not below "
+                              "fp16's %g: the model runs the bf16 kernels of numerics='fast' (MixSTE2.fast_operands())"
+                              % (b.value, self.FP16_MAX), RuntimeWarning, stacklevel=2)
 
     def _workspace(self, ctx, B, H, device):
         n = C.c_size_t()

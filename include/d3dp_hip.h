@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define D3DP_ABI_VERSION 4
+#define D3DP_ABI_VERSION 5
 
 /* The library is built with -fvisibility=hidden: the functions declared in this header -- and nothing else -- are its dynamic
  * symbols (tests/test_abi.py compares `nm -D` with this file). */
@@ -74,6 +74,10 @@ enum {
   D3DP_MODE_FAST = 1,    /* bf16 activations/weights into v_mfma_f32_16x16x32_bf16, fp32 accumulate/LN/softmax */
   D3DP_MODE_TRAIN = 2,   /* fp32 weights and activations; Linears (forward, dgrad, wgrad) on split-fp16 operands whose scales are
                             found on the device: required by d3dp_train_*; inference also works (fp32-MFMA Linears)          */
+  D3DP_MODE_FAST16 = 3,  /* D3DP_MODE_FAST's dataflow, buffers, workspace and launches on IEEE fp16 operands (v_mfma_f32_16x16x32_f16:
+                            11 significand bits instead of 8 at the same rate), fp32 accumulate/LN/softmax/residual stream --
+                            when d3dp_set_weights can PROVE from the weights that no value stored in 2 bytes reaches fp16's
+                            65504 (d3dp_fast_operands); otherwise the context runs FAST's bf16 kernels, bit for bit (ABI v5) */
 };
 
 /* MixSTE2 hyper-parameters -- reference common/diffusionpose.py:123-124, common/mixste.py:142-163 */
@@ -135,7 +139,8 @@ D3DP_API const char* d3dp_last_error(void);
 /* Lifetime.  Replaces: MixSTE2.__init__ (mixste.py:142-210) + .cuda() (main.py:243).
  * Shapes (D3DP_ENOTSUP outside them, with the reason in d3dp_last_error):
  *   1 <= frames <= 1024   up to 256 frames the MFMA attention kernels hold a whole sequence; longer clips (`-f 351`,
- *                         common/arguments.py:58) take chunked-key forms of the same kernels (EXACT, TRAIN) or the row kernel (FAST);
+ *                         common/arguments.py:58) take chunked-key forms of the same kernels (EXACT, TRAIN) or the row kernel
+ *                         (FAST, FAST16: fp32 arithmetic on the 2-byte rows, keys through LDS in chunks of 256);
  *   1 <= joints <= 256    MixSTE2's num_joints (mixste.py:141; D3DP builds 17): above 32 the spatial axis runs on the
  *                         whole-sequence attention kernels of the temporal axis;
  *   channels in {64, 128, 256, 512} with head dim in {8, 16, 32, 64} and hidden % 64 == 0: every mode, on the matrix-core
@@ -146,9 +151,10 @@ D3DP_API const char* d3dp_last_error(void);
  *                         (fp32-MFMA Linears, fp32 row attention, run-time-width row kernels; d3dp_exact_scales reports
  *                         implementation 2): the same 1e-3 mm tolerance at roughly a fifth of the throughput.  D3DP_MODE_TRAIN
  *                         takes such a width too, on the fp32 path of the training step (what D3DP_TRAIN_IMPL=f32 selects for
- *                         the instantiated widths), whose attention backward holds a whole sequence in LDS: max(frames,
- *                         joints) <= 256 tokens, <= 153 at head dims above 64.  FAST contexts exist for the instantiated
- *                         widths only.
+ *                         the instantiated widths), whose attention backward holds a whole sequence in LDS: there, and only
+ *                         there, a TRAIN context is limited to max(frames, joints) <= 256 tokens (<= 153 at head dims
+ *                         above 64) and refused beyond; at the instantiated widths TRAIN takes every frames / joints value
+ *                         above.  FAST and FAST16 contexts exist for the instantiated widths only.
  * A D3DP_MODE_TRAIN context whose backward pass overlaps (split-fp16 Linears, D3DP_TRAIN_OVERLAP not 0) gets its second stream
  * and three events here, so that d3dp_train_backward never creates anything. */
 D3DP_API int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out);
@@ -187,6 +193,28 @@ D3DP_API int d3dp_set_weights_borrowed(d3dp_ctx* ctx, const d3dp_weights* w);
 D3DP_API int d3dp_exact_range_bound(const d3dp_ctx* ctx, float* bound);
 D3DP_API int d3dp_exact_scales(const d3dp_ctx* ctx, float* s_kv, float* s_hidden, int32_t* implementation);
 D3DP_API int d3dp_status(d3dp_ctx* ctx, int32_t* nonfinite);
+
+/* D3DP_MODE_FAST16 stores in IEEE fp16 what D3DP_MODE_FAST stores in bf16: the weight matrices, the LayerNorm outputs, q / k / v,
+ * the attention output, the MLP hidden and the two branch outputs (proj, fc2) that the row kernels add to the fp32 residual
+ * stream.  fp16 overflows at 65504 where bf16 has fp32's exponent range, so d3dp_set_weights PROVES the range first, on the
+ * device, per block, for ANY input (C = channels; sums in fp64, every result rounded up to fp32, so the bound never
+ * under-states the formula):
+ *     L1, L2   LayerNorm outputs   max_k sqrt(C-1) |gamma_k| + |beta_k|                                  (norm1, norm2)
+ *     b_qkv    q, k, v             max_n sum_k |Wqkv[n,k]| (sqrt(C-1) |gamma1_k| + |beta1_k|) + |bqkv_n|;  b_v: the v rows n >= 2C
+ *              attention output    <= b_v (a convex combination of v rows; probabilities <= 1)
+ *     b_proj   proj output         max_n sum_k |Wproj[n,k]| b_v + |bproj_n|
+ *     b_h      MLP hidden          max_n sum_k |Wfc1[n,k]| (sqrt(C-1) |gamma2_k| + |beta2_k|) + |bfc1_n|     (|GELU(x)| <= |x|)
+ *     b_fc2    fc2 output          max_n sum_k |Wfc2[n,k]| b_h + |bfc2_n|
+ *              weight matrices     max |w| of each of the four
+ * The context's bound is the largest of these over all blocks.  Bound finite and < 65504: the context runs on fp16 operands,
+ * unscaled.  Otherwise -- or with an inf / nan weight -- it runs the bf16 kernels: exactly what a D3DP_MODE_FAST context
+ * launches on those weights, bit for bit (never an error, never an inf that FAST would not give); this mirrors EXACT's move to
+ * split-bf16.  The decision is per context, not per tensor: a Linear's two operands share one type.
+ * d3dp_fast_operands (after d3dp_set_weights): *type = 0 bf16, 1 fp16, -1 not a FAST / FAST16 context; *bound = the proven
+ * maximum (inf for non-finite weights; 0 for a plain FAST context, which proves nothing).  The worst-case bound is loose by
+ * construction: the seed-initialised 8-block model at C = 512 proves 4762 (13.8x below the limit); where trained checkpoints
+ * sit against it has not been measured. */
+D3DP_API int d3dp_fast_operands(const d3dp_ctx* ctx, int32_t* type, float* bound);
 
 /* Scratch needed by d3dp_denoise for a (B, H) call. */
 D3DP_API int d3dp_workspace_bytes(const d3dp_ctx* ctx, int32_t B, int32_t H, size_t* bytes);
@@ -305,9 +333,10 @@ D3DP_API int d3dp_procrustes(const float* pred, const float* target, float* err,
 
 /* ---- single operators (unit parity tests; same kernels the denoiser launches) ---------------------------- */
 /* out[M,N] = epi(A[M,K] W[N,K]^T + bias).  epi & 3: 0 bias, 1 bias+GELU(erf), 2 out(fp32) += result.
- * mode EXACT: everything fp32 (fp32 MFMA; the EXACT denoiser itself runs mode 3 below).  mode FAST: A, W bf16 (uint16
+ * mode EXACT: everything fp32 (fp32 MFMA; the EXACT denoiser itself runs d3dp_op_linear_x2 below).  mode FAST: A, W bf16 (uint16
  * storage), fp32 accumulate, epi 0 or 1 only, out bf16 unless (epi & 16) (fp32): the persistent streaming kernel the
- * denoiser uses. */
+ * denoiser uses.  mode 4: the same kernel on IEEE fp16 A, W and out (what a FAST16 context launches; NOT D3DP_MODE_FAST16's
+ * number, which this entry point does not take: 2 and 3 are the split-operand selectors here). */
 D3DP_API int d3dp_op_linear(int32_t mode, int32_t epi, const void* A, const void* W, const float* bias, void* out, int32_t M,
                    int32_t N, int32_t K, void* stream);
 /* Multi-head attention over qkv[T,3C] -> out[T,C]; axis 0 = spatial (sequences of J joints), 1 = temporal
@@ -315,7 +344,10 @@ D3DP_API int d3dp_op_linear(int32_t mode, int32_t epi, const void* A, const void
  * 1 = matrix-core kernel (head dim 64): bf16 MFMA for bf16 activations (both axes), fp32 MFMA for fp32 activations
  * (temporal axis), 2 = the EXACT-mode kernels: split-fp16 operands on the fp16 matrix cores (both axes; head dim 64).  Inside
  * the denoiser those read the packed rows of its qkv Linear (d3dp_op_linear_x2, epi 4); this entry point takes plain fp32
- * rows and repacks them into a stream-ordered temporary (hipMallocAsync) first. */
+ * rows and repacks them into a stream-ordered temporary (hipMallocAsync) first.
+ * act_bf16: 0 fp32 rows, 1 bf16 rows, 4 IEEE fp16 rows (impl 0 and 1: the kernels of a FAST16 context).
+ * d3dp_op_layernorm out_bf16: the activation code of the row kernels -- 0 fp32, 1 bf16, 2 three split-bf16 planes, 3 two
+ * split-fp16 planes (h2i), 4 IEEE fp16. */
 D3DP_API int d3dp_op_attention(int32_t act_bf16, int32_t impl, int32_t axis, const void* qkv, void* out, int32_t n_bh,
                       int32_t F, int32_t J, int32_t C, int32_t heads, void* stream);
 D3DP_API int d3dp_op_layernorm(int32_t out_bf16, const float* x, const float* w, const float* b, float eps, void* out,

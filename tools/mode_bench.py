@@ -1,0 +1,78 @@
+#!/usr/bin/env python3
+"""Interleaved same-process comparison of numerics modes on BASELINE configs[2] (ddim_sample_flip, F=243, J=17, B=16, H=20, K=10).
+
+    python tools/mode_bench.py --numerics fast,fast16 [--steps 20] [--warmup 5] [--rounds 4]
+
+Every mode gets its own model (and library context) on the same weights, inputs and generator seed.  After `--warmup` steps of each,
+the timed steps are taken in `--rounds` rounds that visit the modes in turn (a b a b ...), steps / rounds steps per visit, a host
+clock around a device synchronise per visit: drift of the box (clock, temperature, neighbours) lands on every mode alike, which two
+back-to-back bench.py runs cannot offer.  Clock and power are sampled the way bench.py samples them (its GpuTelemetry), per mode,
+over that mode's timed visits only.  Prints ONE JSON line: per mode hypothesis-clips/s, ms per step, the per-visit spread, mean
+clock / power; the ratio of every mode to the first; the operand type and proven bound of the FAST modes; the library's sha256.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--numerics", default="fast,fast16", help="comma-separated modes, e.g. fast,fast16,exact")
+    ap.add_argument("--steps", type=int, default=20, help="timed steps per mode (>= rounds)")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=4, help="interleaving rounds the timed steps are split into")
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--hyps", type=int, default=20)
+    ap.add_argument("--ksteps", type=int, default=10)
+    a = ap.parse_args()
+    modes = [m.strip() for m in a.numerics.split(",") if m.strip()]
+    if not modes or a.steps < a.rounds or a.rounds < 1 or a.warmup < 0:
+        ap.error("need at least one mode, --rounds >= 1 and --steps >= --rounds")
+    import torch
+    import bench
+    from d3dp_amd.weights import flip_2d, synthetic_inputs_2d
+    B, H, K = a.batch, a.hyps, a.ksteps
+    x2d_np = synthetic_inputs_2d(1234, B, bench.F_)
+    x2d, x2f = torch.from_numpy(x2d_np).cuda(), torch.from_numpy(flip_2d(x2d_np)).cuda()
+    models = {m: bench.build_model(H, K, m, 0) for m in modes}
+    gens = {m: torch.Generator(device="cuda").manual_seed(1) for m in modes}
+    teles = {m: bench.GpuTelemetry(torch.cuda.current_device()) for m in modes}
+    for m in modes:
+        for _ in range(a.warmup):
+            models[m](x2d, None, input_2d_flip=x2f, generator=gens[m])
+    torch.cuda.synchronize()
+    per_visit = [a.steps // a.rounds + (1 if r < a.steps % a.rounds else 0) for r in range(a.rounds)]
+    visits = {m: [] for m in modes}
+    out = None
+    for n in per_visit:
+        for m in modes:
+            teles[m].start()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                out = models[m](x2d, None, input_2d_flip=x2f, generator=gens[m])
+            torch.cuda.synchronize()
+            visits[m].append((time.perf_counter() - t0) / n)
+            teles[m].stop()
+            assert bool(torch.isfinite(out).all())
+    res = {"workload": f"BASELINE configs[2]: ddim_sample_flip F={bench.F_} J=17 B={B} H={H} K={K} flip-TTA, cs=512 dep=8",
+           "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "order": modes, "library_sha256": bench.lib_sha256(), "modes": {}}
+    for m in modes:
+        dt = sum(v * n for v, n in zip(visits[m], per_visit))
+        tr = teles[m].report()
+        fo = models[m].pose_estimator.fast_operands()
+        res["modes"][m] = {"value": B * H * a.steps / dt, "unit": "hypothesis-clips/s", "ms_per_step": dt / a.steps * 1e3,
+                           "ms_per_step_by_visit": [round(v * 1e3, 2) for v in visits[m]],
+                           "clock_mhz_mean": tr["clock_mhz_mean"], "power_w_mean": tr["power_w_mean"], "power_cap_w": tr["power_cap_w"],
+                           "fast_operands": None if fo is None else {"type": fo[0], "proven_bound": fo[1]}}
+    base = res["modes"][modes[0]]["value"]
+    res["ratio_to_first"] = {m: res["modes"][m]["value"] / base for m in modes}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
