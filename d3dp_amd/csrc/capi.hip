@@ -429,6 +429,72 @@ int run_block(d3dp_ctx* c, const BlockDev& w, int axis, float* x, void* y1, void
   return 0;
 }
 
+// The environment switches of a context, read once at d3dp_create: the cross-check implementations, the training step's
+// scheduling switches and the measurement switches of the experiment kernels.  `width_inst`: the width is one the matrix-core
+// kernels are instantiated for (d3dp_create).  D3DP_OK, or the refusal (the caller deletes the context).
+// (D3DP_TRAIN_ATTN_BWD alone is read per call, in train.hip: tests flip it between steps.)
+int read_switches(d3dp_ctx* c, bool width_inst) {
+  const d3dp_cfg& g = c->cfg;
+  const char* xf = getenv("D3DP_EXACT_IMPL");
+  c->exact_impl = c->exact_impl_req = (xf && !strcmp(xf, "bf16x3")) ? 1 : (xf && !strcmp(xf, "f32")) ? 2 : 0;
+  if (!width_inst) {
+    if (c->exact_impl_req == 1)
+      return fail(D3DP_ENOTSUP, "D3DP_EXACT_IMPL=bf16x3 exists for channels in {64,128,256,512}; channels=%d runs the fp32 implementation", g.channels);
+    c->exact_impl = c->exact_impl_req = 2;
+  }
+  const char* lr = getenv("D3DP_LONG_ATTN");             // cross-check: clips > 256 frames on the fp32 row attention kernel
+  c->long_rows = lr && !strcmp(lr, "rows");
+  const char* nf = getenv("D3DP_NO_FOLD");               // cross-check: residual adds (and norm2) in the row kernels
+  c->fold = !(nf && nf[0] == '1');
+  const char* ti = getenv("D3DP_TRAIN_IMPL");
+  c->train_x2 = !(ti && !strcmp(ti, "f32")) && width_inst;     // (a width outside the instantiated set: the fp32 path)
+  const char* ov = getenv("D3DP_TRAIN_OVERLAP");
+  c->train_overlap = !(ov && ov[0] == '0');
+  c->train_overlap_sets = (ov && ov[0] == '1') ? 1 : 2;
+  const char* tg = getenv("D3DP_TRAIN_GELU");
+  c->train_gelu_in_prep = !(tg && !strcmp(tg, "pass"));
+  const char* tw = getenv("D3DP_TRAIN_WGRAD");
+  c->train_wgrad_merged = !(tw && !strcmp(tw, "each"));
+  const char* tl = getenv("D3DP_TRAIN_LN_OPERAND");       // =pass: round 5's operand pass behind every LayerNorm (variants build only)
+  c->train_ln_direct = !(tl && !strcmp(tl, "pass"));
+  const char* tt = getenv("D3DP_TRAIN_TAIL");
+  c->train_tail_blocks = !(tt && !strcmp(tt, "split"));
+  const char* ta = getenv("D3DP_TRAIN_ATTN");
+  c->train_attn_x2 = (ta && !strcmp(ta, "f32")) ? 0 : (ta && !strcmp(ta, "x2t")) ? 1 : 2;
+  // D3DP_TRAIN_WGRAD=each / D3DP_TRAIN_TAIL=split / D3DP_TRAIN_GELU=pass were round 5's same-box A/B switches: they make the
+  // configs[4] shapes take the launch forms the library keeps for the shapes its merged / fused forms do not cover (widths below
+  // 256, contractions that are not a multiple of 16 k-steps).  Measured and superseded (DESIGN.md section 7a): like the experiment
+  // kernels below they are honoured by the `make variants` library only and REFUSED here -- never ignored.  (What stays: the
+  // cross-check implementations D3DP_TRAIN_IMPL=f32, D3DP_TRAIN_ATTN=f32|x2t, D3DP_TRAIN_ATTN_BWD=valu, D3DP_EXACT_IMPL, D3DP_NO_FOLD,
+  // and the profiling switch D3DP_TRAIN_OVERLAP=0|1: one stream, so that no kernel's duration contains a wait for CUs.)
+  if ((!c->train_gelu_in_prep || !c->train_wgrad_merged || !c->train_tail_blocks || !c->train_ln_direct) && !d3dp_x2_variants_built())
+    return fail(D3DP_ENOTSUP, "D3DP_TRAIN_WGRAD=each / D3DP_TRAIN_TAIL=split / D3DP_TRAIN_GELU=pass / D3DP_TRAIN_LN_OPERAND=pass select superseded launch forms of the "
+                              "training step that only the variants build honours (make -C d3dp_amd/csrc variants; "
+                              "D3DP_LIB=d3dp_amd/lib/variants/libd3dp_variants.so)");
+  {
+    // Measurement switches of experiments that were measured and not adopted (DESIGN.md section 7): the row-class skewed schedule
+    // (D3DP_X2_SKEW=1|2|4), the ping-pong (D3DP_X2_PP=1) and wide (D3DP_X2_WIDE=1) forms of the EXACT Linear, norm2 folded into
+    // proj / fc1 (D3DP_FOLD_LN=1), the sequence padding the skewed schedule needs (D3DP_SEQ_PAD).  Their kernels exist only in a
+    // library built with -DD3DP_X2_VARIANTS=1 (`make variants`): the product library refuses the request instead of ignoring it.
+    const char* sk = getenv("D3DP_X2_SKEW");
+    const char* pp = getenv("D3DP_X2_PP");
+    const char* wide = getenv("D3DP_X2_WIDE");
+    const char* pd = getenv("D3DP_SEQ_PAD");
+    const char* nl = getenv("D3DP_FOLD_LN");
+    int skew_d = 0, pingpong = 0, pad = -1;
+    if (sk && (sk[0] == '0' || sk[0] == '1' || sk[0] == '2' || sk[0] == '4') && sk[1] == 0) skew_d = sk[0] - '0';
+    if (pp && (pp[0] == '0' || pp[0] == '1') && pp[1] == 0) pingpong = pp[0] - '0';
+    if (wide && wide[0] == '1' && wide[1] == 0) pingpong = 2;
+    if (pd && (pd[0] == '0' || pd[0] == '1') && pd[1] == 0) pad = pd[0] - '0';
+    const bool fold_ln = nl && nl[0] == '1';
+    if ((skew_d || pingpong || pad > 0 || fold_ln) && !d3dp_x2_variants_built())
+      return fail(D3DP_ENOTSUP, "D3DP_X2_SKEW / D3DP_X2_PP / D3DP_X2_WIDE / D3DP_SEQ_PAD / D3DP_FOLD_LN select experiment kernels that this "
+                                "library was built without (make -C d3dp_amd/csrc variants; D3DP_LIB=d3dp_amd/lib/variants/libd3dp_variants.so)");
+    c->skew_d = skew_d; c->pingpong = pingpong; c->pad_override = pad; c->fold_ln_on = fold_ln;
+  }
+  return D3DP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -518,68 +584,9 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   d3dp_ctx* c = new d3dp_ctx();
   c->cfg = g;
   c->fast_f16 = c->fast16() ? 1 : (c->fast() ? D3DP_FAST_F16 : 0);   // (FAST16: until d3dp_set_weights has seen the weights)
-  const char* xf = getenv("D3DP_EXACT_IMPL");
-  c->exact_impl = c->exact_impl_req = (xf && !strcmp(xf, "bf16x3")) ? 1 : (xf && !strcmp(xf, "f32")) ? 2 : 0;
-  if (!width_inst) {
-    if (c->exact_impl_req == 1) {
-      delete c;
-      return fail(D3DP_ENOTSUP, "D3DP_EXACT_IMPL=bf16x3 exists for channels in {64,128,256,512}; channels=%d runs the fp32 implementation", g.channels);
-    }
-    c->exact_impl = c->exact_impl_req = 2;
-  }
-  const char* lr = getenv("D3DP_LONG_ATTN");             // cross-check: clips > 256 frames on the fp32 row attention kernel
-  c->long_rows = lr && !strcmp(lr, "rows");
-  const char* nf = getenv("D3DP_NO_FOLD");               // cross-check: residual adds (and norm2) in the row kernels
-  c->fold = !(nf && nf[0] == '1');
-  const char* ti = getenv("D3DP_TRAIN_IMPL");
-  c->train_x2 = !(ti && !strcmp(ti, "f32")) && width_inst;     // (a width outside the instantiated set: the fp32 path)
-  const char* ov = getenv("D3DP_TRAIN_OVERLAP");
-  c->train_overlap = !(ov && ov[0] == '0');
-  c->train_overlap_sets = (ov && ov[0] == '1') ? 1 : 2;
-  const char* tg = getenv("D3DP_TRAIN_GELU");
-  c->train_gelu_in_prep = !(tg && !strcmp(tg, "pass"));
-  const char* tw = getenv("D3DP_TRAIN_WGRAD");
-  c->train_wgrad_merged = !(tw && !strcmp(tw, "each"));
-  const char* tl = getenv("D3DP_TRAIN_LN_OPERAND");       // =pass: round 5's operand pass behind every LayerNorm (variants build only)
-  c->train_ln_direct = !(tl && !strcmp(tl, "pass"));
-  const char* tt = getenv("D3DP_TRAIN_TAIL");
-  c->train_tail_blocks = !(tt && !strcmp(tt, "split"));
-  const char* ta = getenv("D3DP_TRAIN_ATTN");
-  c->train_attn_x2 = (ta && !strcmp(ta, "f32")) ? 0 : (ta && !strcmp(ta, "x2t")) ? 1 : 2;
-  // D3DP_TRAIN_WGRAD=each / D3DP_TRAIN_TAIL=split / D3DP_TRAIN_GELU=pass were round 5's same-box A/B switches: they make the
-  // configs[4] shapes take the launch forms the library keeps for the shapes its merged / fused forms do not cover (widths below
-  // 256, contractions that are not a multiple of 16 k-steps).  Measured and superseded (DESIGN.md section 7a): like the experiment
-  // kernels below they are honoured by the `make variants` library only and REFUSED here -- never ignored.  (What stays: the
-  // cross-check implementations D3DP_TRAIN_IMPL=f32, D3DP_TRAIN_ATTN=f32|x2t, D3DP_TRAIN_ATTN_BWD=valu, D3DP_EXACT_IMPL, D3DP_NO_FOLD,
-  // and the profiling switch D3DP_TRAIN_OVERLAP=0|1: one stream, so that no kernel's duration contains a wait for CUs.)
-  if ((!c->train_gelu_in_prep || !c->train_wgrad_merged || !c->train_tail_blocks || !c->train_ln_direct) && !d3dp_x2_variants_built()) {
+  if (const int rc = read_switches(c, width_inst); rc != D3DP_OK) {
     delete c;
-    return fail(D3DP_ENOTSUP, "D3DP_TRAIN_WGRAD=each / D3DP_TRAIN_TAIL=split / D3DP_TRAIN_GELU=pass / D3DP_TRAIN_LN_OPERAND=pass select superseded launch forms of the "
-                              "training step that only the variants build honours (make -C d3dp_amd/csrc variants; "
-                              "D3DP_LIB=d3dp_amd/lib/variants/libd3dp_variants.so)");
-  }
-  {
-    // Measurement switches of experiments that were measured and not adopted (DESIGN.md section 7): the row-class skewed schedule
-    // (D3DP_X2_SKEW=1|2|4), the ping-pong (D3DP_X2_PP=1) and wide (D3DP_X2_WIDE=1) forms of the EXACT Linear, norm2 folded into
-    // proj / fc1 (D3DP_FOLD_LN=1), the sequence padding the skewed schedule needs (D3DP_SEQ_PAD).  Their kernels exist only in a
-    // library built with -DD3DP_X2_VARIANTS=1 (`make variants`): the product library refuses the request instead of ignoring it.
-    const char* sk = getenv("D3DP_X2_SKEW");
-    const char* pp = getenv("D3DP_X2_PP");
-    const char* wide = getenv("D3DP_X2_WIDE");
-    const char* pd = getenv("D3DP_SEQ_PAD");
-    const char* nl = getenv("D3DP_FOLD_LN");
-    int skew_d = 0, pingpong = 0, pad = -1;
-    if (sk && (sk[0] == '0' || sk[0] == '1' || sk[0] == '2' || sk[0] == '4') && sk[1] == 0) skew_d = sk[0] - '0';
-    if (pp && (pp[0] == '0' || pp[0] == '1') && pp[1] == 0) pingpong = pp[0] - '0';
-    if (wide && wide[0] == '1' && wide[1] == 0) pingpong = 2;
-    if (pd && (pd[0] == '0' || pd[0] == '1') && pd[1] == 0) pad = pd[0] - '0';
-    const bool fold_ln = nl && nl[0] == '1';
-    if ((skew_d || pingpong || pad > 0 || fold_ln) && !d3dp_x2_variants_built()) {
-      delete c;
-      return fail(D3DP_ENOTSUP, "D3DP_X2_SKEW / D3DP_X2_PP / D3DP_X2_WIDE / D3DP_SEQ_PAD / D3DP_FOLD_LN select experiment kernels that this "
-                                "library was built without (make -C d3dp_amd/csrc variants; D3DP_LIB=d3dp_amd/lib/variants/libd3dp_variants.so)");
-    }
-    c->skew_d = skew_d; c->pingpong = pingpong; c->pad_override = pad; c->fold_ln_on = fold_ln;
+    return rc;
   }
   HIP_TRY(hipGetDevice(&c->device));
   {
@@ -1213,6 +1220,7 @@ struct TrainLayout {
   size_t xn, y, hid, dA, dB, dC, dqkv, dh, z, At, Xt, Wt, dtemb, stats;
   // split-fp16 operands of the training Linears (X2Train below): row form [rows][2 K] and transposed form [features][2 Tp]
   size_t op_a, op_w, op_at, op_xt, part, part_rem, slots;
+  size_t part_floats;               // capacity of `part` and of `part2`: split-K partial products, at most ~ (CUs + tiles) output tiles
   size_t op_a2, op_at2, part2;      // a second set of the dY operand and partial-tile regions: two weight-gradient products in flight
   size_t x_cols, x_block;           // every Linear's activation operand kept from the forward pass for its wgrad: the ROW form [Tp][2 K]
                                     // where the TN kernel applies (it is then also the forward product's operand), else the transposed [K][2 Tp]
@@ -1255,8 +1263,9 @@ TrainLayout train_layout(const d3dp_cfg& g, int B) {
     L.op_w = take(fmax * kmax);                      // [N][2 K] or [K][2 N] fp16
     L.op_at = take(fmax * L.Tp_max);                 // dY^T: [N][2 Tp] fp16
     L.op_xt = take(kmax * L.Tp_max);                 // X^T:  [K][2 Tp] fp16
-    L.part = take((size_t)(1024 + 64) * 256 * 128);  // split-K partial products: at most ~ (CUs + tiles) output tiles
-    L.op_a2 = take(L.Tp_max * dy_all); L.op_at2 = take(fmax * L.Tp_max); L.part2 = take((size_t)(1024 + 64) * 256 * 128);
+    L.part_floats = (size_t)(1024 + 64) * 256 * 128;
+    L.part = take(L.part_floats);
+    L.op_a2 = take(L.Tp_max * dy_all); L.op_at2 = take(fmax * L.Tp_max); L.part2 = take(L.part_floats);
     L.part_rem = take((size_t)16 * 256 * fmax);      // ... of a forward / dgrad product's remainder rows (its own region: the
                                                      // weight-gradient product of the same dY runs concurrently on the second stream)
     L.slots = take(2 * 8192);                        // absmax words | 1 / scale per operand
@@ -1362,7 +1371,7 @@ struct X2Train {
     const int nk = (T + 31) / 32;
     mZ = std::max(1, std::min(std::min(n_cu / std::max(tiles, 1), 64), nk / 4));
     mTp = mZ * ((nk + mZ - 1) / mZ) * 32;
-    merged = ok && (size_t)mTp <= L.Tp_max && (size_t)mZ * nk_sum <= (size_t)(1024 + 64) * 256 * 128;
+    merged = ok && (size_t)mTp <= L.Tp_max && (size_t)mZ * nk_sum <= L.part_floats;
   }
   // rows the operands of the weight gradient dW[N, K] must have (zero behind T)
   int pad_rows(int T, int N, int K) const {
@@ -1568,7 +1577,7 @@ struct X2Train {
     const int sx = 2 * l;
     int Z, Tp;
     wgrad_split(T, N, K, Z, Tp);
-    if ((size_t)Tp > L.Tp_max || (size_t)Z * N * K > (size_t)(1024 + 64) * 256 * 128) return -1;
+    if ((size_t)Tp > L.Tp_max || (size_t)Z * N * K > L.part_floats) return -1;
     (void)X;                                           // X's operand form: left by the forward pass of this step
     if (merged) {                                      // recorded; launched with the block's other three by flush_wgrads()
       if (!dy_ready || n_def >= D3DP_TN_MAX || !d3dp_tn_applies(N, K)) return -1;
@@ -1883,7 +1892,7 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
     Scope ps_(pc, T_WGRAD, st);
     // contraction over tokens: split-K, the chunks' partial products added in a fixed order (no float atomics: this path's gradients
     // are bit-reproducible too)
-    return d3dp_launch_linear_f32_splitk(At, Xt, dW, N, K, Tp, st, ws + L.part, (size_t)(1024 + 64) * 256 * 128);
+    return d3dp_launch_linear_f32_splitk(At, Xt, dW, N, K, Tp, st, ws + L.part, L.part_floats);
   };
   // dgrad: dX[T, K] = dY[T, N] W[N, K]   (W transposed to [K, N])
   auto dgrad = [&](int l, const float* dY, int N, const float* W, int K, float* dX, unsigned* out_amax = nullptr) -> int {

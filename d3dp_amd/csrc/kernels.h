@@ -79,7 +79,12 @@ void d3dp_launch_ln_combine(const float* slices, float* rowstat, int M, int C, f
 void d3dp_launch_fold_ln(const float* W, const float* gamma, const float* beta, const float* bias, float* Wp, float* c12,
                          int N, int K, hipStream_t st);
 void d3dp_launch_split2(const float* src, void* dst, size_t n, float scale, hipStream_t st);
-// ---- the training step's split-fp16 Linear (gemm_x2.hip, gemm_f16x2_dyn_kernel): operand scales live on the device ----
+// out[0] = max |src[i]| as the bit pattern of a non-negative float (`out` pre-zeroed)
+void d3dp_launch_absmax(const float* src, size_t n, unsigned* out, hipStream_t st);
+// flag[0] |= 1 if any of x[0..n) is inf / nan
+void d3dp_launch_nonfinite_flag(const float* x, size_t n, unsigned* flag, hipStream_t st);
+// ---- gemm_x2_train.hip (the training step's split-fp16 Linears, their operand passes and partial sums) ------------
+// gemm_f16x2_dyn_kernel: operand scales live on the device.
 // out_z[M, N] (z = 0 .. Z-1, M N floats apart) = A2[M][2 Kfull] . W2[N][2 Kfull]^T over k-chunk z, x dynA[0] x dynW[0], + bias
 // (bias may be null).  Kfull % (32 Z) == 0, N % 4 == 0.
 // amax_out (optional, Z == 1): absmax slot of the output (bit pattern of a non-negative float, pre-zeroed; one atomicMax per workgroup)
@@ -100,9 +105,8 @@ void d3dp_launch_split2_dyn(const float* src, void* dst, int R, int C, int Cpad,
 // the TRANSPOSE as a split operand: src [R][C] -> h2i [C][2 Rpad] (zero behind R; Rpad % 32 == 0)
 void d3dp_launch_split2_t_dyn(const float* src, void* dst, int R, int C, int Rpad, const unsigned* amax, float* unscale,
                               hipStream_t st);
-// out[i] = sum over z of part[z n + i], z ascending
 // src [R][C] -> row form [R][2 C], transposed form [C][2 Rpad] and (colpart != null) its column sums as D3DP_DYPREP_ROWS
-// partial rows of C floats (every row written; summed by d3dp_train_reduce_many) in one pass (gemm_x2.hip)
+// partial rows of C floats (every row written; summed by d3dp_train_reduce_many) in one pass
 constexpr int D3DP_DYPREP_ROWS = 96;
 int d3dp_launch_dyprep(const float* src, void* drow, void* dcol, float* colpart, int R, int C, int Rpad, const unsigned* amax,
                        float* unscale, hipStream_t st);
@@ -136,18 +140,17 @@ struct D3dpTnTable { D3dpTnProduct p[D3DP_TN_MAX]; int n; };
 int d3dp_launch_linear_f16x2_tn_many(const D3dpTnProduct* prods, int n, int Tp, int Z, hipStream_t st);
 struct D3dpSumTable { const float* part[D3DP_TN_MAX]; float* out[D3DP_TN_MAX]; size_t n4[D3DP_TN_MAX]; int Z; int n; };
 void d3dp_launch_sum_partials_many(const D3dpSumTable& tb, hipStream_t st);   // out_p[i] = sum_z part_p[z n_p + i], z ascending
-// the training step's weight operands in three launches (gemm_x2.hip): absmax -> slot, rows form [N][2 K] at rows_base + 2 off
+// the training step's weight operands in three launches: absmax -> slot, rows form [N][2 K] at rows_base + 2 off
 // halves, transposed form [K][2 N] at cols_base + 2 off halves, unscale[slot] = 1 / scale
 constexpr int D3DP_WPREP_MAX = 64;
 struct D3dpWPrepItem { const float* w; int N, K, slot, pad; size_t off; };
 struct D3dpWPrepTable { D3dpWPrepItem it[D3DP_WPREP_MAX]; int n; };
 int d3dp_launch_wprep(const D3dpWPrepTable& tb, void* rows_base, void* cols_base, unsigned* amax, float* unscale, hipStream_t st);
+// out[i] = sum over z of part[z n + i], z ascending
 void d3dp_launch_sum_partials(const float* part, float* out, size_t n, int Z, hipStream_t st);
 void d3dp_launch_sum_partials_bias(const float* part, const float* bias, float* out, size_t n, int N, int Z, hipStream_t st,
                                    unsigned* amax = nullptr, int amax_pos = 0);
-void d3dp_launch_absmax(const float* src, size_t n, unsigned* out, hipStream_t st);
-// flag[0] |= 1 if any of x[0..n) is inf / nan
-void d3dp_launch_nonfinite_flag(const float* x, size_t n, unsigned* flag, hipStream_t st);
+// ---- gemm.hip again: the fp32-MFMA Linears of the fp32 implementations ---------------------------------------------
 int d3dp_launch_linear_f32_splitk(const float* A, const float* W, float* out, int M, int N, int K, hipStream_t st, float* part,
                                   size_t part_floats);
 int d3dp_launch_linear_f32(int epi, const float* A, const float* W, const float* bias, float* out, int M, int N,

@@ -515,7 +515,7 @@ def test_reference_attributes_exist():
 
 
 def _simulate_skewed_linear(M, tm, tiles_n, G, NK, D):
-    """Index-level model of gemm_f16x2_skew_kernel (d3dp_amd/csrc/gemm_x2.hip), written from the kernel's formulas: per
+    """Index-level model of gemm_f16x2_skew_kernel (d3dp_amd/csrc/gemm_x2_variants.h), written from the kernel's formulas: per
     workgroup the loader's row pointers (rotating LDS image), the compute waves' park / shift / store sequence.  Returns,
     per (row tile, strip, row class), the list of k-steps that were accumulated into what got stored, and the store count."""
     from collections import defaultdict
