@@ -336,9 +336,12 @@ __device__ __forceinline__ void pv_chunks(const FragBases& fb, const typename Op
 
 // One 16-query tile against NKT 16-key tiles resident in LDS.  q0/q1: the tile's Q fragments (d 0..31 / 32..63).
 // Returns O^T accumulators (4 channel tiles) and the softmax denominator of query (lane & 15).
-template <typename E, int NKT>
+// ONLINE (the chunked-key kernel below): the resident keys are one chunk of a longer row.  `mrun` is the running row maximum
+// in base-2 logit units (-inf before the first chunk); the probabilities are formed against the larger of it and this chunk's
+// maximum, and `o` / `denom` -- the sums over the earlier chunks -- are rescaled to that maximum and added to.
+template <typename E, int NKT, bool ONLINE>
 __device__ __forceinline__ void attn_tile(const FragBases& fb, typename Op2<E>::x8 q0, typename Op2<E>::x8 q1, int n, int lane,
-                                          f32x4 (&o)[4], float& denom) {
+                                          f32x4 (&o)[4], float& denom, float& mrun) {
   using e8 = typename Op2<E>::x8;
   const int fg = lane >> 4;
   const float cexp = 0.125f * 1.44269504088896340736f;   // hd^-0.5 * log2(e), hd = 64
@@ -366,7 +369,12 @@ __device__ __forceinline__ void attn_tile(const FragBases& fb, typename Op2<E>::
   }
   mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  const float mc = mx * cexp;
+  float mc = mx * cexp, alpha = 0.f;
+  if constexpr (ONLINE) {
+    mc = fmaxf(mc, mrun);                                  // (finite: the chunk holds at least one key)
+    alpha = __builtin_amdgcn_exp2f(mrun - mc);             // (first chunk: 0)
+    mrun = mc;
+  }
   float sum = 0.f;
   e8 pf[NKT / 2];
 #pragma unroll
@@ -380,10 +388,22 @@ __device__ __forceinline__ void attn_tile(const FragBases& fb, typename Op2<E>::
   }
   sum += __shfl_xor(sum, 16, 64);
   sum += __shfl_xor(sum, 32, 64);
-  denom = sum;
+  if constexpr (ONLINE) {
+    denom = fmaf(denom, alpha, sum);
 #pragma unroll
-  for (int dn = 0; dn < 4; ++dn) o[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int dn = 0; dn < 4; ++dn) o[dn] *= alpha;
+  } else {
+    denom = sum;
+#pragma unroll
+    for (int dn = 0; dn < 4; ++dn) o[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
   pv_chunks<E, NKT, 0>(fb, pf, o);
+}
+template <typename E, int NKT>
+__device__ __forceinline__ void attn_tile(const FragBases& fb, typename Op2<E>::x8 q0, typename Op2<E>::x8 q1, int n, int lane,
+                                          f32x4 (&o)[4], float& denom) {
+  float m = 0.f;
+  attn_tile<E, NKT, false>(fb, q0, q1, n, lane, o, denom, m);
 }
 
 // rows [0, n) of K and V (128 B per row for this head) -> swizzled LDS images; rows [n, NK) of V zeroed.
@@ -445,6 +465,107 @@ __global__ __launch_bounds__(512, 4) void attn_temporal2_bf16_kernel(const E* __
     attn_tile<E, NKT>(fb, qf[i][0], qf[i][1], n, lane, o, denom);
     if (q < n) {
       const float inv = 1.0f / denom;
+      E* dst = out + (size_t)(base + q * ts) * C + head * 64 + fg * 4;
+#pragma unroll
+      for (int dn = 0; dn < 4; ++dn) {
+        e4 r = {(E)(o[dn][0] * inv), (E)(o[dn][1] * inv), (E)(o[dn][2] * inv), (E)(o[dn][3] * inv)};
+        *reinterpret_cast<e4*>(dst + dn * 16) = r;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Sequences LONGER than 256 tokens (up to the library's 1024) on the same operands: the flash form, as
+// attn_temporal_x2_long_kernel is for EXACT.  A work unit = one (sequence, head) problem x one group of eight 16-query tiles,
+// one tile per wave; a persistent grid walks the units.  The keys pass through LDS in chunks of 16 NKT (K and V images in
+// stage_kv's layouts, two buffers); attn_tile's ONLINE form runs its two-pass softmax over each chunk against the larger of
+// the chunk's and the running row maximum -- probabilities rounded to E before P.V, the mode's definition -- and rescales the
+// running denominator and O^T, which stay in registers, in base-2 units whenever a chunk raises the maximum (-inf before the
+// first chunk: the empty sums are scaled by 0, never by inf - inf).  Chunk c + 1's global loads are issued
+// into registers before chunk c's MFMAs and written to the other buffer after them, so one barrier per chunk serves both
+// "buffer c is complete" and "buffer c - 1 is free".  Keys >= n: zero K / V rows, scores masked by attn_tile; queries >= n are
+// computed on row n - 1 and not stored.  Correct for any n >= 1; launched for n > 256.
+// -DD3DP_FAST_LONG_NKT=16 (measurement build): chunks of 256 keys, 128 KiB of LDS, one workgroup per CU
+// (profiles/fast_long_attn.md has the comparison).
+#ifndef D3DP_FAST_LONG_NKT
+#define D3DP_FAST_LONG_NKT 8
+#endif
+template <typename E, int NKT>
+__global__ __launch_bounds__(512, NKT == 8 ? 4 : 2) void attn_long2_bf16_kernel(const E* __restrict__ qkv, E* __restrict__ out,
+                                                                                  SeqMap map, int C, int heads, int groups,
+                                                                                  int n_work) {
+  using e4 = typename Op2<E>::x4;
+  using e8 = typename Op2<E>::x8;
+  constexpr int NK = 16 * NKT, IMG = NK * 128, BUF = 2 * IMG, NLD = NK * 8 / 512;
+  extern __shared__ __attribute__((aligned(16))) char smem[];       // two buffers of [K image | V image]
+  const int n = map.n_tok;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fi = lane & 15, fg = lane >> 4;
+  const int ts = map.tok_stride;
+  const size_t ld = (size_t)3 * C, rs = (size_t)ts * ld;
+  const int n_chunks = (n + NK - 1) / NK;
+  float4 kr[NLD], vr[NLD];
+  // Staging: thread `tid` moves 16-byte slot (tid & 7) of rows (tid >> 3) + 64 u of a chunk, so everything that depends on the
+  // thread is one 32-bit element offset into the rows (63 tok_stride 3 C + 56 < 2^31 for every shape the library takes) and one
+  // byte offset into each image (the swizzles have period 16 rows); the rest is wave-uniform.
+  const int r0 = tid >> 3, slot = tid & 7;
+  const unsigned goff = (unsigned)r0 * (unsigned)rs + slot * 8;
+  const int koff = r0 * 128 + ((slot ^ ((r0 >> 1) & 7)) << 4);
+  const int voff = IMG + r0 * 128 + ((slot ^ (((r0 >> 1) & 3) << 1)) << 4);
+  // rows k0 .. k0 + NK - 1 of K and V -> registers (rows >= n: zeros) ...
+  auto fetch = [&](const E* kbase, int k0) {
+#pragma unroll
+    for (int u = 0; u < NLD; ++u) {
+      kr[u] = make_float4(0.f, 0.f, 0.f, 0.f); vr[u] = kr[u];
+      if (k0 + 64 * u + r0 < n) {
+        const E* src = kbase + (size_t)(k0 + 64 * u) * rs + goff;
+        kr[u] = *reinterpret_cast<const float4*>(src);
+        vr[u] = *reinterpret_cast<const float4*>(src + C);
+      }
+    }
+  };
+  // ... and from there into one buffer's swizzled images (stage_kv's layouts)
+  auto commit = [&](char* buf) {
+#pragma unroll
+    for (int u = 0; u < NLD; ++u) {
+      *reinterpret_cast<float4*>(buf + koff + u * 8192) = kr[u];
+      *reinterpret_cast<float4*>(buf + voff + u * 8192) = vr[u];
+    }
+  };
+  for (int unit = blockIdx.x; unit < n_work; unit += gridDim.x) {
+    const int prob = unit / groups, group = unit - prob * groups;
+    const int seq = prob / heads, head = prob - seq * heads;
+    const int base = seq_base(map, seq);
+    const E* qbase = qkv + (size_t)base * ld + (size_t)head * 64;
+    const int qt = group * 8 + wave;
+    const bool active = qt * 16 < n;                     // (wave-uniform)
+    const int q = qt * 16 + fi;
+    e8 q0 = {}, q1 = {};
+    if (active) {
+      const E* qsrc = qbase + (size_t)min(q, n - 1) * rs + fg * 8;
+      q0 = *reinterpret_cast<const e8*>(qsrc);
+      q1 = *reinterpret_cast<const e8*>(qsrc + 32);
+    }
+    fetch(qbase + C, 0);
+    __syncthreads();                                     // every wave is done with the previous unit's images
+    commit(smem);
+    float mrun = -INFINITY, lrun = 0.f;                  // running row maximum (base-2 logit units) and denominator
+    f32x4 o[4];
+#pragma unroll
+    for (int dn = 0; dn < 4; ++dn) o[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < n_chunks; ++c) {
+      __syncthreads();                                   // buffer c & 1 is complete; every wave has left buffer (c + 1) & 1
+      if (c + 1 < n_chunks) fetch(qbase + C, (c + 1) * NK);          // in flight under this chunk's MFMAs
+      if (active) {
+        const int off = (c & 1) * BUF, rem = n - c * NK; // (rem >= 1: the chunk holds a key, its maximum is finite)
+        const FragBases fb = make_frag_bases(smem + off, smem + off + IMG, lane);
+        attn_tile<E, NKT, true>(fb, q0, q1, rem, lane, o, lrun, mrun);
+      }
+      if (c + 1 < n_chunks) commit(smem + ((c + 1) & 1) * BUF);
+    }
+    if (active && q < n) {
+      const float inv = 1.0f / lrun;
       E* dst = out + (size_t)(base + q * ts) * C + head * 64 + fg * 4;
 #pragma unroll
       for (int dn = 0; dn < 4; ++dn) {
@@ -1912,6 +2033,25 @@ int launch_temporal2(const void* qkv, void* out, int n_seq, SeqMap map, int C, i
   return 0;
 }
 
+// n_tok > 256: the chunked-key kernel; a persistent grid of two workgroups per CU (64 KiB of LDS each)
+template <typename E>
+int launch_long2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
+  constexpr int NKT = D3DP_FAST_LONG_NKT;
+  static_assert(NKT == 8 || NKT == 16, "chunks of 128 or 256 keys");
+  const int groups = ((map.n_tok + 15) / 16 + 7) / 8, n_work = n_seq * heads * groups;
+  auto kern = attn_long2_bf16_kernel<E, NKT>;
+  static PerDeviceOnce once;                          // (one per template instantiation = per kernel)
+  const int cus = once.get([&](int dev) {
+    const int r = d3dp_lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024);
+    return r < 0 ? r : d3dp_cu_count(dev);
+  });
+  if (cus < 0) return -3;
+  const int wgs = (NKT == 8 ? 2 : 1) * cus;
+  hipLaunchKernelGGL(kern, dim3(n_work < wgs ? n_work : wgs), dim3(512), (size_t)NKT * 16 * 512, st, (const E*)qkv, (E*)out, map,
+                     C, heads, groups, n_work);
+  return 0;
+}
+
 }  // namespace
 
 // act: 0 = fp32 in/out, 1 = bf16 in/out, 2 = fp32 in, split-bf16 planes out, 3 = fp32 in, split-fp16 planes out,
@@ -1931,15 +2071,17 @@ int d3dp_launch_attn_rows(int act, const void* qkv, void* out, int n_seq, SeqMap
 template <typename E>
 static int attn_temporal2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
   const int n = map.n_tok;
+  if (n > 256) return launch_long2<E>(qkv, out, n_seq, map, C, heads, st);
   if (n <= 32) return launch_temporal2<E, 2>(qkv, out, n_seq, map, C, heads, st);
   if (n <= 64) return launch_temporal2<E, 4>(qkv, out, n_seq, map, C, heads, st);
   if (n <= 128) return launch_temporal2<E, 8>(qkv, out, n_seq, map, C, heads, st);
   return launch_temporal2<E, 16>(qkv, out, n_seq, map, C, heads, st);
 }
-// (f16: 0 = bf16 rows in and out, 1 = IEEE fp16)
+// (f16: 0 = bf16 rows in and out, 1 = IEEE fp16.  Any SeqMap: <= 256 tokens the whole-sequence kernel, up to 1024 the
+//  chunked-key one)
 int d3dp_launch_attn_temporal_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
                                    hipStream_t st, int f16) {
-  if (C / heads != 64 || map.n_tok > 256 || map.n_tok < 1) return -2;
+  if (C / heads != 64 || map.n_tok > 1024 || map.n_tok < 1) return -2;
   return f16 ? attn_temporal2<_Float16>(qkv, out, n_seq, map, C, heads, st) : attn_temporal2<__bf16>(qkv, out, n_seq, map, C, heads, st);
 }
 

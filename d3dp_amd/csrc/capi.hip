@@ -199,7 +199,8 @@ struct d3dp_ctx {
   // sequence's K / V images in LDS; longer clips (`-f 351`, reference common/arguments.py:58, mixste.py:172) take the flash form of the
   // same arithmetic (attention.hip attn_temporal_x2_long_kernel: keys in chunks of 128 under an online softmax; round 5 ran both
   // attentions of such clips on the chunked fp32 VALU row kernel, ten times the cost per FLOP).  D3DP_LONG_ATTN=rows keeps that
-  // kernel as a cross-check (read in d3dp_create).
+  // kernel as a cross-check (read in d3dp_create); a FAST / FAST16 context then keeps the row kernel too, for more than 256 frames
+  // and for more than 32 joints (attention() below).
   bool long_rows = false;
   bool x2_attn() const { return x2() && cfg.channels / cfg.heads == 64 && (cfg.frames <= 256 || !long_rows); }
   // proj / fc2 add into the residual stream in their epilogue (x += ...), so the row kernels read x alone
@@ -375,14 +376,21 @@ int attention(d3dp_ctx* c, int axis, const void* qkv, void* out, int n_bh, float
                                axis == 0 ? spatial_map(g.frames, g.joints, c->seq_pitch())
                                          : temporal_map(g.frames, g.joints, c->seq_pitch()),
                                g.channels, g.heads, s_kv, st);
+  // FAST / FAST16 at head dim 64: every shape on the 2-byte matrix cores -- more than 32 joints on the whole-sequence kernel
+  // of the temporal axis (it takes any SeqMap), more than 256 frames on its chunked-key form.  D3DP_LONG_ATTN=rows keeps
+  // the fp32 VALU row kernel for those two cases, as a cross-check.
+  const bool fast_mfma = c->fast() && g.channels / g.heads == 64;
   if (axis == 0) {
-    if (c->fast() && g.channels / g.heads == 64 && g.joints <= 32)
+    if (fast_mfma && g.joints <= 32)
       return d3dp_launch_attn_spatial_bf16(qkv, out, n_bh * g.frames, spatial_map(g.frames, g.joints), g.channels,
                                            g.heads, st, c->fast_f16);
+    if (fast_mfma && !c->long_rows)
+      return d3dp_launch_attn_temporal_bf16(qkv, out, n_bh * g.frames, spatial_map(g.frames, g.joints), g.channels,
+                                            g.heads, st, c->fast_f16);
     return d3dp_launch_attn_rows(c->act(), qkv, out, n_bh * g.frames, spatial_map(g.frames, g.joints), g.channels,
                                  g.heads, st);
   }
-  if (c->fast() && g.channels / g.heads == 64 && g.frames <= 256)
+  if (fast_mfma && (g.frames <= 256 || !c->long_rows))
     return d3dp_launch_attn_temporal_bf16(qkv, out, n_bh * g.joints, temporal_map(g.frames, g.joints), g.channels,
                                           g.heads, st, c->fast_f16);
   if (c->exact() && g.channels / g.heads == 64 && g.frames <= 256)     // fp32 matrix cores
@@ -537,8 +545,8 @@ const char* d3dp_profile_class_name(int32_t cls) {
 int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   if (!cfg || !out) return fail(D3DP_EINVAL, "d3dp_create: null argument");
   const d3dp_cfg& g = *cfg;
-  // (frames > 256: EXACT and TRAIN contexts take chunked-key forms of their attention kernels, FAST / FAST16 contexts the row
-  //  kernel -- fp32 arithmetic on their 2-byte rows, keys through LDS in chunks of 256)
+  // (frames > 256: every mode takes the chunked-key form of its attention kernels; FAST / FAST16 contexts at a head dim other
+  //  than 64 stay on the row kernel -- fp32 arithmetic on their 2-byte rows)
   if (g.frames < 1 || g.frames > 1024) return fail(D3DP_ENOTSUP, "frames=%d not in [1,1024]", g.frames);
   // (more than 32 joints: the spatial axis takes the whole-sequence attention kernels the temporal axis runs on, round 6)
   if (g.joints < 1 || g.joints > 256) return fail(D3DP_ENOTSUP, "joints=%d not in [1,256]", g.joints);
@@ -1155,7 +1163,9 @@ int d3dp_op_attention(int32_t act_bf16, int32_t impl, int32_t axis, const void* 
     LAUNCH_TRY(rc);
   } else if (axis == 0 && impl == 1) {
     if (!act_bf16) return fail(D3DP_EINVAL, "MFMA spatial attention needs bf16 activations");
-    LAUNCH_TRY(d3dp_launch_attn_spatial_bf16(qkv, out, n_bh * F, spatial_map(F, J), C, heads, st, f16));
+    if (J <= 32) LAUNCH_TRY(d3dp_launch_attn_spatial_bf16(qkv, out, n_bh * F, spatial_map(F, J), C, heads, st, f16));
+    else if (J > 256) return fail(D3DP_ENOTSUP, "MFMA spatial attention takes up to 256 joints; J=%d", J);
+    else LAUNCH_TRY(d3dp_launch_attn_temporal_bf16(qkv, out, n_bh * F, spatial_map(F, J), C, heads, st, f16));   // whole-sequence kernel
   } else if (axis == 0) LAUNCH_TRY(d3dp_launch_attn_rows(act_bf16, qkv, out, n_bh * F, spatial_map(F, J), C, heads, st));
   else if (impl == 1 && !act_bf16) {
     LAUNCH_TRY(d3dp_launch_attn_temporal_f32(0, qkv, out, n_bh * J, temporal_map(F, J), C, heads, st));   // fp32 MFMA

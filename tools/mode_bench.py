@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Interleaved same-process comparison of numerics modes on BASELINE configs[2] (ddim_sample_flip, F=243, J=17, B=16, H=20, K=10).
 
-    python tools/mode_bench.py --numerics fast,fast16 [--steps 20] [--warmup 5] [--rounds 4]
+    python tools/mode_bench.py --numerics fast,fast16 [--steps 20] [--warmup 5] [--rounds 4] [--frames 243]
+
+`--frames N` runs the same sampler on clips of N frames (1 ... 1024).  A `:rows` suffix on a mode name (`fast:rows`, `exact:rows`)
+creates that model's library context with D3DP_LONG_ATTN=rows in the environment: the row attention kernel wherever the mode would
+take a chunked-key or, in the FAST modes, a whole-sequence matrix-core kernel beyond 256 frames / 32 joints -- the A/B of those
+kernels in one process.  The variable is read when a context is created, so every context is created before anything is timed.
 
 Every mode gets its own model (and library context) on the same weights, inputs and generator seed.  After `--warmup` steps of each,
 the timed steps are taken in `--rounds` rounds that visit the modes in turn (a b a b ...), steps / rounds steps per visit, a host
@@ -29,6 +34,7 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--hyps", type=int, default=20)
     ap.add_argument("--ksteps", type=int, default=10)
+    ap.add_argument("--frames", type=int, default=None, help="clip length (default: bench.py's, 243)")
     a = ap.parse_args()
     modes = [m.strip() for m in a.numerics.split(",") if m.strip()]
     if not modes or a.steps < a.rounds or a.rounds < 1 or a.warmup < 0:
@@ -37,9 +43,23 @@ def main():
     import bench
     from d3dp_amd.weights import flip_2d, synthetic_inputs_2d
     B, H, K = a.batch, a.hyps, a.ksteps
-    x2d_np = synthetic_inputs_2d(1234, B, bench.F_)
+    frames = bench.F_ if a.frames is None else a.frames
+    if not 1 <= frames <= 1024 or any(m.count(":") > 1 or (":" in m and not m.endswith(":rows")) for m in modes):
+        ap.error("--frames must be in [1, 1024]; the only mode suffix is ':rows'")
+    x2d_np = synthetic_inputs_2d(1234, B, frames)
     x2d, x2f = torch.from_numpy(x2d_np).cuda(), torch.from_numpy(flip_2d(x2d_np)).cuda()
-    models = {m: bench.build_model(H, K, m, 0) for m in modes}
+    models = {m: bench.build_model(H, K, m.split(":")[0], 0, frames=frames) for m in modes}
+    saved = os.environ.get("D3DP_LONG_ATTN")
+    for m in modes:                                    # the contexts, now: a `:rows` one with the switch set for its creation
+        if m.endswith(":rows"):
+            os.environ["D3DP_LONG_ATTN"] = "rows"
+        try:
+            models[m].pose_estimator._context(torch.device("cuda", torch.cuda.current_device()))
+        finally:
+            if m.endswith(":rows"):
+                os.environ.pop("D3DP_LONG_ATTN")
+                if saved is not None:
+                    os.environ["D3DP_LONG_ATTN"] = saved
     gens = {m: torch.Generator(device="cuda").manual_seed(1) for m in modes}
     teles = {m: bench.GpuTelemetry(torch.cuda.current_device()) for m in modes}
     for m in modes:
@@ -59,7 +79,7 @@ def main():
             visits[m].append((time.perf_counter() - t0) / n)
             teles[m].stop()
             assert bool(torch.isfinite(out).all())
-    res = {"workload": f"BASELINE configs[2]: ddim_sample_flip F={bench.F_} J=17 B={B} H={H} K={K} flip-TTA, cs=512 dep=8",
+    res = {"workload": f"{'BASELINE configs[2]: ' if frames == bench.F_ else ''}ddim_sample_flip F={frames} J=17 B={B} H={H} K={K} flip-TTA, cs=512 dep=8",
            "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "order": modes, "library_sha256": bench.lib_sha256(), "modes": {}}
     for m in modes:
         dt = sum(v * n for v, n in zip(visits[m], per_visit))
