@@ -86,6 +86,7 @@ struct BlockDev {
   // the bound is below 4094, the largest smaller power of two that keeps bound x scale below fp16's 65504 otherwise
   // (LayerNorm outputs always use 2^4: their bound is sqrt(C-1) |gamma| + |beta|).
   float s_kv = kActScale, s_h = kActScale;
+  const float* proj_bgb = nullptr;  // defer_norm: [proj_b | gamma | beta] of the shared norm in FRONT of the block (EPI_RESID_NORM)
 };
 
 template <typename E>   // E: bf16 or f16 -- a plain cast, round to nearest even
@@ -214,6 +215,16 @@ struct d3dp_ctx {
   // the operand and reduces the statistics with the matrix pipes idle) and +90 ms in fc1 (profiles/r03_fold_ln_ab.md).
   bool fold_ln() const { return fold_resid() && fold_ln_on && 2 * cfg.hidden <= 2048; }
   bool fold_ln_on = false;
+  // The shared norm at a block boundary (Spatial_norm in front of the TTE blocks, Temporal_norm in front of the STE blocks d >= 1)
+  // is DEFERRED into the next block's proj: the norm pair stores the next qkv operand and 8 bytes of (mean, rstd) per row but does
+  // not rewrite x (2 KB per row at C = 512, a third of its traffic); proj, the first kernel to touch x again and one that reads
+  // and writes that row anyway, forms LN(x) in its epilogue (EPI_RESID_NORM) -- the same expression on the same values, so every
+  // result bit stays.  The boundary that adds Temporal_pos (after STE block 0) keeps the in-place form.  D3DP_DEFER_NORM=0 keeps it
+  // everywhere: the cross-check.  Plain-kernel dataflow only (proj's k-loop must cover the statistics' double buffer: C >= 96).
+  bool defer_norm() const {
+    return fold_resid() && defer && !fold_ln() && skew_d == 0 && pingpong == 0 && cfg.channels >= 96 && 3 * cfg.channels <= 2048;
+  }
+  bool defer = true;
   // The EXACT qkv / fc1 Linears run the SKEWED schedule of gemm_x2.hip (a tile's epilogue spread under the k-loop of the
   // next): the order in which a token row sums its k-steps then depends on (row within its pass) / 16 mod 4.  Every sequence
   // therefore starts at a multiple of 64 rows -- seq_pitch() rows per sequence, F J rounded up, the rest finite filler -- so
@@ -405,8 +416,10 @@ int attention(d3dp_ctx* c, int axis, const void* qkv, void* out, int n_bh, float
 // (activation type: bf16 in FAST mode, fp16 in FAST16 -- one more 2-byte rounding on the branch output, none on the fp32 residual
 // stream itself) and the next row-wise kernel (LN2 here; the norm pair / head in the caller) performs x += y while it has the row in
 // registers anyway.  On return y1 / y hold the proj / fc2 outputs that the CALLER's next kernel must add to x.
+// nstat: non-null if the norm pair in front of the block DEFERRED its shared norm (d3dp_ctx::defer_norm): x is still
+// un-normalised, (mean, rstd) per row are there, and proj applies the norm as it adds (gamma / beta behind its bias: w.proj_bgb).
 int run_block(d3dp_ctx* c, const BlockDev& w, int axis, float* x, void* y1, void* y, void* bufA, void* bufB, float* lnst,
-              int n_bh, hipStream_t st) {
+              int n_bh, hipStream_t st, float* nstat = nullptr) {
   const d3dp_cfg& g = c->cfg;
   const int Tc = n_bh * c->seq_pitch(), C = g.channels;
   // (s_kv / s_h differ from kActScale only in EXACT f16x2 contexts whose weights asked for it, and s_kv only with the x2
@@ -426,7 +439,8 @@ int run_block(d3dp_ctx* c, const BlockDev& w, int axis, float* x, void* y1, void
     }
     LAUNCH_TRY(linear(c, P_FC1, EPI_GELU_LN, 0, y1, w.fc1_w, w.fc1_u, w.fc1_c12, bufB, Tc, g.hidden, C, st, bufB, rowstat, kActScale, w.s_h));
   } else {
-  LAUNCH_TRY(linear(c, P_PROJ, fold ? EPI_RESID : EPI_BIAS, 0, bufA, w.proj_w, w.proj_u, w.proj_b, fold ? (void*)x : y1, Tc, C, C, st, nullptr, nullptr, s_o));
+  if (nstat) LAUNCH_TRY(linear(c, P_PROJ, EPI_RESID_NORM, 0, bufA, w.proj_w, w.proj_u, w.proj_bgb, x, Tc, C, C, st, nullptr, nstat, s_o));
+  else LAUNCH_TRY(linear(c, P_PROJ, fold ? EPI_RESID : EPI_BIAS, 0, bufA, w.proj_w, w.proj_u, w.proj_b, fold ? (void*)x : y1, Tc, C, C, st, nullptr, nullptr, s_o));
   {
     Scope s(c, P_LN, st);      // xn = LN2(x + y1); x itself stays untouched (the caller's norm pair adds y1 and y)
     LAUNCH_TRY(d3dp_launch_ln(c->act(), x, fold ? nullptr : y1, 0, w.n2w, w.n2b, g.eps_block, bufA, Tc, C, st));
@@ -454,6 +468,8 @@ int read_switches(d3dp_ctx* c, bool width_inst) {
   c->long_rows = lr && !strcmp(lr, "rows");
   const char* nf = getenv("D3DP_NO_FOLD");               // cross-check: residual adds (and norm2) in the row kernels
   c->fold = !(nf && nf[0] == '1');
+  const char* dn = getenv("D3DP_DEFER_NORM");            // cross-check: =0 keeps the shared norms in place in the norm pair
+  c->defer = !(dn && dn[0] == '0');
   const char* ti = getenv("D3DP_TRAIN_IMPL");
   c->train_x2 = !(ti && !strcmp(ti, "f32")) && width_inst;     // (a width outside the instantiated set: the fp32 path)
   const char* ov = getenv("D3DP_TRAIN_OVERLAP");
@@ -779,7 +795,7 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
   const size_t i_tnw = add(w->temporal_norm_w, C, false), i_tnb = add(w->temporal_norm_b, C, false);
   const size_t i_hnw = add(w->head_norm_w, C, false), i_hnb = add(w->head_norm_b, C, false);
   const size_t i_hw = add(w->head_w, 3 * C, false), i_hb = add(w->head_b, 3, false);
-  struct BI { size_t v[13]; };
+  struct BI { size_t v[13]; bool bgb; };
   std::vector<BI> bis;
   // fold_ln: fc1 runs on W diag(gamma2) with [c2 | c1] in place of its bias (computed into temporaries that live until the
   // synchronisation below)
@@ -794,6 +810,13 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
       bi.v[0] = add(b.norm1_w, C, false); bi.v[1] = add(b.norm1_b, C, false);
       bi.v[2] = add(b.qkv_w, 3 * C * C, true); bi.v[3] = add(b.qkv_b, 3 * C, false);
       bi.v[4] = add(b.proj_w, C * C, true); bi.v[5] = add(b.proj_b, C, false);
+      // defer_norm: gamma / beta of the shared norm in front of the block right behind proj's bias -- one array [b | gamma | beta]
+      // (C floats are whole 256-byte units at the widths of the split-fp16 kernels, so the three items lie back to back)
+      bi.bgb = c->defer_norm() && (C * 4) % kAlign == 0;
+      if (bi.bgb) {
+        add(kind == 0 ? w->temporal_norm_w : w->spatial_norm_w, C, false);
+        add(kind == 0 ? w->temporal_norm_b : w->spatial_norm_b, C, false);
+      }
       bi.v[6] = add(b.norm2_w, C, false); bi.v[7] = add(b.norm2_b, C, false);
       if (c->fold_ln()) {
         float *wp = nullptr, *c12 = nullptr;
@@ -864,6 +887,7 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
                F32(bi.v[11]), ANY(bi.v[2]), ANY(bi.v[4]), ANY(bi.v[8]), ANY(bi.v[10]),
                unscale[bi.v[2]], unscale[bi.v[4]], unscale[bi.v[8]], unscale[bi.v[10]], F32(bi.v[12]),
                blk_scale[2 * k], blk_scale[2 * k + 1]};
+    if (bi.bgb) b.proj_bgb = F32(bi.v[5]);
     (k < (size_t)g.depth ? c->ste : c->tte).push_back(b);
   }
   c->weights_set = true;
@@ -905,7 +929,8 @@ int d3dp_workspace_bytes(const d3dp_ctx* c, int32_t B, int32_t H, size_t* bytes)
   const size_t wide = (size_t)std::max(3 * g.channels, g.hidden);
   *bytes = align_up((size_t)B * C * 4) + align_up(Tc * C * 4) + 2 * align_up(Tc * C * c->y_size()) +
            align_up(Tc * C * c->act_size()) + align_up(Tc * wide * c->wide_size()) +
-           (c->fold_ln() ? align_up(Tc * ((C + 63) / 64) * 8) + align_up((Tc + 256) * 8) : 0);
+           (c->fold_ln() ? align_up(Tc * ((C + 63) / 64) * 8) + align_up((Tc + 256) * 8) : 0) +
+           (c->defer_norm() ? align_up((Tc + 256) * 8) : 0);   // (mean, rstd) per row + a tile of slack: proj's loaders fetch whole tiles
   return D3DP_OK;
 }
 
@@ -931,6 +956,10 @@ int d3dp_denoise(d3dp_ctx* c, const float* x2d, const float* x_t, const int64_t*
   void* bufB = p;          p += align_up(Tmax * (size_t)std::max(3 * g.channels, g.hidden) * c->wide_size());
   float* lnst = (float*)p;                               // fold_ln: slice statistics, then (mean, rstd) per row
   c->ln_slice_floats = align_up(Tmax * ((C + 63) / 64) * 8) / 4;
+  if (c->fold_ln()) p += align_up(Tmax * ((C + 63) / 64) * 8) + align_up((Tmax + 256) * 8);
+  // deferred shared norms: (mean, rstd) [Tmax + 256][2], written by every deferring norm pair for the rows of its pass and read
+  // by the proj behind it for those rows alone (the slack rows are fetched into LDS and never used)
+  float* nstat = c->defer_norm() ? (float*)p : nullptr;
 
   {
     Scope s(c, P_TIME, st);
@@ -946,16 +975,24 @@ int d3dp_denoise(d3dp_ctx* c, const float* x2d, const float* x_t, const int64_t*
     }
     const bool fold = c->fold_resid();
     for (int d = 0; d < g.depth; ++d) {
-      int r = run_block(c, c->ste[d], 0, x, y1, y, bufA, bufB, lnst, n, st);
+      // (the boundary in front of STE block d >= 1 deferred Temporal_norm; the one in front of TTE block d >= 1 Spatial_norm)
+      const bool defer = nstat != nullptr && c->ste[d].proj_bgb && c->tte[d].proj_bgb;
+      int r = run_block(c, c->ste[d], 0, x, y1, y, bufA, bufB, lnst, n, st, defer && d > 0 ? nstat : nullptr);
       if (r) return r;
-      {
+      if (defer && d > 0) {
+        Scope s(c, P_LN2, st);   // Spatial_norm deferred into TTE block d's proj; TTE block d's norm1
+        LAUNCH_TRY(d3dp_launch_ln2_defer(c->act(), x, c->snw, c->snb, c->tte[d].n1w, c->tte[d].n1b, g.eps_block, bufA, nstat, Tc, C, st));
+      } else {
         Scope s(c, P_LN2, st);   // x += fc2 out; Spatial_norm (+ Temporal_pos after block 0); TTE block d's norm1
         LAUNCH_TRY(d3dp_launch_ln2(c->act(), x, fold ? nullptr : y1, fold ? nullptr : y, c->snw, c->snb, d == 0 ? c->tpos : nullptr, c->tte[d].n1w,
                                    c->tte[d].n1b, g.eps_block, bufA, Tc, C, F, J, st, SP));
       }
-      r = run_block(c, c->tte[d], 1, x, y1, y, bufA, bufB, lnst, n, st);
+      r = run_block(c, c->tte[d], 1, x, y1, y, bufA, bufB, lnst, n, st, defer && d > 0 ? nstat : nullptr);
       if (r) return r;
-      if (d + 1 < g.depth) {
+      if (d + 1 < g.depth && defer) {
+        Scope s(c, P_LN2, st);   // Temporal_norm deferred into STE block d+1's proj; STE block d+1's norm1
+        LAUNCH_TRY(d3dp_launch_ln2_defer(c->act(), x, c->tnw, c->tnb, c->ste[d + 1].n1w, c->ste[d + 1].n1b, g.eps_block, bufA, nstat, Tc, C, st));
+      } else if (d + 1 < g.depth) {
         Scope s(c, P_LN2, st);   // x += fc2 out; Temporal_norm; STE block d+1's norm1
         LAUNCH_TRY(d3dp_launch_ln2(c->act(), x, fold ? nullptr : y1, fold ? nullptr : y, c->tnw, c->tnb, nullptr, c->ste[d + 1].n1w, c->ste[d + 1].n1b,
                                    g.eps_block, bufA, Tc, C, F, J, st, SP));
@@ -1122,7 +1159,7 @@ int d3dp_op_linear_x2(int32_t epi, const void* A2, const void* W2, const float* 
     return fail(D3DP_ENOTSUP, "d3dp_op_linear_x2: epi flags %d select an experiment kernel this library was built without "
                               "(make -C d3dp_amd/csrc variants)", epi & ~0xff);
   epi &= 255;
-  if (epi == EPI_RESID_LN || epi == EPI_GELU_LN) return fail(D3DP_EINVAL, "d3dp_op_linear_x2: epilogues 5 / 6 are internal to d3dp_denoise");
+  if (epi == EPI_RESID_LN || epi == EPI_GELU_LN || epi == EPI_RESID_NORM) return fail(D3DP_EINVAL, "d3dp_op_linear_x2: epilogues 5 / 6 / 7 are internal to d3dp_denoise");
   if (skew_d) {
     int dev = 0;
     hipDeviceProp_t prop;

@@ -36,7 +36,10 @@
 //   EPI_GELU     -> GELU (rational erf, common.h) re-split into the h2i rows of the fc2 operand
 //   EPI_QKV_PACK -> q fp32, k and v as fp16 planes: the packed rows the split-fp16 attention kernels read (attention.hip)
 //   EPI_RESID    -> x += A W^T + b in place on the fp32 residual stream (proj, fc2: mixste.py:113-115)
-//   EPI_RESID_LN -> the same, and the sum leaves a second time as the NEXT Linear's split-fp16 operand (un-normalised) together
+//   EPI_RESID_NORM -> EPI_RESID behind a DEFERRED LayerNorm of the residual row: x = LN(x) + A W^T + b, the LayerNorm's (mean, rstd)
+//                   per row left by the row kernel in front (pointwise.hip ln2_defer_kernel), its gamma / beta behind the bias: the
+//                   proj Linear behind a block boundary, whose norm pair then does not rewrite x
+//   EPI_RESID_LN -> the same as EPI_RESID, and the sum leaves a second time as the NEXT Linear's split-fp16 operand (un-normalised) together
 //                   with (mean, M2) of each 64-column slice of each row: the statistics of the LayerNorm that follows
 //   EPI_GELU_LN  -> EPI_GELU of a Linear with that LayerNorm folded in: LN(x) W^T + b = rstd (x W'^T - mean c1) + c2 with
 //                   W' = W diag(gamma), c1 = W' 1, c2 = W beta + b -- norm2 + fc1 (mixste.py:115) without a row kernel in between
@@ -111,7 +114,7 @@ __global__ __launch_bounds__(768) void gemm_f16x2_kernel(const f16* __restrict__
   const int t_flip = tiles_n_arg < 0 ? total_tiles - 1 : 0, t_sign = tiles_n_arg < 0 ? -1 : 1;
   auto tile_of = [&](int ti_) { return t_flip + t_sign * (L + ti_ * G); };
 
-  for (int i = tid; i < (EPI == EPI_GELU_LN ? 2 * N : N); i += (XNCW + 4) * 64) sbias[i] = bias[i];   // (GELU_LN: c2 | c1)
+  for (int i = tid; i < (EPI == EPI_GELU_LN ? 2 * N : EPI == EPI_RESID_NORM ? 3 * N : N); i += (XNCW + 4) * 64) sbias[i] = bias[i];   // (GELU_LN: c2 | c1; RESID_NORM: b | gamma | beta)
   __syncthreads();
 
   if (wave >= XNCW) {
@@ -137,7 +140,7 @@ __global__ __launch_bounds__(768) void gemm_f16x2_kernel(const f16* __restrict__
           pw[i] = W2 + (size_t)min(n0 + wrow, N - 1) * (2 * K) + swz128(row, lq) * 8;
         }
       }
-      if constexpr (EPI == EPI_GELU_LN) {
+      if constexpr (EPI == EPI_GELU_LN || EPI == EPI_RESID_NORM) {
         // the tile's 256 (mean, rstd) pairs: 2 KiB = two pieces, by loader wave 0, the OLDEST operations of this k-step
         // (every counted wait below then covers them); buffer ti & 1 -- the epilogue of tile ti - 1 may still be reading
         if (ks == 0 && lw == 0) {
@@ -280,6 +283,12 @@ __global__ __launch_bounds__(768) void gemm_f16x2_kernel(const f16* __restrict__
         c1z = *reinterpret_cast<const float4*>(sbias + N + nb);
         srow = reinterpret_cast<const float*>(smem + XROWSTAT + (ti & 1) * (XBM * 8)) + (wr * 64 + 4 * fg) * 2;
       }
+      [[maybe_unused]] float4 gmz = {}, btz = {};      // EPI_RESID_NORM: gamma / beta of the lane's four columns
+      if constexpr (EPI == EPI_RESID_NORM) {
+        gmz = *reinterpret_cast<const float4*>(sbias + N + nb);
+        btz = *reinterpret_cast<const float4*>(sbias + 2 * N + nb);
+        srow = reinterpret_cast<const float*>(smem + XROWSTAT + (ti & 1) * (XBM * 8)) + (wr * 64 + 4 * fg) * 2;
+      }
       auto value = [&](int mi, int r, int e) {
         const float bze = e == 0 ? bz.x : e == 1 ? bz.y : e == 2 ? bz.z : bz.w;
         if constexpr (EPI == EPI_GELU_LN) {            // rstd (x W'^T - mean c1) + c2
@@ -314,7 +323,7 @@ __global__ __launch_bounds__(768) void gemm_f16x2_kernel(const f16* __restrict__
                 ph[e] = h; pl[e] = l;
               }
               store_planes_paired(dst, ph, pl, odd, live);
-            } else if constexpr (EPI != EPI_RESID && EPI != EPI_RESID_LN) {
+            } else if constexpr (EPI != EPI_RESID && EPI != EPI_RESID_LN && EPI != EPI_RESID_NORM) {
               if (live) OUT_STORE(reinterpret_cast<f32x4*>(dst), ((f32x4){value(mi, r, 0), value(mi, r, 1), value(mi, r, 2), value(mi, r, 3)}));
             }
           }
@@ -340,6 +349,42 @@ __global__ __launch_bounds__(768) void gemm_f16x2_kernel(const f16* __restrict__
                                res[mi][r][2] + value(mi, r, 2), res[mi][r][3] + value(mi, r, 3)};
               if (live) *reinterpret_cast<f32x4*>(base + (off + (unsigned)k * pitch)) = v;   // (re-read by the next row kernel: no nt hint)
             }
+        }
+        if constexpr (EPI == EPI_RESID_NORM && !decltype(planes_c)::value) {
+          // x = LN(x) + A W^T + b in place.  gamma, beta and a row's statistics beside the accumulators leave room for twelve of
+          // the sixteen row reads (168 registers, 12-wave workgroup): row blocks 0 - 2 are in flight before the first add, and row
+          // block 3 is read into block 0's registers once block 0 has left.
+          f32x4 res[3][4];
+          auto read_block = [&](int mi, f32x4 (&dstv)[4]) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int k = mi * 16 + r;
+              const bool live = !decltype(checked_c)::value || k < rows;
+              dstv[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+              if (live) dstv[r] = *reinterpret_cast<const f32x4*>(base + (off + (unsigned)k * pitch));
+            }
+          };
+#pragma unroll
+          for (int mi = 0; mi < 3; ++mi) read_block(mi, res[mi]);
+#pragma unroll
+          for (int mi = 0; mi < 4; ++mi) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int k = mi * 16 + r;
+              const bool live = !decltype(checked_c)::value || k < rows;
+              // the deferred LayerNorm of the residual row, as Row<C>::norm (pointwise.hip) writes it: subtract, multiply, fma --
+              // on the x the row kernel read and the (mean, rstd) it left, so the bits it would have stored over x
+              const float2 st = *reinterpret_cast<const float2*>(srow + k * 2);
+              const f32x4 x = res[mi % 3][r];
+              const f32x4 v = {fmaf((x[0] - st.x) * st.y, gmz.x, btz.x) + value(mi, r, 0), fmaf((x[1] - st.x) * st.y, gmz.y, btz.y) + value(mi, r, 1),
+                               fmaf((x[2] - st.x) * st.y, gmz.z, btz.z) + value(mi, r, 2), fmaf((x[3] - st.x) * st.y, gmz.w, btz.w) + value(mi, r, 3)};
+              if (live) *reinterpret_cast<f32x4*>(base + (off + (unsigned)k * pitch)) = v;   // (re-read by the next row kernel: no nt hint)
+            }
+            if (mi == 0) {
+              __builtin_amdgcn_sched_barrier(0);
+              read_block(3, res[0]);
+            }
+          }
         }
         if constexpr (EPI == EPI_RESID_LN && !decltype(planes_c)::value) {
           // x += A W^T + b in place, in two halves of eight rows per lane (the sums stay in registers for what follows, and
@@ -489,6 +534,7 @@ void d3dp_launch_fold_ln(const float*, const float*, const float*, const float*,
 // out = epi((A W^T) unscale + bias) with A2/W2 split-fp16 operands in the h2i layout; EPI_BIAS: fp32 `outf`; EPI_GELU: `out2` in the h2i layout [M][N] (the fc2 operand);
 // EPI_QKV_PACK (N = 3 C, C % 64 == 0): `outf` rows of 12 C bytes = q fp32 | k hi | k lo | v hi | v lo (fp16 x 16);
 // EPI_RESID: `outf` [M, N] fp32 is read and written (outf += ...).
+// EPI_RESID_NORM: the same with outf's rows normalised first: bias = [b | gamma | beta], aux = [M + 256][2] (mean, rstd) per row.
 // `unscale` = 1 / (scale of the A planes * scale of the W planes).
 // K must be a multiple of 64: the k-loop is unrolled by two k-steps of 32 (the lagged products alternate between two
 // register sets), and the loader / compute waves count barriers per k-step.
@@ -502,7 +548,9 @@ int d3dp_launch_linear_f16x2(int epi, const void* A2, const void* W2, const floa
   if (K % (2 * XBK) != 0 || N % 4 != 0 || N > XBIAS_MAX || M <= 0) return -1;
   if ((size_t)M * N * 4 >= ((size_t)1 << 32)) return -1;   // 32-bit byte offsets in the epilogue
   if (epi != EPI_BIAS && epi != EPI_GELU && epi != EPI_QKV_PACK && epi != EPI_RESID && epi != EPI_RESID_LN &&
-      epi != EPI_GELU_LN) return -1;
+      epi != EPI_GELU_LN && epi != EPI_RESID_NORM) return -1;
+  // the row statistics come through the two LDS buffers of EPI_GELU_LN (see below for the k-loop condition); b | gamma | beta in the bias area
+  if (epi == EPI_RESID_NORM && (!aux || 3 * N > XBIAS_MAX || K / XBK < XNSTAGE)) return -1;
   if ((epi == EPI_RESID_LN || epi == EPI_GELU_LN) && (!aux || !out2)) return -1;
   if (epi == EPI_RESID_LN && !flag) return -1;
   if (epi == EPI_RESID_LN && N % 64 != 0) return -1;    // whole 64-column slices: every compute wave's columns exist
@@ -516,16 +564,18 @@ int d3dp_launch_linear_f16x2(int epi, const void* A2, const void* W2, const floa
   const int tm = (M + XBM - 1) / XBM, tn = (N + XBN - 1) / XBN;
   using KernT = void (*)(const f16*, const f16*, const float*, float, float, float*, f16*, float*, unsigned*, int, int, int, int, int);
 #if D3DP_X2_VARIANTS
-  constexpr int NKERN = 6;
+  constexpr int NKERN = 7;
   static const KernT kerns[NKERN] = {gemm_f16x2_kernel<EPI_BIAS, 0>, gemm_f16x2_kernel<EPI_BIAS, 1>,
                                      gemm_f16x2_kernel<EPI_GELU, 0>, gemm_f16x2_kernel<EPI_RESID, 0>,
+                                     gemm_f16x2_kernel<EPI_RESID_NORM, 0>,
                                      gemm_f16x2_kernel<EPI_RESID_LN, 0>, gemm_f16x2_kernel<EPI_GELU_LN, 0>};
 #else
-  // the product library: the four epilogues the denoiser runs; everything else is a -DD3DP_X2_VARIANTS=1 build
+  // the product library: the five epilogues the denoiser runs; everything else is a -DD3DP_X2_VARIANTS=1 build
   if (epi == EPI_RESID_LN || epi == EPI_GELU_LN || skew_d != 0 || pingpong != 0) return -2;
-  constexpr int NKERN = 4;
+  constexpr int NKERN = 5;
   static const KernT kerns[NKERN] = {gemm_f16x2_kernel<EPI_BIAS, 0>, gemm_f16x2_kernel<EPI_BIAS, 1>,
-                                     gemm_f16x2_kernel<EPI_GELU, 0>, gemm_f16x2_kernel<EPI_RESID, 0>};
+                                     gemm_f16x2_kernel<EPI_GELU, 0>, gemm_f16x2_kernel<EPI_RESID, 0>,
+                                     gemm_f16x2_kernel<EPI_RESID_NORM, 0>};
 #endif
   // per DEVICE: the 156 KiB dynamic-LDS opt-in of every instantiation and the CU count (one process may drive several
   // devices: nn.DataParallel callers)
@@ -542,8 +592,8 @@ int d3dp_launch_linear_f16x2(int epi, const void* A2, const void* W2, const floa
   const int taken = x2_variants_launch(epi, A2, W2, bias, unscale, oscale, outf, out2, aux, flag, M, N, K, st, skew_d, pingpong, cus);
   if (taken <= 0) return taken;
 #endif
-  const KernT kern = kerns[epi == EPI_GELU ? 2 : epi == EPI_RESID ? 3 : epi == EPI_QKV_PACK ? 1 : epi == EPI_RESID_LN ? 4
-                           : epi == EPI_GELU_LN ? 5 : 0];   // (4, 5: the product library has refused them above)
+  const KernT kern = kerns[epi == EPI_GELU ? 2 : epi == EPI_RESID ? 3 : epi == EPI_QKV_PACK ? 1 : epi == EPI_RESID_NORM ? 4
+                           : epi == EPI_RESID_LN ? 5 : epi == EPI_GELU_LN ? 6 : 0];   // (5, 6: the product library has refused them above)
   hipLaunchKernelGGL(kern, dim3(grid), dim3((XNCW + 4) * 64), XLDS, st, (const f16*)A2, (const f16*)W2, bias, unscale, oscale, outf,
                      (f16*)out2, aux, flag, M, N, K, reverse ? -tn : tn, total);
   return 0;

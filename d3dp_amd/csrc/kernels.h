@@ -36,7 +36,8 @@ inline int d3dp_lds_opt_in(const void* kern, int bytes) {
   return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? 1 : -3;
 }
 
-enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_PARTIAL = 3, EPI_QKV_PACK = 4, EPI_RESID_LN = 5, EPI_GELU_LN = 6 };
+enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_PARTIAL = 3, EPI_QKV_PACK = 4, EPI_RESID_LN = 5, EPI_GELU_LN = 6,
+       EPI_RESID_NORM = 7 };
 
 // ---- gemm.hip ----------------------------------------------------------------------------------
 // (f16: the 2-byte type of A, W and a 2-byte out -- 0 = bf16, 1 = IEEE fp16)
@@ -51,6 +52,10 @@ void d3dp_launch_split3(const float* src, void* dst, size_t n, hipStream_t st);
 // EPI_GELU_LN: a LayerNorm FOLDED into the Linear: A2 = un-normalised rows, W2 = W . diag(gamma), bias = [c2 | c1] (2 N floats:
 //   c2 = W beta + b, c1 = row sums of W diag(gamma)), aux = [M + 256][2] (mean, rstd) per row:
 //   out2 = split(GELU(rstd (A W'^T - mean c1) + c2)).
+// EPI_RESID_NORM (internal to d3dp_denoise like 5 / 6): outf = LN(outf) + A W^T + b -- EPI_RESID behind a DEFERRED LayerNorm of
+//   the residual row: bias = [b | gamma | beta] (3 N floats), aux = [M + 256][2] (mean, rstd) per row as d3dp_launch_ln2_defer left
+//   them; every residual value read becomes fmaf((x - mean) * rstd, gamma, beta), the expression of the row kernels, before
+//   the Linear's value is added.  3 N <= 2048, K >= 96.
 // `unscale` = 1 / (scale of the A operand x scale of the W operand); `oscale` = the power of two the plane outputs (EPI_GELU*,
 // k / v of EPI_QKV_PACK, the operand copy of EPI_RESID_LN) are multiplied by before the hi / lo split (kActScale unless the
 // proven range of that operand asks for less, capi.hip)
@@ -197,6 +202,10 @@ int d3dp_launch_ln(int act_bf16, float* x, const void* yadd, int write_x, const 
 int d3dp_launch_ln2(int act_bf16, float* x, const void* yadd0, const void* yadd, const float* wa, const float* ba, const float* pos,
                     const float* wb, const float* bb, float eps, void* xn, int T, int C, int F, int J, hipStream_t st,
                     int SP = 0);
+// the norm pair with its first norm DEFERRED: xn = LN_b(LN_a(x)), x untouched, stat[T][2] = (mean, rstd) of LN_a per row -- the
+// next Linear that adds into x applies LN_a itself (EPI_RESID_NORM).  act_bf16 = 3 (split-fp16 planes) only.
+int d3dp_launch_ln2_defer(int act_bf16, const float* x, const float* wa, const float* ba, const float* wb, const float* bb, float eps,
+                          void* xn, float* stat, int T, int C, hipStream_t st);
 // out[T,3] = Linear(LN_head(LN_a(x)))
 int d3dp_launch_head(int act_bf16, const float* x, const void* yadd0, const void* yadd, const float* wa, const float* ba, float eps_a, const float* wh,
                      const float* bh, float eps_h, const float* w, const float* b, float* out, int T, int C,

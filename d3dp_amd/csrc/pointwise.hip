@@ -169,9 +169,9 @@ template <int C> struct Row {
       }
     }
   }
-  // y = (v - mean) * rstd * w + b   (two-pass statistics, biased variance as torch LayerNorm)
-  static __device__ __forceinline__ void norm(const float* v, const float* w, const float* b, float eps, int lane,
-                                              float* y) {
+  // y = (v - mean) * rstd * w + b   (two-pass statistics, biased variance as torch LayerNorm); returns (mean, rstd)
+  static __device__ __forceinline__ float2 norm(const float* v, const float* w, const float* b, float eps, int lane,
+                                                float* y) {
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) s += v[i];
@@ -185,9 +185,10 @@ template <int C> struct Row {
     load(b, lane, bv);
 #pragma unroll
     for (int i = 0; i < NV; ++i) y[i] = fmaf((v[i] - mean) * rstd, wv[i], bv[i]);
+    return make_float2(mean, rstd);
   }
   // the same arithmetic on weights the caller already holds in registers (kernels that keep them across several tokens)
-  static __device__ __forceinline__ void norm_r(const float* v, const float* wv, const float* bv, float eps, float* y) {
+  static __device__ __forceinline__ float2 norm_r(const float* v, const float* wv, const float* bv, float eps, float* y) {
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) s += v[i];
@@ -198,6 +199,7 @@ template <int C> struct Row {
     const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / C) + eps);
 #pragma unroll
     for (int i = 0; i < NV; ++i) y[i] = fmaf((v[i] - mean) * rstd, wv[i], bv[i]);
+    return make_float2(mean, rstd);
   }
 };
 
@@ -279,6 +281,43 @@ __global__ __launch_bounds__(256) void ln2_kernel(float* __restrict__ x, const Y
   if (NT_STREAMS) R::store_nt(x + (size_t)tok * C, lane, y); else R::store(x + (size_t)tok * C, lane, y);
   R::norm(y, wb, bb, eps, lane, z);
   ActOut<C, XN>::st(xn, plane, (size_t)tok * C, lane, z);
+}
+
+// The DEFERRED norm pair (EXACT split-fp16 contexts with the residual fold on, boundaries without Temporal_pos): the same loads
+// and the same two norms as ln2_kernel, but y = LN_shared(x) is NOT stored over x.  The row leaves (mean, rstd) of that first
+// norm instead -- 8 bytes in place of 4 C -- and the next block's proj Linear, the first kernel to touch x again (qkv reads xn,
+// the attention reads qkv's output), forms y = fmaf((x - mean) * rstd, wa, ba) from the untouched x inside its x += ...
+// epilogue (gemm_x2.hip EPI_RESID_NORM): the expression of Row<C>::norm on the same fp32 values, so no bit of x moves.
+// kDeferRows rows per wave, the two norms' weights held in registers across them (Row<C>::norm_r: the arithmetic of norm; as
+// embed_ln_kernel / head_kernel below).  Measured on configs[2], norm-pair class per step, one box: 297 ms at one row per wave --
+// with a third of the row traffic gone, the 8 KB of weight reads per row were the larger part of what a wave issued -- against
+// 280 / 277 / 279 ms at 2 / 4 / 8 rows (profiles/defer_norm_ab.md).
+constexpr int kDeferRows = 4;
+
+template <int C, typename XN>
+__global__ __launch_bounds__(256) void ln2_defer_kernel(const float* __restrict__ x, const float* __restrict__ wa,
+                                                        const float* __restrict__ ba, const float* __restrict__ wb,
+                                                        const float* __restrict__ bb, float eps,
+                                                        typename ActOut<C, XN>::ptr xn, float2* __restrict__ stat,
+                                                        size_t plane, int T) {
+  using R = Row<C>;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  float wav[R::NV], bav[R::NV], wbv[R::NV], bbv[R::NV];
+  R::load(wa, lane, wav);
+  R::load(ba, lane, bav);
+  R::load(wb, lane, wbv);
+  R::load(bb, lane, bbv);
+  for (int it = 0; it < kDeferRows; ++it) {
+    const int tok = (blockIdx.x * kDeferRows + it) * 4 + wave;
+    if (tok >= T) break;
+    float v[R::NV], y[R::NV], z[R::NV];
+    if (NT_STREAMS) R::load_nt(x + (size_t)tok * C, lane, v); else R::load(x + (size_t)tok * C, lane, v);
+    const float2 st = R::norm_r(v, wav, bav, eps, y);
+    if (lane == 0) stat[tok] = st;
+    R::norm_r(y, wbv, bbv, eps, z);
+    ActOut<C, XN>::st(xn, plane, (size_t)tok * C, lane, z);
+  }
 }
 
 // Tokens per wave of embed_ln_kernel / head_kernel: the weights of a lane's columns (embedding: 5 + 1 values per column; the
@@ -675,6 +714,17 @@ int d3dp_launch_ln2(int act_bf16, float* x, const void* yadd0, const void* yadd,
     else if (act_bf16 == 2) hipLaunchKernelGGL((ln2_kernel<CC, b3, float>), g, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, pos, wb, bb, eps, (bf16*)xn, plane, T, F, J, SP);
     else if (act_bf16 == 3) hipLaunchKernelGGL((ln2_kernel<CC, h2, float>), g, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, pos, wb, bb, eps, (f16*)xn, plane, T, F, J, SP);
     else hipLaunchKernelGGL((ln2_kernel<CC, float, float>), g, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, pos, wb, bb, eps, (float*)xn, plane, T, F, J, SP))
+  return 0;
+}
+
+// the deferred form of the norm pair (ln2_defer_kernel): split-fp16 activations only (act 3), no residual inputs, no Temporal_pos;
+// stat[T][2] = (mean, rstd) of the FIRST norm of every row, x is read only
+int d3dp_launch_ln2_defer(int act_bf16, const float* x, const float* wa, const float* ba, const float* wb, const float* bb, float eps,
+                          void* xn, float* stat, int T, int C, hipStream_t st) {
+  if (act_bf16 != 3 || !stat || !width_instantiated(C)) return -2;
+  dim3 g((T + 4 * kDeferRows - 1) / (4 * kDeferRows)), blk(256);
+  const size_t plane = (size_t)T * C;
+  DISPATCH_C(C, hipLaunchKernelGGL((ln2_defer_kernel<CC, h2>), g, blk, 0, st, x, wa, ba, wb, bb, eps, (f16*)xn, (float2*)stat, plane, T))
   return 0;
 }
 
