@@ -198,7 +198,7 @@ struct d3dp_ctx {
   bool x2() const { return exact() && exact_impl == 0; }
   // split-fp16 attention kernels: head dim 64.  Up to 256 frames (every BASELINE configuration) the temporal kernel holds a whole
   // sequence's K / V images in LDS; longer clips (`-f 351`, reference common/arguments.py:58, mixste.py:172) take the flash form of the
-  // same arithmetic (attention.hip attn_temporal_x2_long_kernel: keys in chunks of 128 under an online softmax; round 5 ran both
+  // same arithmetic (attention_x2.hip attn_temporal_x2_long_kernel: keys in chunks of 128 under an online softmax; round 5 ran both
   // attentions of such clips on the chunked fp32 VALU row kernel, ten times the cost per FLOP).  D3DP_LONG_ATTN=rows keeps that
   // kernel as a cross-check (read in d3dp_create); a FAST / FAST16 context then keeps the row kernel too, for more than 256 frames
   // and for more than 32 joints (attention() below).

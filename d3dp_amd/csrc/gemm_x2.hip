@@ -34,7 +34,7 @@
 // tail cost 11-17 us per 256x128 tile against 18-22 us for its 16 k-steps, fitted over the four Linear shapes.)
 //   EPI_BIAS     -> fp32 out (feeds the residual-adding row kernels)
 //   EPI_GELU     -> GELU (rational erf, common.h) re-split into the h2i rows of the fc2 operand
-//   EPI_QKV_PACK -> q fp32, k and v as fp16 planes: the packed rows the split-fp16 attention kernels read (attention.hip)
+//   EPI_QKV_PACK -> q fp32, k and v as fp16 planes: the packed rows the split-fp16 attention kernels read (attention_x2.hip)
 //   EPI_RESID    -> x += A W^T + b in place on the fp32 residual stream (proj, fc2: mixste.py:113-115)
 //   EPI_RESID_NORM -> EPI_RESID behind a DEFERRED LayerNorm of the residual row: x = LN(x) + A W^T + b, the LayerNorm's (mean, rstd)
 //                   per row left by the row kernel in front (pointwise.hip ln2_defer_kernel), its gamma / beta behind the bias: the

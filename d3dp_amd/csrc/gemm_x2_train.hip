@@ -262,7 +262,7 @@ __global__ __launch_bounds__(768) void gemm_f16x2_dyn_kernel(const f16* __restri
 // the A slab 32 rows x 256 features (1 KiB per row = 8 h2i blocks, ONE LDS-DMA wave-instruction), the W slab 32 rows x 128
 // features (512 B per row, two rows per instruction) -- the same 48 KiB per stage, 12 pieces per loader wave and k-step as the
 // dyn kernel above, and the same 8 + 4 waves, 3-stage ring and barrier structure.  The fragments an MFMA wants -- 8 consecutive
-// TOKENS of one feature -- are columns of the slab: ds_read_b64_tr_b16 (the transposed fragment read of attention.hip's V
+// TOKENS of one feature -- are columns of the slab: ds_read_b64_tr_b16 (the transposed fragment read of attn_frag.h's V
 // image: 4 token rows x 16 features per 16 lanes) delivers them; lane group g holds the tokens {4 g + j} and {16 + 4 g + j} of
 // the k-step for BOTH operands, so the k order of the two fragments agrees.  LDS swizzle: 16-byte slot s of token row r sits at
 // s ^ ((r & 7) << 1): the eight rows a transposed read touches per cycle land in eight different 32-byte bank groups (the rows

@@ -382,7 +382,7 @@ constexpr int WLDS = WW_BASE + WW_STAGES * WW_BYTES; // 160 KiB
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"          // (the expected "clobber list contains reserved registers" note for m0)
 // one LDS-DMA wave-instruction in the  uniform base + 32-bit lane offset  form: lane l's 16 bytes at base + off -> LDS
-// bytes [lds + 16 l, +16).  Inline assembly for the reasons given at lds_dma16 in attention.hip: the builtin makes the
+// bytes [lds + 16 l, +16).  Inline assembly for the reasons given at lds_dma16 in attention_x2.hip: the builtin makes the
 // compiler turn every vector-memory wait of the kernel into vmcnt(0).
 __device__ __forceinline__ void wide_dma16(unsigned off, const char* base, unsigned lds) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(lds) : "memory", "m0");

@@ -161,28 +161,31 @@ int d3dp_launch_linear_f32_splitk(const float* A, const float* W, float* out, in
 int d3dp_launch_linear_f32(int epi, const float* A, const float* W, const float* bias, float* out, int M, int N,
                            int K, hipStream_t st);
 
-// ---- attention.hip -----------------------------------------------------------------------------
+// ---- attention: the sequence map every attention launcher takes ------------------------------------
 // qkv: [T, 3C] (q | k | v, each head-major hd-minor), out: [T, C].  A "sequence" s of length n_tok has
 // token index  tok(s, i) = (s / inner) * outer_stride + (s % inner) * inner_stride + i * tok_stride.
 //   spatial : n_tok = J, inner = 1,  outer_stride = J,   inner_stride = 0, tok_stride = 1   (s = bh*F + f)
 //   temporal: n_tok = F, inner = J,  outer_stride = F*J, inner_stride = 1, tok_stride = J   (s = bh*J + n)
 struct SeqMap { int n_tok, inner, outer_stride, inner_stride, tok_stride; };
+// ---- attention_f32.hip: fp32 arithmetic ---------------------------------------------------------
 // (any sequence length; amax: optional absmax slot of an fp32 output, one atomicMax per workgroup)
 int d3dp_launch_attn_rows(int act_bf16, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
                           hipStream_t st, unsigned* amax = nullptr);
+int d3dp_launch_attn_temporal_f32(int act, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
+                                  hipStream_t st);
+// ---- attention_fast.hip: FAST / FAST16 on the 2-byte matrix cores -------------------------------
 // (the MFMA kernels of the FAST modes -- f16: 0 = bf16 rows in and out, 1 = IEEE fp16; d3dp_launch_attn_rows: act 1 / act 4)
 int d3dp_launch_attn_temporal_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
                                    hipStream_t st, int f16 = 0);
-int d3dp_launch_attn_temporal_f32(int act, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
-                                  hipStream_t st);
+int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st,
+                                  int f16 = 0);
+// ---- attention_x2.hip: EXACT on split-fp16 operands ---------------------------------------------
 // split-fp16 attention: `qkv` = PACKED rows of 12 C bytes (q fp32 | k hi | k lo | v hi | v lo), written by the qkv Linear
 // with EPI_QKV_PACK or from fp32 rows by d3dp_launch_qkv_pack_x2
 // `act_scale`: the power of two the k / v planes were written at (q and, for plane output, o use the same)
 int d3dp_launch_attn_x2(int act, int axis, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
                         float act_scale, hipStream_t st);
 void d3dp_launch_qkv_pack_x2(const float* src, void* dst, size_t T, int C, float act_scale, hipStream_t st);
-int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st,
-                                  int f16 = 0);
 
 // ---- pointwise.hip -----------------------------------------------------------------------------
 int d3dp_launch_time_mlp(const int64_t* t, const float* freq, const float* w1, const float* b1, const float* w2,

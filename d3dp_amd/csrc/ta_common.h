@@ -1,6 +1,7 @@
 // Device helpers shared by the split-fp16 attention kernels that keep their K / V (Q / dO) operands as hi / lo IMAGES in LDS under
 // ONE swizzle serving row reads and transposed reads alike: the training step's attention (train_attn.hip) and the long-clip
-// temporal attention of inference (attention.hip, attn_temporal_x2_long_kernel: more than 256 frames).
+// temporal attention of inference (attention_x2.hip, attn_temporal_x2_long_kernel: more than 256 frames).  ta_seq_base, ta_split8
+// and v4bf16_t are the one definition for every attention source (attention_f32.hip, attention_fast.hip, attn_frag.h too).
 // LDS image of a [n][64] matrix: two planes (hi | lo) of 128-byte rows, 16-byte slot s of row r at s ^ (((r >> 1) & 3) << 1) --
 // conflict-free for the transposed fragment reads (ds_read_b64_tr_b16: 4 rows x 32 B per 16 lanes) AND for the row fragment
 // reads (ds_read_b128, whose lane groups pair rows {0-3, 12-15} of one slot with rows {4-11} of the neighbouring one).
@@ -121,7 +122,7 @@ __device__ __forceinline__ void ta_stage_many(const float* const (&src)[NS], con
 // per-lane fragment addresses inside an image (hi plane; the lo plane is PLANE bytes further)
 //   r0 / r1 : ROW fragment -- image row (16 t + lane & 15), channels 8 fg .. + 7 (r0) and 32 + 8 fg .. + 7 (r1); tile t at + t 2048
 //   t[dn]   : TRANSPOSED fragment -- channel dn 16 + (lane & 15), image rows 32 c + 4 fg + {0..3} (first read) and + 16 (second,
-//             2048 bytes further); chunk c at + c 4096.  (attention.hip make_frag_bases, V image)
+//             2048 bytes further); chunk c at + c 4096.  (attn_frag.h make_frag_bases, V image)
 struct TAFrag { const char* r0; const char* r1; const char* t[4]; };
 __device__ __forceinline__ TAFrag ta_frag(const char* img, int lane) {
   TAFrag f;

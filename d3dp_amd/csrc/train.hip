@@ -1019,7 +1019,7 @@ size_t d3dp_train_attn_stats_bytes(int n_seq, int n_tok, int heads) { return (si
 // up to 256 tokens (the temporal axis: 243 frames).  The two kernels above spend 13 ms of the configs[4] step on the VALU;
 // the same five products per (sequence, head) cost the fp32 matrix pipe 37.8 MFLOP = 148 k cycles of one CU.
 //   pass Q : K, V in LDS; one 16-query tile per wave.  S^T = K Q^T and dP^T = V dO^T as MFMA tiles [key][query] (the layout
-//            of attention.hip's forward kernel), two-pass softmax in registers, dS^T = P^T (dP^T - D) / 8 per key tile and
+//            of attention_fast.hip's forward kernel), two-pass softmax in registers, dS^T = P^T (dP^T - D) / 8 per key tile and
 //            dQ^T += K^T dS^T straight from the registers that hold it.  Writes (row max, denominator, D) per query.
 //   pass KV: Q, dO and the statistics in LDS; one 16-key tile per wave with its K / V fragments in registers.  S = Q K^T and
 //            dP = dO V^T as tiles [query][key], P from the stored statistics, dV^T += dO^T P and dK^T += Q^T dS.

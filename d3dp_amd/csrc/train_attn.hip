@@ -19,7 +19,7 @@
 //             dQ^T += K^T dS^T.  Writes D_i = dO_i . O_i beside L_i.
 //   pass KV : Q, dO images and (L, D); per query pair S = Q K^T, dP = dO V^T, dV^T += dO^T P, dK^T += Q^T dS.
 // LDS image of a [n][64] matrix: two planes (hi | lo) of 128-byte rows, 16-byte slot s of row r at s ^ (((r >> 1) & 3) << 1)
-// -- the V image of attention.hip: conflict-free for the transposed fragment reads (ds_read_b64_tr_b16: 4 rows x 32 B per 16
+// -- the V image of attn_frag.h: conflict-free for the transposed fragment reads (ds_read_b64_tr_b16: 4 rows x 32 B per 16
 // lanes) AND for the row fragment reads (ds_read_b128, whose lane groups pair rows {0-3, 12-15} of one slot with rows {4-11}
 // of the neighbouring one) -- so ONE image serves both uses of K (S^T and dQ^T) and of Q / dO in pass KV.
 #include "common.h"

@@ -233,7 +233,7 @@ def test_header_is_plain_c_and_links():
                          ids=["default", "overlapped-softmax", "k-fragment-pipeline", "mixlo+w16-kernel-compiles"])
 def test_kernels_with_untracked_loads_do_not_spill(tmp_path, flags):
     """attn_temporal_x2_kernel prefetches its queries with loads the compiler does not track (inline asm; see
-    attention.hip gload16_untracked): a register spill placed right after such a load would save the register before the
+    attention_x2.hip gload16_untracked): a register spill placed right after such a load would save the register before the
     data has arrived.  The kernel is sized to fit its 256 registers exactly -- hold the build to that, for the default
     form and for the two measured alternatives kept behind build switches."""
     import shutil
@@ -241,7 +241,7 @@ def test_kernels_with_untracked_loads_do_not_spill(tmp_path, flags):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
-    src = os.path.join(os.path.dirname(_lib.LIB_PATH), "..", "csrc", "attention.hip")
+    src = os.path.join(os.path.dirname(_lib.LIB_PATH), "..", "csrc", "attention_x2.hip")
     out = str(tmp_path / "attention.s")
     subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", *flags, "-o", out, src],
                    check=True, capture_output=True, timeout=600)

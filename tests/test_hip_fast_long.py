@@ -1,5 +1,5 @@
 """GPU tests of FAST / FAST16 attention on the matrix cores beyond the whole-sequence kernels' reach: more than 256 frames on the
-chunked-key kernel (attention.hip attn_long2_bf16_kernel: keys through LDS in chunks of 128 under an online softmax), more than
+chunked-key kernel (attention_fast.hip attn_long2_bf16_kernel: keys through LDS in chunks of 128 under an online softmax), more than
 32 joints on the whole-sequence kernel with the spatial SeqMap.  cs = 512, 8 heads (head dim 64) throughout.
 
   1. the operator on the temporal axis, 257 ... 1024 frames, both 2-byte types;

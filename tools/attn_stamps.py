@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Phase timeline of the EXACT temporal attention kernel from a -DD3DP_ATTN_STAMP=1 build (tools/build_variant.sh stamp
-attention.hip "-DD3DP_ATTN_STAMP=1"; run with D3DP_LIB=.../libd3dp_stamp.so): cycles between the kernel's barriers."""
+attention_x2.hip "-DD3DP_ATTN_STAMP=1"; run with D3DP_LIB=.../libd3dp_stamp.so): cycles between the kernel's barriers."""
 import ctypes
 import os
 import sys
