@@ -387,10 +387,12 @@ int attention(d3dp_ctx* c, int axis, const void* qkv, void* out, int n_bh, float
                                axis == 0 ? spatial_map(g.frames, g.joints, c->seq_pitch())
                                          : temporal_map(g.frames, g.joints, c->seq_pitch()),
                                g.channels, g.heads, s_kv, st);
-  // FAST / FAST16 at head dim 64: every shape on the 2-byte matrix cores -- more than 32 joints on the whole-sequence kernel
-  // of the temporal axis (it takes any SeqMap), more than 256 frames on its chunked-key form.  D3DP_LONG_ATTN=rows keeps
-  // the fp32 VALU row kernel for those two cases, as a cross-check.
-  const bool fast_mfma = c->fast() && g.channels / g.heads == 64;
+  // FAST / FAST16 at head dims 64, 32 and 16: every shape on the 2-byte matrix cores -- more than 32 joints on the whole-sequence
+  // kernel of the temporal axis (it takes any SeqMap), more than 256 frames on its chunked-key form.  D3DP_LONG_ATTN=rows keeps
+  // the fp32 VALU row kernel, as a cross-check: at head dim 64 for those two cases, at head dims 32 and 16 for every shape (what
+  // such a context launched before its head dim had matrix-core kernels).  Head dim 8 is on the row kernel either way.
+  const int hd = g.channels / g.heads;
+  const bool fast_mfma = c->fast() && (hd == 64 || ((hd == 32 || hd == 16) && !c->long_rows));
   if (axis == 0) {
     if (fast_mfma && g.joints <= 32)
       return d3dp_launch_attn_spatial_bf16(qkv, out, n_bh * g.frames, spatial_map(g.frames, g.joints), g.channels,
@@ -561,8 +563,8 @@ const char* d3dp_profile_class_name(int32_t cls) {
 int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   if (!cfg || !out) return fail(D3DP_EINVAL, "d3dp_create: null argument");
   const d3dp_cfg& g = *cfg;
-  // (frames > 256: every mode takes the chunked-key form of its attention kernels; FAST / FAST16 contexts at a head dim other
-  //  than 64 stay on the row kernel -- fp32 arithmetic on their 2-byte rows)
+  // (frames > 256: every mode takes the chunked-key form of its attention kernels; FAST / FAST16 contexts at head dim 8 stay on
+  //  the row kernel -- fp32 arithmetic on their 2-byte rows)
   if (g.frames < 1 || g.frames > 1024) return fail(D3DP_ENOTSUP, "frames=%d not in [1,1024]", g.frames);
   // (more than 32 joints: the spatial axis takes the whole-sequence attention kernels the temporal axis runs on, round 6)
   if (g.joints < 1 || g.joints > 256) return fail(D3DP_ENOTSUP, "joints=%d not in [1,256]", g.joints);
@@ -1198,6 +1200,9 @@ int d3dp_op_attention(int32_t act_bf16, int32_t impl, int32_t axis, const void* 
                                        axis == 0 ? spatial_map(F, J) : temporal_map(F, J), C, heads, kActScale, st);
     HIP_TRY(hipFreeAsync(packed, st));
     LAUNCH_TRY(rc);
+  } else if (impl == 1 && act_bf16 && (heads < 1 || C % heads || (C / heads != 64 && C / heads != 32 && C / heads != 16))) {
+    return fail(D3DP_ENOTSUP, "impl 1 on 2-byte rows takes head dims 64, 32 and 16; C=%d heads=%d is head dim %d (the row kernel, "
+                              "impl 0, takes it)", C, heads, heads > 0 ? C / heads : 0);
   } else if (axis == 0 && impl == 1) {
     if (!act_bf16) return fail(D3DP_EINVAL, "MFMA spatial attention needs bf16 activations");
     if (J <= 32) LAUNCH_TRY(d3dp_launch_attn_spatial_bf16(qkv, out, n_bh * F, spatial_map(F, J), C, heads, st, f16));

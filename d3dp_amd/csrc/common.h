@@ -21,17 +21,23 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // The 2-byte operand type of the FAST kernels is a template parameter E (bf16: D3DP_MODE_FAST, 8 significand bits and fp32's
 // exponent range; f16: D3DP_MODE_FAST16, 11 bits, |x| < 65504).  Op2<E>: its vectors and its matrix instruction
 // (v_mfma_f32_16x16x32_bf16 / v_mfma_f32_16x16x32_f16: the same shape, lane layout and cycles).  Every fp32 -> E conversion in
-// those kernels is a plain cast (round to nearest even) for both types.
+// those kernels is a plain cast (round to nearest even) for both types.  The x4 overload is the 16-deep instruction of the same
+// family (v_mfma_f32_16x16x16_bf16 / _f16: lane (i, g) holds k = 4 g .. 4 g + 3; same output layout), for a k-depth of 16.
 template <typename E> struct Op2;
 template <> struct Op2<bf16> {
   typedef bf16x4 x4;
   typedef bf16x8 x8;
   static __device__ __forceinline__ f32x4 mfma(x8 a, x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ f32x4 mfma(x4 a, x4 b, f32x4 c) {
+    typedef short s16x4 __attribute__((ext_vector_type(4)));
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
+  }
 };
 template <> struct Op2<f16> {
   typedef f16x4 x4;
   typedef f16x8 x8;
   static __device__ __forceinline__ f32x4 mfma(x8 a, x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ f32x4 mfma(x4 a, x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
 };
 // (the split-bf16 EXACT cross-check kernels: always bf16)
 #define D3DP_MFMA_16x16x32_BF16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)

@@ -140,13 +140,14 @@ D3DP_API const char* d3dp_last_error(void);
  * Shapes (D3DP_ENOTSUP outside them, with the reason in d3dp_last_error):
  *   1 <= frames <= 1024   up to 256 frames the MFMA attention kernels hold a whole sequence; longer clips (`-f 351`,
  *                         common/arguments.py:58) take chunked-key forms of the same kernels in every mode (FAST, FAST16:
- *                         keys through LDS in chunks of 128, probabilities rounded to 2 bytes as below 256 frames;
- *                         head dims 8 / 16 / 32 stay on the row kernel, fp32 arithmetic on the 2-byte rows);
+ *                         keys through LDS in chunks of 128, probabilities rounded to 2 bytes as below 256 frames, at
+ *                         head dims 64, 32 and 16; head dim 8 stays on the row kernel, fp32 arithmetic on the 2-byte
+ *                         rows, on both axes and at every clip length);
  *   1 <= joints <= 256    MixSTE2's num_joints (mixste.py:141; D3DP builds 17): above 32 the spatial axis runs on the
  *                         whole-sequence attention kernels of the temporal axis, in every mode;
  *                         (D3DP_LONG_ATTN=rows in the environment of d3dp_create: the row kernel instead, for more than
- *                         256 frames in EXACT, FAST and FAST16 contexts and for more than 32 joints in FAST / FAST16 ones
- *                         -- the cross-check)
+ *                         256 frames in EXACT, FAST and FAST16 contexts, for more than 32 joints in FAST / FAST16 ones,
+ *                         and for every attention of a FAST / FAST16 context at head dim 32 or 16 -- the cross-check)
  *   channels in {64, 128, 256, 512} with head dim in {8, 16, 32, 64} and hidden % 64 == 0: every mode, on the matrix-core
  *                         kernels (split-fp16 / bf16 operands) -- `-cs 512`, the width of every published checkpoint
  *                         (README.md:33-39), and its smaller powers of two;
@@ -345,9 +346,10 @@ D3DP_API int d3dp_op_linear(int32_t mode, int32_t epi, const void* A, const void
                    int32_t N, int32_t K, void* stream);
 /* Multi-head attention over qkv[T,3C] -> out[T,C]; axis 0 = spatial (sequences of J joints), 1 = temporal
  * (sequences of F frames); tokens ordered (seq_batch, f, n).  impl 0 = fp32-VALU row kernel (any activation type),
- * 1 = matrix-core kernel (head dim 64): bf16 / fp16 MFMA for 2-byte activations (both axes: F <= 1024 frames on the
- * temporal axis, the chunked-key kernel beyond 256; J <= 256 joints on the spatial axis), fp32 MFMA for fp32 activations
- * (temporal axis, F <= 256), 2 = the EXACT-mode kernels: split-fp16 operands on the fp16 matrix cores (both axes; head dim 64).  Inside
+ * 1 = matrix-core kernel: bf16 / fp16 MFMA for 2-byte activations (head dim 64, 32 or 16 -- any other, 8 included, is
+ * D3DP_ENOTSUP; both axes: F <= 1024 frames on the temporal axis, the chunked-key kernel beyond 256; J <= 256 joints on the
+ * spatial axis), fp32 MFMA for fp32 activations (head dim 64, temporal axis, F <= 256), 2 = the EXACT-mode kernels:
+ * split-fp16 operands on the fp16 matrix cores (both axes; head dim 64).  Inside
  * the denoiser those read the packed rows of its qkv Linear (d3dp_op_linear_x2, epi 4); this entry point takes plain fp32
  * rows and repacks them into a stream-ordered temporary (hipMallocAsync) first.
  * act_bf16: 0 fp32 rows, 1 bf16 rows, 4 IEEE fp16 rows (impl 0 and 1: the kernels of a FAST16 context).

@@ -1,19 +1,22 @@
 #!/usr/bin/env python3
 """Interleaved same-process comparison of numerics modes on BASELINE configs[2] (ddim_sample_flip, F=243, J=17, B=16, H=20, K=10).
 
-    python tools/mode_bench.py --numerics fast,fast16 [--steps 20] [--warmup 5] [--rounds 4] [--frames 243]
+    python tools/mode_bench.py --numerics fast,fast16 [--steps 20] [--warmup 5] [--rounds 4] [--frames 243] [--cs 512]
 
-`--frames N` runs the same sampler on clips of N frames (1 ... 1024).  A `:rows` suffix on a mode name (`fast:rows`, `exact:rows`)
+`--frames N` runs the same sampler on clips of N frames (1 ... 1024), `--cs C` at a width of C channels (8 heads; 512, 256, 128
+or 64).  A `:rows` suffix on a mode name (`fast:rows`, `exact:rows`)
 creates that model's library context with D3DP_LONG_ATTN=rows in the environment: the row attention kernel wherever the mode would
-take a chunked-key or, in the FAST modes, a whole-sequence matrix-core kernel beyond 256 frames / 32 joints -- the A/B of those
-kernels in one process.  The variable is read when a context is created, so every context is created before anything is timed.
+take a chunked-key or, in the FAST modes, a whole-sequence matrix-core kernel beyond 256 frames / 32 joints, and at head dims 32
+and 16 (`--cs 256`, `--cs 128`) for every attention of a FAST mode -- the A/B of those kernels in one process:
+`--cs 256 --numerics fast:rows,fast,fast16:rows,fast16`.  The variable is read when a context is created, so every context is created before anything is timed.
 
 Every mode gets its own model (and library context) on the same weights, inputs and generator seed.  After `--warmup` steps of each,
 the timed steps are taken in `--rounds` rounds that visit the modes in turn (a b a b ...), steps / rounds steps per visit, a host
 clock around a device synchronise per visit: drift of the box (clock, temperature, neighbours) lands on every mode alike, which two
 back-to-back bench.py runs cannot offer.  Clock and power are sampled the way bench.py samples them (its GpuTelemetry), per mode,
 over that mode's timed visits only.  Prints ONE JSON line: per mode hypothesis-clips/s, ms per step, the per-visit spread, mean
-clock / power; the ratio of every mode to the first; the operand type and proven bound of the FAST modes; the library's sha256.
+clock / power; the ratio of every mode to the first; the operand type and proven bound of the FAST modes; the library's sha256;
+and, from one more untimed step per mode under d3dp_profile_read, launches and kernel ms of the two attention classes.
 """
 import argparse
 import json
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--hyps", type=int, default=20)
     ap.add_argument("--ksteps", type=int, default=10)
     ap.add_argument("--frames", type=int, default=None, help="clip length (default: bench.py's, 243)")
+    ap.add_argument("--cs", type=int, default=None, help="channels, 8 heads (default: bench.py's, 512)")
     a = ap.parse_args()
     modes = [m.strip() for m in a.numerics.split(",") if m.strip()]
     if not modes or a.steps < a.rounds or a.rounds < 1 or a.warmup < 0:
@@ -48,7 +52,8 @@ def main():
         ap.error("--frames must be in [1, 1024]; the only mode suffix is ':rows'")
     x2d_np = synthetic_inputs_2d(1234, B, frames)
     x2d, x2f = torch.from_numpy(x2d_np).cuda(), torch.from_numpy(flip_2d(x2d_np)).cuda()
-    models = {m: bench.build_model(H, K, m.split(":")[0], 0, frames=frames) for m in modes}
+    cs = bench.C_ if a.cs is None else a.cs
+    models = {m: bench.build_model(H, K, m.split(":")[0], 0, frames=frames, cs=cs) for m in modes}
     saved = os.environ.get("D3DP_LONG_ATTN")
     for m in modes:                                    # the contexts, now: a `:rows` one with the switch set for its creation
         if m.endswith(":rows"):
@@ -79,16 +84,19 @@ def main():
             visits[m].append((time.perf_counter() - t0) / n)
             teles[m].stop()
             assert bool(torch.isfinite(out).all())
-    res = {"workload": f"{'BASELINE configs[2]: ' if frames == bench.F_ else ''}ddim_sample_flip F={frames} J=17 B={B} H={H} K={K} flip-TTA, cs=512 dep=8",
+    res = {"workload": f"{'BASELINE configs[2]: ' if (frames, cs) == (bench.F_, bench.C_) else ''}ddim_sample_flip F={frames} J=17 B={B} H={H} K={K} flip-TTA, cs={cs} dep=8",
            "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "order": modes, "library_sha256": bench.lib_sha256(), "modes": {}}
     for m in modes:
         dt = sum(v * n for v, n in zip(visits[m], per_visit))
         tr = teles[m].report()
         fo = models[m].pose_estimator.fast_operands()
+        prof = bench.profile_step(models[m], x2d, x2f, gens[m])       # (one more step, after everything timed)
         res["modes"][m] = {"value": B * H * a.steps / dt, "unit": "hypothesis-clips/s", "ms_per_step": dt / a.steps * 1e3,
                            "ms_per_step_by_visit": [round(v * 1e3, 2) for v in visits[m]],
                            "clock_mhz_mean": tr["clock_mhz_mean"], "power_w_mean": tr["power_w_mean"], "power_cap_w": tr["power_cap_w"],
-                           "fast_operands": None if fo is None else {"type": fo[0], "proven_bound": fo[1]}}
+                           "fast_operands": None if fo is None else {"type": fo[0], "proven_bound": fo[1]},
+                           "attention_classes_one_step": {k: {"launches": c, "kernel_ms": round(ms, 3)} for k, (c, ms) in prof.items()
+                                                          if k.startswith("attn")}}
     base = res["modes"][modes[0]]["value"]
     res["ratio_to_first"] = {m: res["modes"][m]["value"] / base for m in modes}
     print(json.dumps(res))
