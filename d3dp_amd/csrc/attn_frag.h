@@ -1,20 +1,20 @@
 // LDS images and MFMA fragment addresses shared by the two-pass matrix-core attention kernels: the FAST / FAST16 kernels
 // (attention_fast.hip, one 2-byte plane per operand; head dims 64, 32 and 16) and the EXACT split-fp16 kernels (attention_x2.hip,
-// head dim 64, a hi and a lo plane of the same layout `plane` bytes apart).  No transposes anywhere; at head dim 64:
+// the same head dims, a hi and a lo plane of the same layout `plane` bytes apart).  No transposes anywhere; at head dim 64:
 //   K rows sit in LDS row-major (128 B per key) with the 16-byte-slot XOR swizzle ds_read_b128 wants;
 //   V rows sit row-major too, swizzled at 32-byte-chunk granularity, and are consumed with
 //   ds_read_b64_tr_b16: within each 16-lane group the instruction returns, to lane i, column i of the
 //   4-key x 16-column block the group's lanes point at (lanes 4j..4j+3 -> key j) -- exactly the
 //   "8 consecutive keys of one output channel" fragment the O^T = V^T P^T MFMA needs.  (Mapping measured on
 //   gfx950 with tools/probe_tr.hip.)
-// (The chunked-key split-fp16 kernel and the training attention use the one-swizzle images of ta_common.h instead.)
+// (The chunked-key split-fp16 kernel at head dim 64 and the training attention use the one-swizzle images of ta_common.h instead.)
 #pragma once
 #include "common.h"
 #include "ta_common.h"
 
 namespace {
 
-// Head dims 32 and 16 (FAST / FAST16 only; HD is a template parameter that defaults to 64, and the HD = 64 forms below are the
+// Head dims 32 and 16 (HD is a template parameter that defaults to 64, and the HD = 64 forms below are the
 // expressions the images were first written with).  A K or V row is 2 HD bytes = HD / 8 16-byte slots, so the 256-byte bank
 // row that ds_read_b128, ds_read_b64 and ds_read_b64_tr_b16 all bank on ((addr / 4) mod 64) holds 2 / 4 / 8 rows.  The
 // swizzles are XORs on the 16-byte slot index of a row, as functions of the row:

@@ -196,14 +196,22 @@ struct d3dp_ctx {
   bool train() const { return cfg.mode == D3DP_MODE_TRAIN; }
   bool exact() const { return !fast() && !train(); }
   bool x2() const { return exact() && exact_impl == 0; }
-  // split-fp16 attention kernels: head dim 64.  Up to 256 frames (every BASELINE configuration) the temporal kernel holds a whole
+  // split-fp16 attention kernels: head dims 64, 32 and 16 (`-cs` 512 / 256 / 128 with the model's 8 heads; head dim 8 and every other
+  // one stay on the fp32 kernels of attention()).  Up to 256 frames (every BASELINE configuration) the temporal kernel holds a whole
   // sequence's K / V images in LDS; longer clips (`-f 351`, reference common/arguments.py:58, mixste.py:172) take the flash form of the
   // same arithmetic (attention_x2.hip attn_temporal_x2_long_kernel: keys in chunks of 128 under an online softmax; round 5 ran both
   // attentions of such clips on the chunked fp32 VALU row kernel, ten times the cost per FLOP).  D3DP_LONG_ATTN=rows keeps that
   // kernel as a cross-check (read in d3dp_create); a FAST / FAST16 context then keeps the row kernel too, for more than 256 frames
-  // and for more than 32 joints (attention() below).
+  // and for more than 32 joints (attention() below).  At head dims 32 and 16 the switch keeps the fp32 row kernel for EVERY shape,
+  // in this mode as in the FAST modes: what such a context launched before these head dims had matrix-core kernels, i.e. the A/B
+  // handle and the cross-check.  Everything that follows from the packed qkv rows follows x2_attn(): EPI_QKV_PACK in linear(), the
+  // scale of the attention output planes in run_block, seq_pitch(), and the range fallback of d3dp_set_weights, which lowers s_kv
+  // instead of leaving the split-fp16 implementation wherever these kernels run.
   bool long_rows = false;
-  bool x2_attn() const { return x2() && cfg.channels / cfg.heads == 64 && (cfg.frames <= 256 || !long_rows); }
+  bool x2_attn() const {
+    const int hd = cfg.channels / cfg.heads;
+    return x2() && ((hd == 64 && (cfg.frames <= 256 || !long_rows)) || ((hd == 32 || hd == 16) && !long_rows));
+  }
   // proj / fc2 add into the residual stream in their epilogue (x += ...), so the row kernels read x alone
   bool fold_resid() const { return x2() && fold; }
   bool fold = true;
@@ -382,7 +390,7 @@ SeqMap temporal_map(int F, int J, int sp = 0) { return SeqMap{F, J, sp > F * J ?
 int attention(d3dp_ctx* c, int axis, const void* qkv, void* out, int n_bh, float s_kv, hipStream_t st) {
   const d3dp_cfg& g = c->cfg;
   Scope s(c, axis == 0 ? P_ATTN_S : P_ATTN_T, st);
-  if (c->x2_attn())                                    // split-fp16 operands on the fp16 matrix cores; packed qkv rows
+  if (c->x2_attn())                                    // split-fp16 operands on the fp16 matrix cores (head dims 64, 32, 16); packed qkv rows
     return d3dp_launch_attn_x2(3, axis, qkv, out, axis == 0 ? n_bh * g.frames : n_bh * g.joints,
                                axis == 0 ? spatial_map(g.frames, g.joints, c->seq_pitch())
                                          : temporal_map(g.frames, g.joints, c->seq_pitch()),
@@ -563,8 +571,8 @@ const char* d3dp_profile_class_name(int32_t cls) {
 int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   if (!cfg || !out) return fail(D3DP_EINVAL, "d3dp_create: null argument");
   const d3dp_cfg& g = *cfg;
-  // (frames > 256: every mode takes the chunked-key form of its attention kernels; FAST / FAST16 contexts at head dim 8 stay on
-  //  the row kernel -- fp32 arithmetic on their 2-byte rows)
+  // (frames > 256: every mode takes the chunked-key form of its attention kernels; at head dim 8 FAST / FAST16 contexts stay on
+  //  the row kernel -- fp32 arithmetic on their 2-byte rows -- and EXACT contexts on the fp32 kernels, at every clip length)
   if (g.frames < 1 || g.frames > 1024) return fail(D3DP_ENOTSUP, "frames=%d not in [1,1024]", g.frames);
   // (more than 32 joints: the spatial axis takes the whole-sequence attention kernels the temporal axis runs on, round 6)
   if (g.joints < 1 || g.joints > 256) return fail(D3DP_ENOTSUP, "joints=%d not in [1,256]", g.joints);
@@ -716,7 +724,7 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
       }
       worst = std::max(worst, std::max(std::max(bq, bh), std::max(bl1, bl2)));
       if (!(bl1 < kSafe) || !(bl2 < kSafe)) fallback = true;
-      if (!(bq < kSafe) && !c->x2_attn()) fallback = true;
+      if (!(bq < kSafe) && !c->x2_attn()) fallback = true;   // (x2_attn(): head dims 64, 32 and 16 lower s_kv instead)
       blk_scale[2 * i] = pick(bq);
       blk_scale[2 * i + 1] = pick(bh);
     }
@@ -1191,6 +1199,10 @@ int d3dp_op_attention(int32_t act_bf16, int32_t impl, int32_t axis, const void* 
   const int f16 = act_bf16 == 4;
   if (impl == 2) {       // EXACT mode: split-fp16 operands on the fp16 matrix cores, fp32 in / fp32 out
     if (act_bf16) return fail(D3DP_EINVAL, "split-fp16 attention takes fp32 activations");
+    // (refused here, before the temporary exists and the repack kernel runs)
+    if (heads < 1 || C % heads || (C / heads != 64 && C / heads != 32 && C / heads != 16))
+      return fail(D3DP_ENOTSUP, "impl 2 (split-fp16 attention) takes head dims 64, 32 and 16; C=%d heads=%d is head dim %d (the row "
+                                "kernel, impl 0, takes it)", C, heads, heads > 0 ? C / heads : 0);
     // the kernels read the packed rows the EXACT qkv Linear writes: repack the fp32 rows into a stream-ordered temporary
     void* packed = nullptr;
     const size_t T = (size_t)n_bh * F * J;

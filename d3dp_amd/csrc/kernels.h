@@ -179,10 +179,11 @@ int d3dp_launch_attn_temporal_bf16(const void* qkv, void* out, int n_seq, SeqMap
                                    hipStream_t st, int f16 = 0);
 int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st,
                                   int f16 = 0);
-// ---- attention_x2.hip: EXACT on split-fp16 operands ---------------------------------------------
+// ---- attention_x2.hip: EXACT on split-fp16 operands (head dim 64, 32 or 16; -2 for any other) ----
 // split-fp16 attention: `qkv` = PACKED rows of 12 C bytes (q fp32 | k hi | k lo | v hi | v lo), written by the qkv Linear
 // with EPI_QKV_PACK or from fp32 rows by d3dp_launch_qkv_pack_x2
 // `act_scale`: the power of two the k / v planes were written at (q and, for plane output, o use the same)
+// act 0: fp32 rows out, 3: the two fp16 planes of the proj Linear's operand.  Any SeqMap, up to 1024 tokens per sequence.
 int d3dp_launch_attn_x2(int act, int axis, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
                         float act_scale, hipStream_t st);
 void d3dp_launch_qkv_pack_x2(const float* src, void* dst, size_t T, int C, float act_scale, hipStream_t st);

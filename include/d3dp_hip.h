@@ -147,7 +147,7 @@ D3DP_API const char* d3dp_last_error(void);
  *                         whole-sequence attention kernels of the temporal axis, in every mode;
  *                         (D3DP_LONG_ATTN=rows in the environment of d3dp_create: the row kernel instead, for more than
  *                         256 frames in EXACT, FAST and FAST16 contexts, for more than 32 joints in FAST / FAST16 ones,
- *                         and for every attention of a FAST / FAST16 context at head dim 32 or 16 -- the cross-check)
+ *                         and for every attention of an EXACT, FAST or FAST16 context at head dim 32 or 16 -- the cross-check)
  *   channels in {64, 128, 256, 512} with head dim in {8, 16, 32, 64} and hidden % 64 == 0: every mode, on the matrix-core
  *                         kernels (split-fp16 / bf16 operands) -- `-cs 512`, the width of every published checkpoint
  *                         (README.md:33-39), and its smaller powers of two;
@@ -349,7 +349,8 @@ D3DP_API int d3dp_op_linear(int32_t mode, int32_t epi, const void* A, const void
  * 1 = matrix-core kernel: bf16 / fp16 MFMA for 2-byte activations (head dim 64, 32 or 16 -- any other, 8 included, is
  * D3DP_ENOTSUP; both axes: F <= 1024 frames on the temporal axis, the chunked-key kernel beyond 256; J <= 256 joints on the
  * spatial axis), fp32 MFMA for fp32 activations (head dim 64, temporal axis, F <= 256), 2 = the EXACT-mode kernels:
- * split-fp16 operands on the fp16 matrix cores (both axes; head dim 64).  Inside
+ * split-fp16 operands on the fp16 matrix cores (both axes; head dim 64, 32 or 16 -- any other, 8 included, is D3DP_ENOTSUP
+ * and nothing is launched).  Inside
  * the denoiser those read the packed rows of its qkv Linear (d3dp_op_linear_x2, epi 4); this entry point takes plain fp32
  * rows and repacks them into a stream-ordered temporary (hipMallocAsync) first.
  * act_bf16: 0 fp32 rows, 1 bf16 rows, 4 IEEE fp16 rows (impl 0 and 1: the kernels of a FAST16 context).
