@@ -5,7 +5,7 @@
 //
 //   attn_rows_kernel         : fp32 VALU, one thread per query row, K / V of the problem broadcast from LDS in chunks of <= 256
 //                              keys under an online softmax.  Rows in: fp32, bf16 or fp16; out: the same type, or (fp32 in) three
-//                              split-bf16 / two split-fp16 planes.  What attention() in capi.hip sends here is whatever no
+//                              split-bf16 / two split-fp16 planes.  What attention() in capi_denoise.hip sends here is whatever no
 //                              matrix-core kernel takes: every context whose head dim is not 64 (widths outside {64 .. 512} on
 //                              the run-time head dim form); the spatial axis of D3DP_EXACT_IMPL=f32|bf16x3; a D3DP_LONG_ATTN=rows
 //                              context beyond 256 frames (and, FAST / FAST16, beyond 32 joints).  The training step calls it for

@@ -14,7 +14,7 @@
 //                                registers: a plain two-pass softmax, no online rescaling.
 //   attn_long2_bf16_kernel     : 257 .. 1024 tokens, the keys in chunks of 16 D3DP_FAST_LONG_NKT under an online softmax.
 //
-// attention() in capi.hip sends a FAST / FAST16 context here when its head dim is 64, 32 or 16: the spatial axis up to 32 joints
+// attention() in capi_denoise.hip sends a FAST / FAST16 context here when its head dim is 64, 32 or 16: the spatial axis up to 32 joints
 // to the spatial kernel, with more joints to the temporal launcher (it takes any SeqMap), the temporal axis to the temporal
 // launcher -- except where D3DP_LONG_ATTN=rows keeps the fp32 row kernel (attention_f32.hip): beyond 32 joints / 256 frames at
 // head dim 64, for every shape at head dims 32 and 16.  Head dim 8 (a quarter of the narrowest k-depth) stays on the row kernel.

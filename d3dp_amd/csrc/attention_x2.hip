@@ -22,7 +22,7 @@
 //                                  softmax, on the images and helpers of ta_common.h.
 //   qkv_pack_x2_kernel           : fp32 qkv rows -> packed rows, for d3dp_op_attention, whose C-ABI input is the fp32 layout.
 //
-// attention() in capi.hip sends both axes of an EXACT context here (act 3) when it runs the split-fp16 implementation -- the
+// attention() in capi_denoise.hip sends both axes of an EXACT context here (act 3) when it runs the split-fp16 implementation -- the
 // default; D3DP_EXACT_IMPL=f32|bf16x3 does not -- at head dims 64, 32 and 16, unless D3DP_LONG_ATTN=rows keeps the fp32 row kernel
 // (attention_f32.hip): for a clip of more than 256 frames at head dim 64, for every shape at head dims 32 and 16;
 // d3dp_op_attention with impl 2 (act 0).  d3dp_launch_attn_x2 refuses (-2) any other
@@ -67,7 +67,7 @@ __device__ __forceinline__ f16x8 as_f16x8(bf16x8 v) { return __builtin_bit_cast(
 // Operand scales of the split-fp16 attention kernels (kernel argument; wave-uniform).  q is split in registers at `q`; the
 // k / v planes of the packed rows were written at that same scale by the qkv Linear; `cexp` = hd^-0.5 log2(e) / (q scale x
 // k scale) folds both into the softmax exponent; `onorm` = 1 / v scale brings O^T back to its true scale; `oplane` = the scale
-// at which a plane output is split (that of v: |o| <= max |v|).  Everything is 2^4-based unless capi.hip lowered the scale of
+// at which a plane output is split (that of v: |o| <= max |v|).  Everything is 2^4-based unless capi_weights.hip lowered the scale of
 // a block whose proven operand range asks for it (d3dp_exact_range_bound).
 // The true-scale value is formed FIRST and the (power-of-two, hence exact) plane scale applied inside the split on purpose:
 // with  x = o * (1 / denom)  handed to the split directly, hipcc (ROCm 7.2) folds the fp16 conversion of the INEXACT product
@@ -1187,7 +1187,7 @@ void d3dp_launch_qkv_pack_x2(const float* src, void* dst, size_t T, int C, float
 }
 
 // act_scale: the power of two q, k, v (and, for act == 3, the output planes) are scaled by -- kActScale unless the block's
-// proven operand range asked for less (capi.hip).  With 16 the arithmetic is bit for bit that of the constant-scale kernels.
+// proven operand range asked for less (capi_weights.hip).  With 16 the arithmetic is bit for bit that of the constant-scale kernels.
 int d3dp_launch_attn_x2(int act, int axis, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
                         float act_scale, hipStream_t st) {
   if (heads < 1 || C % heads || map.n_tok < 1 || (act != 0 && act != 3) || !(act_scale > 0.f)) return -2;

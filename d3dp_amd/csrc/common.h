@@ -223,7 +223,7 @@ struct b3 {};   // tag: activation stored as three bf16 planes [3][T][C]
 // The power-of-two pre-scale 2^s keeps lo a NORMAL fp16 number for every value that matters: activations use the fixed
 // s = 4 (full 22 bits for 2^-7 <= |x| < 4094; smaller values keep an ABSOLUTE error <= 2^-29, far below 2^-22 of the
 // O(1) values they are summed with; LayerNorm outputs, GELU hidden activations and attention outputs stay orders of
-// magnitude below 4094), weight matrices get s from their largest element (capi.hip).  fp16 subnormal inputs are NOT
+// magnitude below 4094), weight matrices get s from their largest element (capi_weights.hip).  fp16 subnormal inputs are NOT
 // flushed by the fp16 matrix cores (tools/probe_f16_denorm.py, tests/test_hip_parity.py), which the tail of the range
 // relies on.
 constexpr float kActScale = 16.0f, kActUnscale = 1.0f / 16.0f;

@@ -319,7 +319,7 @@ __global__ __launch_bounds__(768) void gemm_f16x2_kernel(const f16* __restrict__
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
                 f16 h, l;
-                split2h_scaled(v[e] * oscale, h, l);       // (oscale: the consumer's operand scale, 2^4 unless capi.hip lowered it)
+                split2h_scaled(v[e] * oscale, h, l);       // (oscale: the consumer's operand scale, 2^4 unless capi_weights.hip lowered it)
                 ph[e] = h; pl[e] = l;
               }
               store_planes_paired(dst, ph, pl, odd, live);
@@ -521,7 +521,7 @@ __global__ void nonfinite_flag_kernel(const float* __restrict__ x, size_t n, uns
 bool d3dp_x2_variants_built() { return D3DP_X2_VARIANTS != 0; }
 
 // The experimental kernels with their dispatcher x2_variants_launch, d3dp_x2_skew_applies and the two norm2-folding launchers;
-// the product library answers for them: the schedule never applies, and capi.hip never reaches the launchers without a
+// the product library answers for them: the schedule never applies, and capi_denoise.hip never reaches the launchers without a
 // variants build.
 #if D3DP_X2_VARIANTS
 #include "gemm_x2_variants.h"

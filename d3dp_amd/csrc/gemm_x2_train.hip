@@ -412,7 +412,7 @@ __global__ __launch_bounds__(768) void gemm_f16x2_tn_kernel(D3dpTnTable tb, int 
 }
 
 // scale of a split operand from its absmax (bit pattern of a non-negative float, absmax_kernel): the power of two that
-// puts the largest magnitude in [2^13, 2^14) (as capi.hip does for the inference weights); 1 for an all-zero tensor
+// puts the largest magnitude in [2^13, 2^14) (as capi_weights.hip does for the inference weights); 1 for an all-zero tensor
 __device__ __forceinline__ float dyn_scale(unsigned amax_bits) {
   const float m = __uint_as_float(amax_bits);
   if (!(m > 0.f) || !(m < INFINITY)) return 1.0f;

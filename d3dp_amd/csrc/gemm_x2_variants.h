@@ -82,7 +82,7 @@ __device__ __forceinline__ void x2_epilogue_at(f32x4 (&acc)[4][4], const int pm0
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               f16 h, l;
-              split2h_scaled(v[e] * oscale, h, l);       // (oscale: the consumer's operand scale, 2^4 unless capi.hip lowered it)
+              split2h_scaled(v[e] * oscale, h, l);       // (oscale: the consumer's operand scale, 2^4 unless capi_weights.hip lowered it)
               ph[e] = h; pl[e] = l;
             }
             store_planes_paired(dst, ph, pl, odd, live);
@@ -581,7 +581,7 @@ __global__ __launch_bounds__(512) void gemm_f16x2_wide_kernel(const f16* __restr
 //   loaders    A piece i of loader wave lw lands in LDS rows lw 64 + 8 i .. + 7 (row slot i >> 1) as before; it FETCHES the
 //              rows of class ((i >> 1) + rot) & 3, from tile ti or ti - 1 as that class stands; pointers re-derived at the
 //              four park steps of a round.  W pieces: one strip for the whole launch.  Ring, barriers, vmcnt: unchanged.
-//   numerics   the rotation changes the ORDER of a row's fp32 partial sums with its row class: capi.hip pads every sequence
+//   numerics   the rotation changes the ORDER of a row's fp32 partial sums with its row class: ctx.h seq_pitch() pads every sequence
 //              to a multiple of 64 rows (d3dp_ctx::seq_pitch), which makes the class a function of the token's index in its
 //              sequence -- results stay bit-identical across batch compositions, pass splits and ranks.
 // Built for the two Linears whose epilogue is pure register work: EPI_BIAS / TAG 1 (qkv, packed rows) and EPI_GELU (fc1).

@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI layer (capi.hip) and the kernel translation units.
+// Internal launcher interface between the C-ABI layer (capi*.hip over ctx.h) and the kernel translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,7 +58,7 @@ void d3dp_launch_split3(const float* src, void* dst, size_t n, hipStream_t st);
 //   the Linear's value is added.  3 N <= 2048, K >= 96.
 // `unscale` = 1 / (scale of the A operand x scale of the W operand); `oscale` = the power of two the plane outputs (EPI_GELU*,
 // k / v of EPI_QKV_PACK, the operand copy of EPI_RESID_LN) are multiplied by before the hi / lo split (kActScale unless the
-// proven range of that operand asks for less, capi.hip)
+// proven range of that operand asks for less, capi_weights.hip)
 int d3dp_launch_linear_f16x2(int epi, const void* A2, const void* W2, const float* bias, float unscale, float oscale,
                              float* outf, void* out2, float* aux, unsigned* flag, int M, int N, int K, hipStream_t st,
                              int skew_d = 0, int pingpong = 0);
@@ -231,6 +231,10 @@ int d3dp_launch_jpma(const float* pred, const float* traj, const float* cam, con
                      int h_offset, int B, int K, int H, int F, int J, int root_joint, int linear, hipStream_t st,
                      int h_inner = 0, size_t outer_stride = 0);   // (h_inner, outer_stride): see jpma_kernel; 0 = contiguous H
 
+// ---- capi_weights.hip ------------------------------------------------------------------------------------------
+// fp32 -> bf16 (f16: IEEE fp16), a plain cast: the FAST / FAST16 weight matrices (d3dp_set_weights) and d3dp_op_to_bf16
+void d3dp_launch_to_bf16(const float* s, void* d, size_t n, hipStream_t st, int f16 = 0);
+
 // ---- capi.hip helpers shared with caller.hip ---------------------------------------------------------------------
 int d3dp_set_error(int code, const char* msg);        // records the message for d3dp_last_error(), returns code
 int d3dp_check_launch(const char* what);              // hipGetLastError -> status
@@ -304,7 +308,7 @@ int d3dp_train_time_mlp_bwd(const int64_t* t, const float* freq, const float* w1
                             const float* dtemb, float* dw1, float* db1, float* dw2, float* db2, int B, int C,
                             hipStream_t st);
 
-// train_g.hip: the training step's row kernels at a run-time width (any C <= 1024; the fp32 path of capi.hip for the widths
+// train_g.hip: the training step's row kernels at a run-time width (any C <= 1024; the fp32 path of capi_train.hip for the widths
 // train.hip does not instantiate).  The d3dp_train_* launchers above forward to these when d3dp_width_instantiated(C) is false.
 inline bool d3dp_width_instantiated(int C) { return C == 64 || C == 128 || C == 256 || C == 512; }
 int d3dp_train_g_add_mask_ln(const float* x_in, const float* y, const float* mask, int axis, int F, int J, const float* w,

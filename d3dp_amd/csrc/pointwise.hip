@@ -351,7 +351,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const float* __restrict__
   for (int it = 0; it < kRowTokens; ++it) {
     const int tl = (blockIdx.x * kRowTokens + it) * 4 + wave;    // chunk-local row: sequence tl / SP, token tl % SP
     if (tl >= T) break;
-    // SP >= F J rows per sequence (capi.hip: a multiple of 64 when the skewed Linear schedule is in use): the pad rows get
+    // SP >= F J rows per sequence (ctx.h seq_pitch(): a multiple of 64 when the skewed Linear schedule is in use): the pad rows get
     // the embedding of an all-zero input at joint 0 -- finite filler that flows through the row-wise kernels and the Linears
     // and is never read by an attention kernel nor written to the output
     const bool pad = (tl % SP) >= FJ;
@@ -464,7 +464,7 @@ __global__ __launch_bounds__(256) void time_mlp_kernel(const int64_t* __restrict
 // ------------------------------------------------------------------------------------------------
 // Any width (round 6, VERDICT r5 missing 4): the reference takes every `-cs` its 8 heads divide (common/arguments.py:49,
 // mixste.py:46-62); the kernels above are instantiated for C in {64, 128, 256, 512}, the widths whose Linears run on the
-// split-fp16 matrix-core kernels.  Other widths run the fp32 implementation (capi.hip: exact_impl 2 -- fp32-MFMA Linears,
+// split-fp16 matrix-core kernels.  Other widths run the fp32 implementation (capi.hip read_switches: exact_impl 2 -- fp32-MFMA Linears,
 // fp32 row attention) through the four kernels below: the same arithmetic in the same order per row (two-pass statistics,
 // 1 / C as a multiplied reciprocal, fma with gamma / beta), the width a run-time argument, a lane's NVM slots masked behind it.
 // fp32 activations only (the FAST and split-operand forms exist for the instantiated widths).

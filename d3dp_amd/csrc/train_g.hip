@@ -2,12 +2,12 @@
 //
 // The reference trains at any `-cs` its 8 heads divide (common/arguments.py:49, main.py:325 around mixste.py:215-225); train.hip
 // instantiates its row kernels for C in {64, 128, 256, 512}, the widths whose Linears run on the split-fp16 matrix-core kernels.
-// Any other width trains on the fp32 path of capi.hip (D3DP_TRAIN_IMPL=f32's path: gemm_f32_kernel forward / dgrad / split-K wgrad,
+// Any other width trains on the fp32 path of capi_train.hip (D3DP_TRAIN_IMPL=f32's path: gemm_f32_kernel forward / dgrad / split-K wgrad,
 // fp32 row attention forward, VALU attention backward with a run-time head dim) through the kernels below: the formulas of
 // train.hip's kernels (same order per row: two-pass statistics, 1 / C as a multiplied reciprocal, fma with gamma / beta; the
 // LayerNorm backward in the same three steps), the width an argument, a lane's NVM slots masked behind it.  No operand rows, no
 // absmax (the fp32 path has no operand scales).  [dgamma | dbeta] leave as per-workgroup partial rows like in train.hip: the
-// fixed-order reduction of capi.hip adds them -- no float atomics here either.
+// fixed-order reduction of capi_train.hip adds them -- no float atomics here either.
 #include "common.h"
 #include "kernels.h"
 

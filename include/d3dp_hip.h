@@ -93,7 +93,7 @@ typedef struct d3dp_cfg {
   int32_t mode;          /* D3DP_MODE_*                              */
   int32_t chunk_seqs;    /* most (clip,hypothesis) sequences per internal pass; 0 = library default (31 EXACT, 15 FAST).  EXACT
                           * mode sizes its passes (<= this) so that the persistent Linear kernels' last tile rounds are full
-                          * (capi.hip plan()); results do not depend on the split, bit for bit.
+                          * (ctx.h plan()); results do not depend on the split, bit for bit.
                           * EXACT mode addresses a pass's Linear outputs with 32-bit byte offsets: chunk_seqs * F * J * 3 *
                           * channels * 4 must stay below 2^32 (169 sequences at F=243, J=17, C=512), else d3dp_denoise fails. */
 } d3dp_cfg;

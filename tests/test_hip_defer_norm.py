@@ -1,4 +1,4 @@
-"""The deferred shared norm of EXACT mode (capi.hip d3dp_ctx::defer_norm): at a block boundary without Temporal_pos the norm pair
+"""The deferred shared norm of EXACT mode (ctx.h d3dp_ctx::defer_norm): at a block boundary without Temporal_pos the norm pair
 leaves x un-normalised and stores (mean, rstd) per row; the next block's proj applies the norm in its residual epilogue
 (gemm_x2.hip EPI_RESID_NORM).  Same expression on the same fp32 values: every comparison here is ``torch.equal`` against
 ``D3DP_DEFER_NORM=0``, the in-place form.

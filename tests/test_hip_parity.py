@@ -143,7 +143,7 @@ def test_linear_split_f16_is_fp32_class(lib, M, N, K):
     A2 = torch.empty(2, M, K, dtype=torch.float16, device="cuda")
     W2 = torch.empty(2, N, K, dtype=torch.float16, device="cuda")
     _lib.check(lib.d3dp_op_split2(Ad.data_ptr(), A2.data_ptr(), M * K, 16.0, stream()))    # activation scale
-    w_scale = 2.0 ** (13 - int(np.floor(np.log2(W.abs().max().item()))))    # max |w| w_scale in [2^13, 2^14), as capi.hip
+    w_scale = 2.0 ** (13 - int(np.floor(np.log2(W.abs().max().item()))))    # max |w| w_scale in [2^13, 2^14), as capi_weights.hip
     _lib.check(lib.d3dp_op_split2(Wd.data_ptr(), W2.data_ptr(), N * K, w_scale, stream()))
     a_hi, a_lo = h2i_planes(A2, M, K)
     assert torch.equal(a_hi, (Ad * 16.0).half()) and torch.equal(a_lo, (Ad * 16.0 - a_hi.float()).half())   # layout + split
@@ -917,7 +917,7 @@ def test_exact_residual_adds_inside_the_linears_change_no_bit(golden_dir, monkey
 @pytest.mark.variants
 @pytest.mark.parametrize("frames", [27, 243])
 def test_exact_norm2_folded_into_the_linears(golden_dir, monkeypatch, frames):
-    """D3DP_FOLD_LN=1 (built, measured and left off: no faster, capi.hip fold_ln): norm2 (mixste.py:115) without
+    """D3DP_FOLD_LN=1 (built, measured and left off: no faster, ctx.h fold_ln): norm2 (mixste.py:115) without
     a kernel of its own -- proj's epilogue leaves x + proj(...) as fc1's UN-normalised split-fp16 operand with the row
     statistics in 64-column pieces, and fc1 = LN folded into the Linear (W diag(gamma), rstd (. - mean c1) + c2 in the
     epilogue).  Against the reference goldens at three timesteps, and against the default (norm2 as a row kernel): the two
