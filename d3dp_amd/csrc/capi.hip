@@ -125,8 +125,13 @@ const char* d3dp_profile_class_name(int32_t cls) {
 int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   if (!cfg || !out) return d3dp_fail(D3DP_EINVAL, "d3dp_create: null argument");
   const d3dp_cfg& g = *cfg;
-  // (frames > 256: every mode takes the chunked-key form of its attention kernels; at head dim 8 FAST / FAST16 contexts stay on
-  //  the row kernel -- fp32 arithmetic on their 2-byte rows -- and EXACT contexts on the fp32 kernels, at every clip length)
+  // (frames > 256: EXACT, FAST and FAST16 contexts take the chunked-key form of their attention kernels; at head dim 8 FAST / FAST16
+  //  contexts stay on the row kernel -- fp32 arithmetic on their 2-byte rows -- and EXACT contexts on the fp32 kernels, at every clip
+  //  length.  TRAIN contexts: the training step's split-fp16 attention (head dims 64, 32, 16: train_attn.hip) passes keys / queries
+  //  through LDS in chunks and takes every length up to 1024; its fp32 attention -- head dim 8, the cross-check switches -- holds a
+  //  whole sequence in LDS and d3dp_train_forward refuses more than 256 frames there; a TRAIN context of a width outside the
+  //  instantiated set runs that fp32 attention with a run-time head dim and is refused BELOW beyond 256 tokens, 153 at head dims
+  //  above 64.)
   if (g.frames < 1 || g.frames > 1024) return d3dp_fail(D3DP_ENOTSUP, "frames=%d not in [1,1024]", g.frames);
   // (more than 32 joints: the spatial axis takes the whole-sequence attention kernels the temporal axis runs on, round 6)
   if (g.joints < 1 || g.joints > 256) return d3dp_fail(D3DP_ENOTSUP, "joints=%d not in [1,256]", g.joints);

@@ -431,10 +431,13 @@ int d3dp_train_forward(d3dp_ctx* c, const float* x2d, const float* x3d, const in
   const TrainPath path(*c);
   const bool use_x2 = path.use_x2;
   // clips longer than 256 frames (reference common/arguments.py:58, main.py:325 train at any `-f`): the split-fp16 attention kernels
-  // pass their keys / queries through LDS in chunks (train_attn.hip, round 6); the fp32 cross-check kernels hold whole sequences
+  // pass their keys / queries through LDS in chunks (train_attn.hip: head dims 64, 32 and 16); the fp32 kernels hold whole
+  // sequences, and they are what head dim 8, a width outside the instantiated set and the cross-check switches run
   if (g.frames > 256 && !(path.attn_x2(0) && path.attn_x2(1)))
-    return d3dp_fail(D3DP_ENOTSUP, "frames=%d > 256: the training step runs such clips on its split-fp16 attention kernels only (head dim 64, "
-                              "no D3DP_TRAIN_IMPL=f32 / D3DP_TRAIN_ATTN=f32|x2t cross-check)", g.frames);
+    return d3dp_fail(D3DP_ENOTSUP, "frames=%d > 256: the training step runs such clips on its split-fp16 attention kernels only, which take "
+                              "head dims 64, 32 and 16 (channels=%d heads=%d is head dim %d) and are switched off by the cross-check "
+                              "switches D3DP_TRAIN_IMPL=f32 and D3DP_TRAIN_ATTN=f32|x2t; the fp32 attention holds a whole sequence "
+                              "in LDS (<= 256 frames)", g.frames, g.channels, g.heads, g.channels / g.heads);
   const TrainLayout L = train_layout(g, B);
   if (workspace_bytes < L.total_floats * 4) return d3dp_fail(D3DP_ESTATE, "train workspace too small");
   hipStream_t st = (hipStream_t)stream;

@@ -254,7 +254,9 @@ inline SeqMap temporal_map(int F, int J, int sp = 0) { return SeqMap{F, J, sp > 
 // Which path a TRAIN context's step takes, computed once per call from the switches read at d3dp_create.
 //   use_x2     the Linears on split-fp16 operands (X2Train, capi_train.hip); else the fp32 matrix cores
 //   attn_x2(a) axis a's attention on the split-fp16 kernels of train_attn.hip: they need the split Linears' device-side scales
-//              and head dim 64; clips of up to 1024 frames (beyond 256 their keys / queries pass through LDS in chunks)
+//              and a head dim the matrix cores take (mfma_head_dim: 64, 32, 16 -- `-cs` 512 / 256 / 128 with the model's 8 heads);
+//              clips of up to 1024 frames (beyond 256 their keys / queries pass through LDS in chunks).  Head dim 8 and the
+//              widths outside the instantiated set stay on the fp32 kernels of train.hip (<= 256 frames)
 //   needs_aux  the backward pass forks its weight-gradient products onto the context's second stream (made by d3dp_create)
 struct TrainPath {
   bool use_x2, attn_x2_t, attn_x2_s, needs_aux;
@@ -262,7 +264,7 @@ struct TrainPath {
   explicit TrainPath(const d3dp_ctx& c) {
     const d3dp_cfg& g = c.cfg;
     use_x2 = c.train_x2 && g.channels % 32 == 0 && g.hidden % 32 == 0;
-    attn_x2_t = use_x2 && c.train_attn_x2 > 0 && g.channels / g.heads == 64 && g.frames <= 1024;
+    attn_x2_t = use_x2 && c.train_attn_x2 > 0 && mfma_head_dim(g.channels / g.heads) && g.frames <= 1024;
     attn_x2_s = attn_x2_t && c.train_attn_x2 > 1;      // the spatial axis too
     needs_aux = c.train() && use_x2 && c.train_overlap;
   }

@@ -286,7 +286,7 @@ size_t d3dp_train_attn_stats_bytes(int n_seq, int n_tok, int heads);
 int d3dp_train_attn_bwd(const float* qkv, const float* o, const float* dout, float* dqkv, void* stats, int n_seq,
                         SeqMap map, int C, int heads, hipStream_t st);
 constexpr int D3DP_EMBED_BWD_ROWS = 64;
-// ---- train_attn.hip: the training step's attention on split-fp16 operands (head dim 64, <= 256 tokens per sequence) ----
+// ---- train_attn.hip: the training step's attention on split-fp16 operands (head dim 64, 32 or 16: -2 for any other; <= 1024 tokens per sequence) ----
 // stats: d3dp_train_attn_x2_stats_bytes per attention (the forward leaves the log-sum-exp of every query for the backward pass);
 // amax_qkv / amax_do: absmax slots of the whole qkv tensor / of dout (left by the Linears that produced them); amax_out
 // (optional): absmax slot of the result.

@@ -1,5 +1,7 @@
 // Attention of the TRAINING step on the fp16 matrix cores (reference common/mixste.py:63-82 inside
-// main.py:387-401's forward / backward), head dim 64, sequences of up to 256 tokens (the temporal axis: 243 frames).
+// main.py:387-401's forward / backward), head dims 64, 32 and 16 (`-cs` 512 / 256 / 128 with the model's 8 heads: HD is a template
+// parameter of every kernel, TAHead<HD> of ta_common.h says what follows from it), sequences of up to 1024 tokens (the temporal
+// axis; beyond 256 every kernel passes its keys / queries through LDS in chunks).  The text below is written at head dim 64.
 //
 // Round 4 ran the temporal forward and both backward passes on the FP32 matrix cores (v_mfma_f32_16x16x4_f32: 1/16 of the fp16
 // rate; 5.9 ms of the 27 ms configs[4] step).  Here every product runs on split-fp16 operands like the step's Linears
@@ -21,14 +23,15 @@
 // LDS image of a [n][64] matrix: two planes (hi | lo) of 128-byte rows, 16-byte slot s of row r at s ^ (((r >> 1) & 3) << 1)
 // -- the V image of attn_frag.h: conflict-free for the transposed fragment reads (ds_read_b64_tr_b16: 4 rows x 32 B per 16
 // lanes) AND for the row fragment reads (ds_read_b128, whose lane groups pair rows {0-3, 12-15} of one slot with rows {4-11}
-// of the neighbouring one) -- so ONE image serves both uses of K (S^T and dQ^T) and of Q / dO in pass KV.
+// of the neighbouring one) -- so ONE image serves both uses of K (S^T and dQ^T) and of Q / dO in pass KV.  Head dims 32 and 16: rows of
+// 64 / 32 bytes under one swizzle each that serves both reads as well (derived in ta_common.h).
 #include "common.h"
 #include "kernels.h"
 #include "ta_common.h"
 
 namespace {
 
-struct TAStat { float L, D; };                         // L = log2 sum_j exp(s_ij) (s = q.k / 8), D = dO_i . O_i
+struct TAStat { float L, D; };                         // L = log2 sum_j exp(s_ij) (s = q.k HD^-0.5), D = dO_i . O_i
 
 template <int NW>
 __device__ __forceinline__ void ta_block_amax(float am, unsigned* amax, float* part) {
@@ -47,13 +50,13 @@ __device__ __forceinline__ void ta_block_amax(float am, unsigned* amax, float* p
 // forward
 // (NKC: key tiles per LDS chunk.  Round 6: the images hold 128 keys at a time -- the online softmax runs over key pairs anyway --
 //  so a 243-frame problem needs 64 KiB instead of 128 and TWO workgroups share a CU: four waves per SIMD instead of two)
-template <int NKT, int NW, int NKC>
+template <int NKT, int NW, int NKC, int HD>
 __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                            TAStat* __restrict__ stats, SeqMap map, int C, int heads, int groups,
                                                            int n_work, const unsigned* __restrict__ amax_qkv,
                                                            unsigned* __restrict__ amax_out, f16* __restrict__ op, int T, int Tp,
                                                            float* __restrict__ op_unscale) {
-  constexpr int NK = 16 * NKC, PLANE = NK * 128;
+  constexpr int NK = 16 * NKC, PLANE = NK * 2 * HD, ND = HD / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* kimg = smem;
   char* vimg = smem + 2 * PLANE;
@@ -77,20 +80,20 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
   const int prob = unit / groups, group = unit % groups;
   const int seq = prob / heads, head = prob % heads;
   const int base = ta_seq_base(map, seq);
-  const float* p0 = qkv + (size_t)base * ld + (size_t)head * 64;
+  const float* p0 = qkv + (size_t)base * ld + (size_t)head * HD;
   const int qt = group * NW + wave;
   const bool active = qt * 16 < n;                     // (wave-uniform)
   const int fi = lane & 15, fg = lane >> 4;
   const int q = qt * 16 + fi;
   const size_t tok = (size_t)(base + min(q, n - 1) * map.tok_stride);
-  f16x8 qh[2], ql[2];
-  if (active) ta_load_row_op(qkv + tok * ld + head * 64, fg, sq, qh, ql);
-  const TAFrag fk = ta_frag(kimg, lane), fv = ta_frag(vimg, lane);
-  const float cexp = 0.125f * kLog2e / (sq * sq);     // raw accumulator -> logit in base-2 units
+  typename TAHead<HD>::frag qh[TAHead<HD>::NQ], ql[TAHead<HD>::NQ];
+  if (active) ta_load_row_op<HD>(qkv + tok * ld + head * HD, fg, sq, qh, ql);
+  const TAFragT<HD> fk = ta_frag<HD>(kimg, lane), fv = ta_frag<HD>(vimg, lane);
+  const float cexp = TAHead<HD>::SCALE * kLog2e / (sq * sq);     // raw accumulator -> logit in base-2 units
   float mrun = -INFINITY, lrun = 0.f;                  // running row maximum (base-2 logit units) and denominator
-  f32x4 o[4];
+  f32x4 o[ND];
 #pragma unroll
-  for (int dn = 0; dn < 4; ++dn) o[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int dn = 0; dn < ND; ++dn) o[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
   for (int kc = 0; kc < NKT && 16 * kc < n; kc += NKC) {
   if (unit != (int)blockIdx.x || kc != 0) __syncthreads();   // every wave is done with the previous chunk's / unit's images
@@ -99,7 +102,7 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
     const size_t rs2[2] = {rs, rs};
     const float sc2[2] = {sq, sq};
     char* const img2[2] = {kimg, vimg};
-    ta_stage_many<NK, NW * 64, 2>(src2, rs2, sc2, img2, n - 16 * kc, tid);
+    ta_stage_many<NK, NW * 64, 2, HD>(src2, rs2, sc2, img2, n - 16 * kc, tid);
   }
   __syncthreads();
   if (active) {
@@ -140,7 +143,7 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
       psum += __shfl_xor(psum, 32, 64);
       lrun = fmaf(lrun, alpha, psum);
 #pragma unroll
-      for (int dn = 0; dn < 4; ++dn) o[dn] *= alpha;
+      for (int dn = 0; dn < ND; ++dn) o[dn] *= alpha;
       ta_tr_chunk<PLANE>(fv, t >> 1, ph, pl, o);
     }
   }
@@ -149,9 +152,9 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
     // o = (v scale) x 1024 x sum_j p_j v_j against the running maximum; lrun = 1024 x sum_j p_j
     const float inv = 1.0f / (sq * lrun);
     if (q < n) {
-      float* dst = out + tok * C + head * 64 + fg * 4;     // O^T[d = dn 16 + 4 fg + i][query fi]
+      float* dst = out + tok * C + head * HD + fg * 4;     // O^T[d = dn 16 + 4 fg + i][query fi]
 #pragma unroll
-      for (int dn = 0; dn < 4; ++dn) {
+      for (int dn = 0; dn < ND; ++dn) {
         const float4 r4 = make_float4(o[dn][0] * inv, o[dn][1] * inv, o[dn][2] * inv, o[dn][3] * inv);
         am = fmaxf(am, fmaxf(fmaxf(fabsf(r4.x), fabsf(r4.y)), fmaxf(fabsf(r4.z), fabsf(r4.w))));
         *reinterpret_cast<float4*>(dst + dn * 16) = r4;
@@ -161,7 +164,7 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
           f16x4 hi, lo;
 #pragma unroll
           for (int e = 0; e < 4; ++e) { const f16 hh = (f16)y[e]; hi[e] = hh; lo[e] = (f16)(y[e] - (float)hh); }
-          f16* d = op + tok * 2 * C + h2i_col(head * 64 + dn * 16 + fg * 4);
+          f16* d = op + tok * 2 * C + h2i_col(head * HD + dn * 16 + fg * 4);
           *reinterpret_cast<f16x4*>(d) = hi;
           *reinterpret_cast<f16x4*>(d + kH2iLo) = lo;
         }
@@ -175,13 +178,13 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
 
 // ------------------------------------------------------------------------------------------------------------------------
 // backward, pass Q: dQ (and D_i into the statistics)
-template <int NKT, int NW, int NKC, int WPE>
+template <int NKT, int NW, int NKC, int WPE, int HD>
 __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                              const float* __restrict__ dout, float* __restrict__ dqkv,
                                                              TAStat* __restrict__ stats, SeqMap map, int C, int heads, int groups,
                                                              int n_work, const unsigned* __restrict__ amax_qkv,
                                                              const unsigned* __restrict__ amax_do, unsigned* __restrict__ amax_out) {
-  constexpr int NK = 16 * NKC, PLANE = NK * 128;      // (the images hold NKC key tiles at a time: see tattn_fwd_kernel)
+  constexpr int NK = 16 * NKC, PLANE = NK * 2 * HD, ND = HD / 16;      // (the images hold NKC key tiles at a time: see tattn_fwd_kernel)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* kimg = smem;
   char* vimg = smem + 2 * PLANE;
@@ -195,26 +198,27 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
   const int prob = unit / groups, group = unit % groups;
   const int seq = prob / heads, head = prob % heads;
   const int base = ta_seq_base(map, seq);
-  const float* p0 = qkv + (size_t)base * ld + (size_t)head * 64;
+  const float* p0 = qkv + (size_t)base * ld + (size_t)head * HD;
   const int qt = group * NW + wave;
   const bool active = qt * 16 < n;                     // (wave-uniform)
   const int fi = lane & 15, fg = lane >> 4;
   const int q = qt * 16 + fi;
   const size_t tok = (size_t)(base + min(q, n - 1) * map.tok_stride);
-  f16x8 qh[2], ql[2], gh[2], gl[2];
+  typename TAHead<HD>::frag qh[TAHead<HD>::NQ], ql[TAHead<HD>::NQ], gh[TAHead<HD>::NQ], gl[TAHead<HD>::NQ];
   float D = 0.f, L = 0.f;
   if (active) {
-    ta_load_row_op(qkv + tok * ld + head * 64, fg, sq, qh, ql);
-    ta_load_row_op(dout + tok * C + head * 64, fg, sg, gh, gl);
+    ta_load_row_op<HD>(qkv + tok * ld + head * HD, fg, sq, qh, ql);
+    ta_load_row_op<HD>(dout + tok * C + head * HD, fg, sg, gh, gl);
     {
-      const float* gs = dout + tok * C + head * 64;
-      const float* os = o + tok * C + head * 64;
+      const float* gs = dout + tok * C + head * HD;
+      const float* os = o + tok * C + head * HD;
+      constexpr int W = HD == 16 ? 4 : 8;              // contiguous channels per lane and half: those of ta_load_row_op, in that order
 #pragma unroll
-      for (int half = 0; half < 2; ++half)
+      for (int half = 0; half < TAHead<HD>::NQ; ++half)
 #pragma unroll
-        for (int c4 = 0; c4 < 2; ++c4) {
-          const float4 g = *reinterpret_cast<const float4*>(gs + half * 32 + fg * 8 + c4 * 4);
-          const float4 ov = *reinterpret_cast<const float4*>(os + half * 32 + fg * 8 + c4 * 4);
+        for (int c4 = 0; c4 < W / 4; ++c4) {
+          const float4 g = *reinterpret_cast<const float4*>(gs + half * 32 + fg * W + c4 * 4);
+          const float4 ov = *reinterpret_cast<const float4*>(os + half * 32 + fg * W + c4 * 4);
           D = fmaf(g.x, ov.x, D); D = fmaf(g.y, ov.y, D); D = fmaf(g.z, ov.z, D); D = fmaf(g.w, ov.w, D);
         }
       D += __shfl_xor(D, 16, 64);
@@ -222,13 +226,13 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
     }
     L = stats[(size_t)prob * n + min(q, n - 1)].L;
   }
-  const TAFrag fk = ta_frag(kimg, lane), fv = ta_frag(vimg, lane);
-  const float cexp = 0.125f * kLog2e / (sq * sq);
+  const TAFragT<HD> fk = ta_frag<HD>(kimg, lane), fv = ta_frag<HD>(vimg, lane);
+  const float cexp = TAHead<HD>::SCALE * kLog2e / (sq * sq);
   const float cdp = 1.0f / (sq * sg);                  // raw dP accumulator -> true scale
   int eb = 20;                                         // running biased exponent of the row's largest |dS| (floor 2^-107)
-  f32x4 dq[4];
+  f32x4 dq[ND];
 #pragma unroll
-  for (int dn = 0; dn < 4; ++dn) dq[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int dn = 0; dn < ND; ++dn) dq[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
   for (int kc = 0; kc < NKT && 16 * kc < n; kc += NKC) {
   if (unit != (int)blockIdx.x || kc != 0) __syncthreads();
@@ -237,7 +241,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
     const size_t rs2[2] = {rs, rs};
     const float sc2[2] = {sq, sq};
     char* const img2[2] = {kimg, vimg};
-    ta_stage_many<NK, NW * 64, 2>(src2, rs2, sc2, img2, n - 16 * kc, tid);
+    ta_stage_many<NK, NW * 64, 2, HD>(src2, rs2, sc2, img2, n - 16 * kc, tid);
   }
   __syncthreads();
   if (active) {
@@ -251,8 +255,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float pa = __builtin_amdgcn_exp2f(fmaf(a[r], cexp, -L)), pb = __builtin_amdgcn_exp2f(fmaf(b[r], cexp, -L));
-        ds[r] = pa * (fmaf(c[r], cdp, -D)) * 0.125f;
-        ds[4 + r] = pb * (fmaf(d[r], cdp, -D)) * 0.125f;
+        ds[r] = pa * (fmaf(c[r], cdp, -D)) * TAHead<HD>::SCALE;
+        ds[4 + r] = pb * (fmaf(d[r], cdp, -D)) * TAHead<HD>::SCALE;
       }
       if (16 * (kc + t + 2) > n) {                     // (uniform: only the last pair(s) hold keys >= n)
 #pragma unroll
@@ -264,7 +268,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
       const int en = max(eb, ta_exp_of_max(ds));
       if (en != eb) {                                  // (uniform over the four lanes of a column; exact rescale)
 #pragma unroll
-        for (int dn = 0; dn < 4; ++dn)
+        for (int dn = 0; dn < ND; ++dn)
 #pragma unroll
           for (int i = 0; i < 4; ++i) dq[dn][i] = ldexpf(dq[dn][i], eb - en);
         eb = en;
@@ -278,9 +282,9 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
   if (active) {
     if (q < n) {
       const float un = 1.0f / sq;
-      float* dst = dqkv + tok * ld + head * 64 + fg * 4;
+      float* dst = dqkv + tok * ld + head * HD + fg * 4;
 #pragma unroll
-      for (int dn = 0; dn < 4; ++dn) {
+      for (int dn = 0; dn < ND; ++dn) {
         const float4 r4 = make_float4(ldexpf(dq[dn][0], eb - 140) * un, ldexpf(dq[dn][1], eb - 140) * un,
                                       ldexpf(dq[dn][2], eb - 140) * un, ldexpf(dq[dn][3], eb - 140) * un);
         am = fmaxf(am, fmaxf(fmaxf(fabsf(r4.x), fabsf(r4.y)), fmaxf(fabsf(r4.z), fabsf(r4.w))));
@@ -295,13 +299,13 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
 
 // ------------------------------------------------------------------------------------------------------------------------
 // backward, pass KV: dK, dV
-template <int NKT, int NW, int NKC, int WPE>
+template <int NKT, int NW, int NKC, int WPE, int HD>
 __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                               float* __restrict__ dqkv, const TAStat* __restrict__ stats,
                                                               SeqMap map, int C, int heads, int groups, int n_work,
                                                               const unsigned* __restrict__ amax_qkv,
                                                               const unsigned* __restrict__ amax_do, unsigned* __restrict__ amax_out) {
-  constexpr int NK = 16 * NKC, PLANE = NK * 128;      // (the images hold NKC QUERY tiles at a time)
+  constexpr int NK = 16 * NKC, PLANE = NK * 2 * HD, ND = HD / 16;      // (the images hold NKC QUERY tiles at a time)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* qimg = smem;
   char* gimg = smem + 2 * PLANE;
@@ -322,25 +326,25 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
   const int key = kt * 16 + fi;
   const bool live = key < n;
   const size_t tok = (size_t)(base + min(key, n - 1) * map.tok_stride);
-  f16x8 kh[2], kl[2], vh[2], vl[2];
+  typename TAHead<HD>::frag kh[TAHead<HD>::NQ], kl[TAHead<HD>::NQ], vh[TAHead<HD>::NQ], vl[TAHead<HD>::NQ];
   if (active) {
-    ta_load_row_op(qkv + tok * ld + C + head * 64, fg, sq, kh, kl);
-    ta_load_row_op(qkv + tok * ld + 2 * C + head * 64, fg, sq, vh, vl);
+    ta_load_row_op<HD>(qkv + tok * ld + C + head * HD, fg, sq, kh, kl);
+    ta_load_row_op<HD>(qkv + tok * ld + 2 * C + head * HD, fg, sq, vh, vl);
   }
-  const TAFrag fq = ta_frag(qimg, lane), fgr = ta_frag(gimg, lane);
-  const float cexp = 0.125f * kLog2e / (sq * sq);
+  const TAFragT<HD> fq = ta_frag<HD>(qimg, lane), fgr = ta_frag<HD>(gimg, lane);
+  const float cexp = TAHead<HD>::SCALE * kLog2e / (sq * sq);
   const float cdp = 1.0f / (sq * sg);
   int eb = 20;
-  f32x4 dk[4], dv[4];
+  f32x4 dk[ND], dv[ND];
 #pragma unroll
-  for (int dn = 0; dn < 4; ++dn) { dk[dn] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[dn] = dk[dn]; }
+  for (int dn = 0; dn < ND; ++dn) { dk[dn] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[dn] = dk[dn]; }
 #pragma unroll 1
   for (int qc = 0; qc < NKT && 16 * qc < n; qc += NKC) {
   if (unit != (int)blockIdx.x || qc != 0) __syncthreads();
   // (one operand after the other here: both at once -- ta_stage_many, as in the forward pass and pass Q -- costs this 200-register
   //  kernel more than the second round trip: 98 -> 105 us)
-  ta_stage<NK, NW * 64>(qkv + (size_t)base * ld + (size_t)head * 64 + (size_t)qc * 16 * rs, rs, n - 16 * qc, sq, qimg, tid);
-  ta_stage<NK, NW * 64>(dout + (size_t)base * C + (size_t)head * 64 + (size_t)qc * 16 * map.tok_stride * C, (size_t)map.tok_stride * C,
+  ta_stage<NK, NW * 64, HD>(qkv + (size_t)base * ld + (size_t)head * HD + (size_t)qc * 16 * rs, rs, n - 16 * qc, sq, qimg, tid);
+  ta_stage<NK, NW * 64, HD>(dout + (size_t)base * C + (size_t)head * HD + (size_t)qc * 16 * map.tok_stride * C, (size_t)map.tok_stride * C,
                         n - 16 * qc, sg, gimg, tid);
   for (int i = tid; i < NK; i += NW * 64) {
     // rows >= n: their Q and dO image rows are zero, so any FINITE p and dS contribute nothing: L = +large keeps p = 0
@@ -363,8 +367,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
         const float2 sa = st[16 * t + 4 * fg + r], sb = st[16 * (t + 1) + 4 * fg + r];
         float pa = __builtin_amdgcn_exp2f(fmaf(a[r], cexp, -sa.x)), pb = __builtin_amdgcn_exp2f(fmaf(b[r], cexp, -sb.x));
         if (!live) { pa = 0.f; pb = 0.f; }
-        ds[r] = pa * (fmaf(c[r], cdp, -sa.y)) * 0.125f;
-        ds[4 + r] = pb * (fmaf(d[r], cdp, -sb.y)) * 0.125f;
+        ds[r] = pa * (fmaf(c[r], cdp, -sa.y)) * TAHead<HD>::SCALE;
+        ds[4 + r] = pb * (fmaf(d[r], cdp, -sb.y)) * TAHead<HD>::SCALE;
         const float ya = ta_opaque(pa * 1024.0f), yb = ta_opaque(pb * 1024.0f);
         const f16 ha = (f16)ya, hb = (f16)yb;
         ph[r] = ha; pl[r] = (f16)(ya - (float)ha);
@@ -374,7 +378,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
       const int en = max(eb, ta_exp_of_max(ds));
       if (en != eb) {
 #pragma unroll
-        for (int dn = 0; dn < 4; ++dn)
+        for (int dn = 0; dn < ND; ++dn)
 #pragma unroll
           for (int i = 0; i < 4; ++i) dk[dn][i] = ldexpf(dk[dn][i], eb - en);
         eb = en;
@@ -388,9 +392,9 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
   if (active) {
     if (live) {
       const float uk = 1.0f / sq, uv = 1.0f / (sg * 1024.0f);
-      float* dst = dqkv + tok * ld + C + head * 64 + fg * 4;
+      float* dst = dqkv + tok * ld + C + head * HD + fg * 4;
 #pragma unroll
-      for (int dn = 0; dn < 4; ++dn) {
+      for (int dn = 0; dn < ND; ++dn) {
         const float4 k4 = make_float4(ldexpf(dk[dn][0], eb - 140) * uk, ldexpf(dk[dn][1], eb - 140) * uk,
                                       ldexpf(dk[dn][2], eb - 140) * uk, ldexpf(dk[dn][3], eb - 140) * uk);
         const float4 v4 = make_float4(dv[dn][0] * uv, dv[dn][1] * uv, dv[dn][2] * uv, dv[dn][3] * uv);
@@ -413,12 +417,13 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
 // are row-fragment reads of the very images the other wave's products contract over -- and D_i = dO_i . O_i goes from pass Q to
 // pass KV through LDS instead of the statistics buffer.  Same products, same splits, same accumulation order as the two
 // kernels: bit-identical gradients (test_attention_backward_on_matrix_cores_matches_the_valu_kernels covers n = 9, 17 through it).
+template <int HD>
 __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                               const float* __restrict__ dout, float* __restrict__ dqkv,
                                                               const TAStat* __restrict__ stats, SeqMap map, int C, int heads,
                                                               int n_work, const unsigned* __restrict__ amax_qkv,
                                                               const unsigned* __restrict__ amax_do, unsigned* __restrict__ amax_out) {
-  constexpr int NK = 32, PLANE = NK * 128, NW = 2;
+  constexpr int NK = 32, PLANE = NK * 2 * HD, NW = 2, ND = HD / 16;
   __shared__ __attribute__((aligned(16))) char smem[8 * PLANE];
   __shared__ float2 st[NK];                              // (L, D) of the sequence's queries
   __shared__ float part[NW];
@@ -431,28 +436,32 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
   const int fi = lane & 15, fg = lane >> 4;
   const size_t ld = (size_t)3 * C, rs = (size_t)map.tok_stride * ld;
   const float sq = ta_scale(amax_qkv), sg = ta_scale(amax_do);
-  const float cexp = 0.125f * kLog2e / (sq * sq);
+  const float cexp = TAHead<HD>::SCALE * kLog2e / (sq * sq);
   const float cdp = 1.0f / (sq * sg);                    // raw dP accumulator -> true scale
-  const TAFrag fq = ta_frag(qimg, lane), fk = ta_frag(kimg, lane), fv = ta_frag(vimg, lane), fgr = ta_frag(gimg, lane);
-  auto row_op = [&](const TAFrag& f, int t, f16x8 (&h)[2], f16x8 (&l)[2]) {   // tile t's rows as a split register operand
-    h[0] = *reinterpret_cast<const f16x8*>(f.r0 + t * 2048);
-    h[1] = *reinterpret_cast<const f16x8*>(f.r1 + t * 2048);
-    l[0] = *reinterpret_cast<const f16x8*>(f.r0 + t * 2048 + PLANE);
-    l[1] = *reinterpret_cast<const f16x8*>(f.r1 + t * 2048 + PLANE);
+  const TAFragT<HD> fq = ta_frag<HD>(qimg, lane), fk = ta_frag<HD>(kimg, lane), fv = ta_frag<HD>(vimg, lane), fgr = ta_frag<HD>(gimg, lane);
+  typedef typename TAHead<HD>::frag frag;
+  constexpr int NQ = TAHead<HD>::NQ, TILE = 32 * HD;     // (16 image rows)
+  auto row_op = [&](const TAFragT<HD>& f, int t, frag (&h)[NQ], frag (&l)[NQ]) {   // tile t's rows as a split register operand
+    h[0] = *reinterpret_cast<const frag*>(f.r0 + t * TILE);
+    l[0] = *reinterpret_cast<const frag*>(f.r0 + t * TILE + PLANE);
+    if constexpr (NQ == 2) {
+      h[1] = *reinterpret_cast<const frag*>(f.r1 + t * TILE);
+      l[1] = *reinterpret_cast<const frag*>(f.r1 + t * TILE + PLANE);
+    }
   };
   float am = 0.f;
   for (int unit = blockIdx.x; unit < n_work; unit += gridDim.x) {
     const int seq = unit / heads, head = unit - seq * heads;
     const int base = ta_seq_base(map, seq);
-    const float* p0 = qkv + (size_t)base * ld + (size_t)head * 64;
-    const float* g0 = dout + (size_t)base * C + (size_t)head * 64;
+    const float* p0 = qkv + (size_t)base * ld + (size_t)head * HD;
+    const float* g0 = dout + (size_t)base * C + (size_t)head * HD;
     if (unit != (int)blockIdx.x) __syncthreads();        // every wave is done with the previous unit's images
     {
       const float* const src4[4] = {p0, p0 + C, p0 + 2 * C, g0};
       const size_t rs4[4] = {rs, rs, rs, (size_t)map.tok_stride * C};
       const float sc4[4] = {sq, sq, sq, sg};
       char* const img4[4] = {qimg, kimg, vimg, gimg};
-      ta_stage_many<NK, NW * 64, 4>(src4, rs4, sc4, img4, n, tid);
+      ta_stage_many<NK, NW * 64, 4, HD>(src4, rs4, sc4, img4, n, tid);
     }
     const int row = wave * 16 + fi;                      // this lane's query (pass Q) and key (pass KV)
     const bool live = row < n;
@@ -460,14 +469,15 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
     {
       // D_i = dO_i . O_i in the channel order of tattn_bwd_q_kernel; rows >= n: L = +large keeps p = 0 in pass KV
       float D = 0.f;
-      const float* gs = dout + tok * C + head * 64;
-      const float* os = o + tok * C + head * 64;
+      const float* gs = dout + tok * C + head * HD;
+      const float* os = o + tok * C + head * HD;
+      constexpr int W = HD == 16 ? 4 : 8;
 #pragma unroll
-      for (int half = 0; half < 2; ++half)
+      for (int half = 0; half < NQ; ++half)
 #pragma unroll
-        for (int c4 = 0; c4 < 2; ++c4) {
-          const float4 g = *reinterpret_cast<const float4*>(gs + half * 32 + fg * 8 + c4 * 4);
-          const float4 ov = *reinterpret_cast<const float4*>(os + half * 32 + fg * 8 + c4 * 4);
+        for (int c4 = 0; c4 < W / 4; ++c4) {
+          const float4 g = *reinterpret_cast<const float4*>(gs + half * 32 + fg * W + c4 * 4);
+          const float4 ov = *reinterpret_cast<const float4*>(os + half * 32 + fg * W + c4 * 4);
           D = fmaf(g.x, ov.x, D); D = fmaf(g.y, ov.y, D); D = fmaf(g.z, ov.z, D); D = fmaf(g.w, ov.w, D);
         }
       D += __shfl_xor(D, 16, 64);
@@ -478,7 +488,7 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
     if (wave * 16 < n) {
       // ---- pass Q: this wave's tile as QUERIES against the key pair (0, 1)
       {
-        f16x8 qh[2], ql[2], gh[2], gl[2];
+        frag qh[NQ], ql[NQ], gh[NQ], gl[NQ];
         row_op(fq, wave, qh, ql);
         row_op(fgr, wave, gh, gl);
         const float2 ld_ = st[row];
@@ -489,23 +499,23 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float pa = __builtin_amdgcn_exp2f(fmaf(a[r], cexp, -ld_.x)), pb = __builtin_amdgcn_exp2f(fmaf(b[r], cexp, -ld_.x));
-          ds[r] = pa * (fmaf(c[r], cdp, -ld_.y)) * 0.125f;
-          ds[4 + r] = pb * (fmaf(d[r], cdp, -ld_.y)) * 0.125f;
+          ds[r] = pa * (fmaf(c[r], cdp, -ld_.y)) * TAHead<HD>::SCALE;
+          ds[4 + r] = pb * (fmaf(d[r], cdp, -ld_.y)) * TAHead<HD>::SCALE;
           if (4 * fg + r >= n) ds[r] = 0.f;
           if (16 + 4 * fg + r >= n) ds[4 + r] = 0.f;
         }
         const int eb = max(20, ta_exp_of_max(ds));
         f16x8 sh, sl;
         ta_split_run(ds, eb, sh, sl);
-        f32x4 dq[4];
+        f32x4 dq[ND];
 #pragma unroll
-        for (int dn = 0; dn < 4; ++dn) dq[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int dn = 0; dn < ND; ++dn) dq[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
         ta_tr_chunk<PLANE>(fk, 0, sh, sl, dq);           // dQ^T[d][query] = K^T dS^T
         if (live) {
           const float un = 1.0f / sq;
-          float* dst = dqkv + tok * ld + head * 64 + fg * 4;
+          float* dst = dqkv + tok * ld + head * HD + fg * 4;
 #pragma unroll
-          for (int dn = 0; dn < 4; ++dn) {
+          for (int dn = 0; dn < ND; ++dn) {
             const float4 r4 = make_float4(ldexpf(dq[dn][0], eb - 140) * un, ldexpf(dq[dn][1], eb - 140) * un,
                                           ldexpf(dq[dn][2], eb - 140) * un, ldexpf(dq[dn][3], eb - 140) * un);
             am = fmaxf(am, fmaxf(fmaxf(fabsf(r4.x), fabsf(r4.y)), fmaxf(fabsf(r4.z), fabsf(r4.w))));
@@ -515,7 +525,7 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
       }
       // ---- pass KV: the same tile as KEYS against the query pair (0, 1)
       {
-        f16x8 kh[2], kl[2], vh[2], vl[2];
+        frag kh[NQ], kl[NQ], vh[NQ], vl[NQ];
         row_op(fk, wave, kh, kl);
         row_op(fv, wave, vh, vl);
         f32x4 a, b, c, d;
@@ -528,16 +538,16 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
           const float2 sa = st[4 * fg + r], sb = st[16 + 4 * fg + r];
           float pa = __builtin_amdgcn_exp2f(fmaf(a[r], cexp, -sa.x)), pb = __builtin_amdgcn_exp2f(fmaf(b[r], cexp, -sb.x));
           if (!live) { pa = 0.f; pb = 0.f; }
-          ds[r] = pa * (fmaf(c[r], cdp, -sa.y)) * 0.125f;
-          ds[4 + r] = pb * (fmaf(d[r], cdp, -sb.y)) * 0.125f;
+          ds[r] = pa * (fmaf(c[r], cdp, -sa.y)) * TAHead<HD>::SCALE;
+          ds[4 + r] = pb * (fmaf(d[r], cdp, -sb.y)) * TAHead<HD>::SCALE;
           const float ya = ta_opaque(pa * 1024.0f), yb = ta_opaque(pb * 1024.0f);
           const f16 ha = (f16)ya, hb = (f16)yb;
           ph[r] = ha; pl[r] = (f16)(ya - (float)ha);
           ph[4 + r] = hb; pl[4 + r] = (f16)(yb - (float)hb);
         }
-        f32x4 dk[4], dv[4];
+        f32x4 dk[ND], dv[ND];
 #pragma unroll
-        for (int dn = 0; dn < 4; ++dn) { dk[dn] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[dn] = dk[dn]; }
+        for (int dn = 0; dn < ND; ++dn) { dk[dn] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[dn] = dk[dn]; }
         ta_tr_chunk<PLANE>(fgr, 0, ph, pl, dv);          // dV^T[d][key] = dO^T P
         const int eb = max(20, ta_exp_of_max(ds));
         f16x8 sh, sl;
@@ -545,9 +555,9 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
         ta_tr_chunk<PLANE>(fq, 0, sh, sl, dk);           // dK^T[d][key] = Q^T dS
         if (live) {
           const float uk = 1.0f / sq, uv = 1.0f / (sg * 1024.0f);
-          float* dst = dqkv + tok * ld + C + head * 64 + fg * 4;
+          float* dst = dqkv + tok * ld + C + head * HD + fg * 4;
 #pragma unroll
-          for (int dn = 0; dn < 4; ++dn) {
+          for (int dn = 0; dn < ND; ++dn) {
             const float4 k4 = make_float4(ldexpf(dk[dn][0], eb - 140) * uk, ldexpf(dk[dn][1], eb - 140) * uk,
                                           ldexpf(dk[dn][2], eb - 140) * uk, ldexpf(dk[dn][3], eb - 140) * uk);
             const float4 v4 = make_float4(dv[dn][0] * uv, dv[dn][1] * uv, dv[dn][2] * uv, dv[dn][3] * uv);
@@ -564,7 +574,7 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
 }
 
 struct TAOperand { f16* op; int T, Tp; float* unscale; };   // forward only: the output also as the next Linear's operand rows
-template <int NKT>
+template <int NKT, int HD>
 int ta_launch(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats, int n_seq,
               SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
               hipStream_t st, TAOperand po = {nullptr, 0, 0, nullptr}) {
@@ -575,36 +585,42 @@ int ta_launch(int which, const float* qkv, const float* o, const float* dout, fl
   // whole sequences of Q / dO in LDS and one workgroup per CU.
   // Sequences longer than 256 tokens (training at `-f 351`, reference common/arguments.py:58): every kernel is chunked, so nothing
   // holds a whole sequence -- pass KV then takes its queries in chunks of 128 too (at its own register count: one workgroup per CU).
-  constexpr int NKC_KV = NKT > 16 ? 8 : NKT;
-  const size_t lds = (size_t)4 * NKC * 16 * 128 + 64, lds_kv = (size_t)4 * NKC_KV * 16 * 128 + NKC_KV * 16 * 8 + 64, lds_fwd = lds;
+  // Head dims 32 and 16: the same tiles, chunks and waves per workgroup; the images are a half / a quarter of the above (a 243-frame
+  // forward or pass Q: 32 / 16 KiB) and the accumulators HD / 16 tiles, so every kernel fits 128 registers WITHOUT scratch and pass
+  // KV is held to 128 as well and always chunked (compiler's figures: profiles/train_small_heads.md) -- two workgroups of eight
+  // waves per CU in all three kernels.
+  constexpr int NKC_KV = (NKT > 16 || (HD < 64 && NKT > 8)) ? 8 : NKT;
+  constexpr int WPE_KV = HD < 64 ? 4 : 2;
+  constexpr int ROWB = 2 * HD;                         // bytes of an image row
+  const size_t lds = (size_t)4 * NKC * 16 * ROWB + 64, lds_kv = (size_t)4 * NKC_KV * 16 * ROWB + NKC_KV * 16 * 8 + 64, lds_fwd = lds;
   (void)NK;
   static PerDeviceOnce once;
   if (once.get([&](int) {
-        return d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_fwd_kernel<NKT, NW, NKC>), 160 * 1024) < 0 ? -3
-               : d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_bwd_q_kernel<NKT, NW, NKC, 4>), 160 * 1024) < 0 ? -3
-               : d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_bwd_kv_kernel<NKT, NW, NKC_KV, 2>), 160 * 1024);
+        return d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_fwd_kernel<NKT, NW, NKC, HD>), 160 * 1024) < 0 ? -3
+               : d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_bwd_q_kernel<NKT, NW, NKC, 4, HD>), 160 * 1024) < 0 ? -3
+               : d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_bwd_kv_kernel<NKT, NW, NKC_KV, WPE_KV, HD>), 160 * 1024);
       }) < 0) return -3;
   const int tiles = (map.n_tok + 15) / 16, groups = (tiles + NW - 1) / NW;
   const int n_work = n_seq * heads * groups;
   const dim3 grid(n_work < 2048 ? n_work : 2048), blk(NW * 64);   // (<= 2048 absmax atomics per launch)
   TAStat* s = reinterpret_cast<TAStat*>(stats);
   if (which == 0)
-    hipLaunchKernelGGL((tattn_fwd_kernel<NKT, NW, NKC>), grid, blk, lds_fwd, st, qkv, out, s, map, C, heads, groups, n_work, amax_qkv, amax_out,
+    hipLaunchKernelGGL((tattn_fwd_kernel<NKT, NW, NKC, HD>), grid, blk, lds_fwd, st, qkv, out, s, map, C, heads, groups, n_work, amax_qkv, amax_out,
                        po.op, po.T, po.Tp, po.unscale);
   else if (NKT == 2) {
     // sequences of at most 32 tokens: both passes in ONE kernel (tattn_bwd_small_kernel); under the per-kernel profile it is timed as
     // pass Q and the pass-KV call is empty
     if (which != 3) {
       const dim3 g2(n_seq * heads < 4096 ? n_seq * heads : 4096);
-      hipLaunchKernelGGL(tattn_bwd_small_kernel, g2, dim3(128), 0, st, qkv, o, dout, dqkv, (const TAStat*)s, map, C, heads, n_seq * heads,
+      hipLaunchKernelGGL(tattn_bwd_small_kernel<HD>, g2, dim3(128), 0, st, qkv, o, dout, dqkv, (const TAStat*)s, map, C, heads, n_seq * heads,
                          amax_qkv, amax_do, amax_out);
     }
   } else {                                             // which: 1 = both passes, 2 = pass Q alone, 3 = pass KV alone (needs pass Q's D_i)
     if (which != 3)
-      hipLaunchKernelGGL((tattn_bwd_q_kernel<NKT, NW, NKC, 4>), grid, blk, lds, st, qkv, o, dout, dqkv, s, map, C, heads, groups, n_work,
+      hipLaunchKernelGGL((tattn_bwd_q_kernel<NKT, NW, NKC, 4, HD>), grid, blk, lds, st, qkv, o, dout, dqkv, s, map, C, heads, groups, n_work,
                          amax_qkv, amax_do, amax_out);
     if (which != 2)
-      hipLaunchKernelGGL((tattn_bwd_kv_kernel<NKT, NW, NKC_KV, 2>), grid, blk, lds_kv, st, qkv, dout, dqkv, (const TAStat*)s, map, C, heads, groups,
+      hipLaunchKernelGGL((tattn_bwd_kv_kernel<NKT, NW, NKC_KV, WPE_KV, HD>), grid, blk, lds_kv, st, qkv, dout, dqkv, (const TAStat*)s, map, C, heads, groups,
                          n_work, amax_qkv, amax_do, amax_out);
   }
   return 0;
@@ -614,15 +630,23 @@ int ta_dispatch(int which, const float* qkv, const float* o, const float* dout, 
                 SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
                 hipStream_t st, TAOperand po = {nullptr, 0, 0, nullptr}) {
   const int n = map.n_tok;
-  if (C / heads != 64 || C % 4 != 0 || n < 1 || n > 1024 || !amax_qkv || !stats) return -2;
+  if (heads < 1 || C % heads != 0 || C % 4 != 0 || n < 1 || n > 1024 || !amax_qkv || !stats) return -2;
   if (po.op && (po.Tp < po.T || !po.unscale || C % 32 != 0)) return -1;
-#define TA_CASE(NKT_) return ta_launch<NKT_>(which, qkv, o, dout, out, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st, po);
-  if (n <= 32) { TA_CASE(2) }
-  if (n <= 64) { TA_CASE(4) }
-  if (n <= 128) { TA_CASE(8) }
-  if (n <= 256) { TA_CASE(16) }
-  if (n <= 512) { TA_CASE(32) }
-  TA_CASE(64)
+#define TA_CASE(NKT_, HD_) return ta_launch<NKT_, HD_>(which, qkv, o, dout, out, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st, po);
+#define TA_LENGTHS(HD_)              \
+  if (n <= 32) { TA_CASE(2, HD_) }   \
+  if (n <= 64) { TA_CASE(4, HD_) }   \
+  if (n <= 128) { TA_CASE(8, HD_) }  \
+  if (n <= 256) { TA_CASE(16, HD_) } \
+  if (n <= 512) { TA_CASE(32, HD_) } \
+  TA_CASE(64, HD_)
+  switch (C / heads) {                                 // the head dims these kernels are instantiated for (ctx.h mfma_head_dim)
+    case 64: { TA_LENGTHS(64) }
+    case 32: { TA_LENGTHS(32) }
+    case 16: { TA_LENGTHS(16) }
+    default: return -2;                                // (head dim 8, or a width outside the instantiated set: the fp32 kernels of train.hip)
+  }
+#undef TA_LENGTHS
 #undef TA_CASE
 }
 
@@ -630,7 +654,7 @@ int ta_dispatch(int which, const float* qkv, const float* o, const float* dout, 
 
 size_t d3dp_train_attn_x2_stats_bytes(int n_seq, int n_tok, int heads) { return (size_t)n_seq * heads * n_tok * sizeof(TAStat); }
 
-// out [T, C] = softmax(q k^T / 8) v per (sequence, head); stats: n_seq x heads x n_tok (L, D) pairs for the backward pass;
+// out [T, C] = softmax(q k^T HD^-0.5) v per (sequence, head), HD = C / heads in {64, 32, 16} (-2 for any other); stats: n_seq x heads x n_tok (L, D) pairs for the backward pass;
 // amax_qkv: absmax slot of the whole qkv tensor (the qkv Linear's epilogue); amax_out (optional): absmax slot of `out`
 // op (optional): the output also as split operand rows [Tp][2 C] (rows T .. Tp - 1 zero; T = all token rows of the batch) at the
 // scale of q / k / v, op_unscale[0] = 1 / scale, amax_out[0] = the bound (the qkv absmax) -- see tattn_fwd_kernel

@@ -154,12 +154,21 @@ D3DP_API const char* d3dp_last_error(void);
  *   any other width the reference's 8 heads divide (common/arguments.py:49, mixste.py:46-62) with channels <= 1024,
  *                         head dim % 4 == 0 and <= 128, hidden % 4 == 0: D3DP_MODE_EXACT on the fp32 implementation
  *                         (fp32-MFMA Linears, fp32 row attention, run-time-width row kernels; d3dp_exact_scales reports
- *                         implementation 2): the same 1e-3 mm tolerance at roughly a fifth of the throughput.  D3DP_MODE_TRAIN
- *                         takes such a width too, on the fp32 path of the training step (what D3DP_TRAIN_IMPL=f32 selects for
- *                         the instantiated widths), whose attention backward holds a whole sequence in LDS: there, and only
- *                         there, a TRAIN context is limited to max(frames, joints) <= 256 tokens (<= 153 at head dims
- *                         above 64) and refused beyond; at the instantiated widths TRAIN takes every frames / joints value
- *                         above.  FAST and FAST16 contexts exist for the instantiated widths only.
+ *                         implementation 2): the same 1e-3 mm tolerance at roughly a fifth of the throughput.  FAST and FAST16
+ *                         contexts exist for the instantiated widths only.
+ * What a D3DP_MODE_TRAIN context takes, by the attention its training step runs:
+ *   channels in {128, 256, 512} with head dim in {16, 32, 64} (`-cs 128 / 256 / 512` with 8 heads): Linears on split-fp16 operands and
+ *                         the attention of both axes on the split-fp16 matrix-core kernels (train_attn.hip), which pass keys /
+ *                         queries through LDS in chunks: every frames <= 1024 and joints <= 256 above;
+ *   head dim 8 (`-cs 64`): split-fp16 Linears, fp32 attention (VALU / row kernels), whose backward holds a whole sequence in LDS:
+ *                         d3dp_create accepts the context, d3dp_train_forward answers D3DP_ENOTSUP beyond 256 frames;
+ *   the cross-check switches at the widths above (D3DP_TRAIN_IMPL=f32, D3DP_TRAIN_ATTN=f32|x2t in the environment of d3dp_create)
+ *                         select that fp32 attention too, with the same limit of 256 frames;
+ *   any other width (see above: channels <= 1024, head dim % 4 == 0 and <= 128, hidden % 4 == 0): the fp32 path of the training step
+ *                         (what D3DP_TRAIN_IMPL=f32 selects for the instantiated widths: fp32-MFMA Linears, run-time-width row
+ *                         kernels, VALU attention backward with a run-time head dim).  There d3dp_create itself refuses
+ *                         max(frames, joints) > 256 tokens, and > 153 tokens at head dims above 64 (two whole-sequence images
+ *                         of the capacity head dim + the statistics in 160 KiB of LDS).
  * A D3DP_MODE_TRAIN context whose backward pass overlaps (split-fp16 Linears, D3DP_TRAIN_OVERLAP not 0) gets its second stream
  * and three events here, so that d3dp_train_backward never creates anything. */
 D3DP_API int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out);
@@ -289,9 +298,9 @@ D3DP_API int d3dp_jpma_ex(const float* pred, const float* traj, const float* cam
  * from and joined back to `stream` with events before it returns (the host is never synchronised; env D3DP_TRAIN_OVERLAP=0: one
  * stream) -- see Conventions: the caller orders against `stream` alone.
  * No gradient is accumulated with float atomics: the same inputs give the same bits.
- * Clip length: any F <= 1024 like inference (reference common/arguments.py:58); beyond 256 frames the step needs head dim 64 and
- * its split-fp16 attention kernels (keys / queries through LDS in chunks) -- the fp32 cross-check implementations
- * (D3DP_TRAIN_IMPL=f32, D3DP_TRAIN_ATTN=f32|x2t) hold whole sequences and answer D3DP_ENOTSUP there. */
+ * Clip length: any F <= 1024 like inference (reference common/arguments.py:58); beyond 256 frames the step needs its split-fp16
+ * attention kernels (head dims 64, 32 and 16; keys / queries through LDS in chunks) -- head dim 8 and the fp32 cross-check
+ * implementations (D3DP_TRAIN_IMPL=f32, D3DP_TRAIN_ATTN=f32|x2t) hold whole sequences and answer D3DP_ENOTSUP there (d3dp_create). */
 D3DP_API int d3dp_train_workspace_bytes(const d3dp_ctx* ctx, int32_t B, size_t* bytes);
 D3DP_API int d3dp_train_forward(d3dp_ctx* ctx, const float* x2d, const float* x3d, const int64_t* t, const float* masks, float* out,
                        int32_t B, void* workspace, size_t workspace_bytes, void* stream);
