@@ -1138,11 +1138,14 @@ int launch_temporal_x2(const void* qkv, void* out, int n_seq, SeqMap map, int C,
 // whole-sequence kernel (<= 256 tokens) or the chunked-key form (longer)
 template <int HD>
 int launch_attn_x2_hd(int act, int axis, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, float act_scale,
-                      hipStream_t st) {
+                      hipStream_t st, int hd_true) {
   const size_t plane = (size_t)n_seq * map.n_tok * C;
   const int n = map.n_tok;
-  const X2Scales sc = {act_scale, (HD == 64 ? 0.125f : HD == 32 ? 0.17677669529663689f : 0.25f) * 1.44269504088896340736f / (act_scale * act_scale),
-                       1.0f / act_scale, act_scale};   // cexp: HD^-0.5 log2(e) / (q scale x k scale)
+  // (padded heads: the columns hd_true .. HD - 1 of every head are exact zeros in q, k and v, and the exponent is the true head dim's)
+  const float rsq = hd_true > 0 && hd_true != HD ? (float)(1.0 / sqrt((double)hd_true))
+                                                 : (HD == 64 ? 0.125f : HD == 32 ? 0.17677669529663689f : 0.25f);
+  const X2Scales sc = {act_scale, rsq * 1.44269504088896340736f / (act_scale * act_scale),
+                       1.0f / act_scale, act_scale};   // cexp: hd^-0.5 log2(e) / (q scale x k scale)
   if (axis == 0 && n <= 32) {                          // (more than 32 joints: the kernels below take any SeqMap)
     const int n_prob = n_seq * heads;
     if (act == 3) hipLaunchKernelGGL((attn_spatial_x2_kernel<2, HD>), dim3((n_prob + 3) / 4), dim3(256), 0, st, (const float*)qkv, out, n_prob, map, C, heads, plane, sc);
@@ -1189,12 +1192,12 @@ void d3dp_launch_qkv_pack_x2(const float* src, void* dst, size_t T, int C, float
 // act_scale: the power of two q, k, v (and, for act == 3, the output planes) are scaled by -- kActScale unless the block's
 // proven operand range asked for less (capi_weights.hip).  With 16 the arithmetic is bit for bit that of the constant-scale kernels.
 int d3dp_launch_attn_x2(int act, int axis, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
-                        float act_scale, hipStream_t st) {
-  if (heads < 1 || C % heads || map.n_tok < 1 || (act != 0 && act != 3) || !(act_scale > 0.f)) return -2;
+                        float act_scale, hipStream_t st, int hd_true) {
+  if (heads < 1 || C % heads || map.n_tok < 1 || (act != 0 && act != 3) || !(act_scale > 0.f) || hd_true < 0 || hd_true > C / heads) return -2;
   switch (C / heads) {
-    case 64: return launch_attn_x2_hd<64>(act, axis, qkv, out, n_seq, map, C, heads, act_scale, st);
-    case 32: return launch_attn_x2_hd<32>(act, axis, qkv, out, n_seq, map, C, heads, act_scale, st);
-    case 16: return launch_attn_x2_hd<16>(act, axis, qkv, out, n_seq, map, C, heads, act_scale, st);
+    case 64: return launch_attn_x2_hd<64>(act, axis, qkv, out, n_seq, map, C, heads, act_scale, st, hd_true);
+    case 32: return launch_attn_x2_hd<32>(act, axis, qkv, out, n_seq, map, C, heads, act_scale, st, hd_true);
+    case 16: return launch_attn_x2_hd<16>(act, axis, qkv, out, n_seq, map, C, heads, act_scale, st, hd_true);
   }
   return -2;
 }

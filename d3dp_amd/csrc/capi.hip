@@ -44,7 +44,8 @@ const char* kClassNames[D3DP_PROFILE_CLASSES] = {"gemm_qkv", "gemm_proj", "gemm_
 
 // The environment switches of a context, read once at d3dp_create: the cross-check implementations, the training step's
 // scheduling switches and the measurement switches of the experiment kernels.  `width_inst`: the width is one the matrix-core
-// kernels are instantiated for (d3dp_create).  D3DP_OK, or the refusal (the caller deletes the context).
+// kernels are instantiated for, or one the split-fp16 implementation takes with padded heads under D3DP_EXACT_IMPL=f16x2
+// (d3dp_create).  D3DP_OK, or the refusal (the caller deletes the context).
 // (D3DP_TRAIN_ATTN_BWD alone is read per call, in train.hip: tests flip it between steps.)
 int read_switches(d3dp_ctx* c, bool width_inst) {
   const d3dp_cfg& g = c->cfg;
@@ -151,7 +152,28 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   // train_g.hip and the VALU attention backward with a run-time head dim.  FAST contexts exist for the instantiated widths only.
   const bool width_inst = (g.channels == 64 || g.channels == 128 || g.channels == 256 || g.channels == 512) &&
                           (hd == 8 || hd == 16 || hd == 32 || hd == 64) && g.hidden >= 64 && g.hidden % 64 == 0;
-  if (!width_inst) {
+  // D3DP_EXACT_IMPL=f16x2 (opt-in): an EXACT context at channels in {192, 320, 384, 448} runs the split-fp16 implementation with
+  // its head dim padded to 32 / 64 inside the packed weights (ctx.h hdp).  At an instantiated width the switch names the default;
+  // anywhere else it cannot be honoured and is refused HERE, before the device is looked for -- never ignored.
+  int hdp = 0;
+  {
+    const char* xi = getenv("D3DP_EXACT_IMPL");
+    if (xi && !strcmp(xi, "f16x2") && !width_inst) {
+      const bool shape = (g.channels == 192 || g.channels == 320 || g.channels == 384 || g.channels == 448) && hd % 8 == 0 &&
+                         hd <= 64 && g.hidden >= 64 && g.hidden % 64 == 0;
+      if (!shape || g.mode != D3DP_MODE_EXACT)
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_EXACT_IMPL=f16x2 outside the instantiated widths exists for D3DP_MODE_EXACT contexts with channels in "
+                                  "{192,320,384,448}, head dim a multiple of 8 up to 64 and hidden a multiple of 64; channels=%d heads=%d "
+                                  "hidden=%d mode=%d is not one (unset the switch: such a context runs the fp32 implementation)",
+                    g.channels, g.heads, g.hidden, g.mode);
+      const char* lr = getenv("D3DP_LONG_ATTN");
+      if (lr && !strcmp(lr, "rows"))
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_LONG_ATTN=rows with D3DP_EXACT_IMPL=f16x2 at channels=%d: the run-time-head-dim row attention has no "
+                                  "split-fp16 output form", g.channels);
+      hdp = hd <= 32 ? 32 : 64;
+    }
+  }
+  if (!width_inst && !hdp) {
     if (g.mode == D3DP_MODE_FAST)
       return d3dp_fail(D3DP_ENOTSUP, "channels=%d heads=%d hidden=%d: FAST contexts exist for channels in {64,128,256,512} with head dim in "
                                 "{8,16,32,64} and hidden a multiple of 64; other widths run in D3DP_MODE_EXACT / D3DP_MODE_TRAIN (fp32 implementation)",
@@ -177,7 +199,8 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   d3dp_ctx* c = new d3dp_ctx();
   c->cfg = g;
   c->fast_f16 = c->fast16() ? 1 : (c->fast() ? D3DP_FAST_F16 : 0);   // (FAST16: until d3dp_set_weights has seen the weights)
-  if (const int rc = read_switches(c, width_inst); rc != D3DP_OK) {
+  c->hdp = hdp;
+  if (const int rc = read_switches(c, width_inst || hdp != 0); rc != D3DP_OK) {
     delete c;
     return rc;
   }

@@ -7,6 +7,9 @@
 //   bufB [Tc, 3C]  act   qkv (EXACT: the packed rows of the split-fp16 attention kernels); reused as the [Tc, hidden] MLP hidden
 //   y1,y [Tc, C]   act   proj / fc2 outputs that the next row kernel adds to x: FAST modes and EXACT cross-checks.  EXACT split-fp16
 //                        adds them in the proj / fc2 epilogues (x += ...) and leaves both regions unused
+// A padded-head context (D3DP_EXACT_IMPL=f16x2 at channels 192 / 320 / 384 / 448, ctx.h hdp): qkv rows hold 3 Cp columns and the
+// attention output Cp = heads x hdp, so bufA holds max(C, Cp) columns (LayerNorm rows at pitch 2 C, attention output rows at pitch
+// 2 Cp fp16) and bufB max(3 Cp, hidden).
 // The reference keeps two physical layouts and transposes between them 16 times per call (mixste.py:244,270,274); here spatial
 // and temporal attention both index the single layout by stride.
 #include "ctx.h"
@@ -50,15 +53,15 @@ struct InferLayout {
   size_t temb, x, y1, y, bufA, bufB, lnst, ln_rowstat, nstat, total;
   InferLayout(const d3dp_ctx* c, int B, int H) {
     const d3dp_cfg& g = c->cfg;
-    const size_t Tc = (size_t)std::min(c->chunk(), B * H) * c->seq_pitch(), C = g.channels;
+    const size_t Tc = (size_t)std::min(c->chunk(), B * H) * c->seq_pitch(), C = g.channels, Cp = c->cp();   // (Cp = C without padded heads)
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
     temb = take((size_t)B * C * 4);
     x = take(Tc * C * 4);
     y1 = take(Tc * C * c->y_size());
     y = take(Tc * C * c->y_size());
-    bufA = take(Tc * C * c->act_size());
-    bufB = take(Tc * (size_t)std::max(3 * g.channels, g.hidden) * c->wide_size());   // (qkv fp32 = 12C; hidden planes <= 12C)
+    bufA = take(Tc * std::max(C, Cp) * c->act_size());
+    bufB = take(Tc * std::max(3 * Cp, (size_t)g.hidden) * c->wide_size());   // (qkv fp32 = 12C; hidden planes <= 12C)
     lnst = take(c->fold_ln() ? Tc * ((C + 63) / 64) * 8 : 0);
     ln_rowstat = take(c->fold_ln() ? (Tc + 256) * 8 : 0);
     nstat = take(c->defer_norm() ? (Tc + 256) * 8 : 0);
@@ -94,10 +97,11 @@ int attention(d3dp_ctx* c, int axis, const void* qkv, void* out, int n_bh, float
   const d3dp_cfg& g = c->cfg;
   Scope s(c, axis == 0 ? P_ATTN_S : P_ATTN_T, st);
   // (seq_pitch() exceeds F J on the X2 route alone: every other kernel sees the unpadded map)
-  const int n = axis == 0 ? n_bh * g.frames : n_bh * g.joints, act = c->act(), C = g.channels;
+  // (a padded-head context: rows of attn_cols() = heads x hdp columns, the true head dim in the softmax exponent)
+  const int n = axis == 0 ? n_bh * g.frames : n_bh * g.joints, act = c->act(), C = c->attn_cols();
   const SeqMap map = axis == 0 ? spatial_map(g.frames, g.joints, c->seq_pitch()) : temporal_map(g.frames, g.joints, c->seq_pitch());
   switch (c->route(axis)) {
-    case AttnRoute::X2: return d3dp_launch_attn_x2(3, axis, qkv, out, n, map, C, g.heads, s_kv, st);
+    case AttnRoute::X2: return d3dp_launch_attn_x2(3, axis, qkv, out, n, map, C, g.heads, s_kv, st, g.channels / g.heads);
     case AttnRoute::FAST_SPATIAL: return d3dp_launch_attn_spatial_bf16(qkv, out, n, map, C, g.heads, st, c->fast_f16);
     case AttnRoute::FAST_WHOLE_SEQ: return d3dp_launch_attn_temporal_bf16(qkv, out, n, map, C, g.heads, st, c->fast_f16);
     case AttnRoute::F32_TEMPORAL: return d3dp_launch_attn_temporal_f32(act, qkv, out, n, map, C, g.heads, st);
@@ -116,25 +120,25 @@ int attention(d3dp_ctx* c, int axis, const void* qkv, void* out, int n_bh, float
 int run_block(d3dp_ctx* c, const BlockDev& w, int axis, float* x, void* y1, void* y, void* bufA, void* bufB, float* slices,
               float* rowstat, int n_bh, hipStream_t st, float* nstat = nullptr) {
   const d3dp_cfg& g = c->cfg;
-  const int Tc = n_bh * c->seq_pitch(), C = g.channels;
+  const int Tc = n_bh * c->seq_pitch(), C = g.channels, Ca = c->attn_cols();   // Ca: columns of q / k / v and of the attention output
   // (s_kv / s_h differ from kActScale only in EXACT f16x2 contexts whose weights asked for it, and s_kv only with the x2
   //  attention kernels: the other attention kernels write their output planes at kActScale)
   const float s_o = c->x2_attn() ? w.s_kv : kActScale;
-  LAUNCH_TRY(linear(c, P_QKV, EPI_BIAS, 0, bufA, w.qkv_w, w.qkv_u, w.qkv_b, bufB, Tc, 3 * C, C, st, nullptr, nullptr, kActScale, s_o));
+  LAUNCH_TRY(linear(c, P_QKV, EPI_BIAS, 0, bufA, w.qkv_w, w.qkv_u, w.qkv_b, bufB, Tc, 3 * Ca, C, st, nullptr, nullptr, kActScale, s_o));
   LAUNCH_TRY(attention(c, axis, bufB, bufA, n_bh, s_o, st));
   const bool fold = c->fold_resid();   // EXACT split-fp16 Linears: x += proj / fc2 inside their epilogues
   if (c->fold_ln()) {
     // norm2 folded into proj's epilogue (statistics, un-normalised operand -> y1) and fc1's (normalisation): no row kernel
     // (slices [Tc][C / 64][2], rowstat [Tc + 256][2]: InferLayout)
-    LAUNCH_TRY(linear(c, P_PROJ, EPI_RESID_LN, 0, bufA, w.proj_w, w.proj_u, w.proj_b, x, Tc, C, C, st, y1, slices, s_o));
+    LAUNCH_TRY(linear(c, P_PROJ, EPI_RESID_LN, 0, bufA, w.proj_w, w.proj_u, w.proj_b, x, Tc, C, Ca, st, y1, slices, s_o));
     {
       Scope s(c, P_LN, st);
       d3dp_launch_ln_combine(slices, rowstat, Tc, C, g.eps_block, st);
     }
     LAUNCH_TRY(linear(c, P_FC1, EPI_GELU_LN, 0, y1, w.fc1_w, w.fc1_u, w.fc1_c12, bufB, Tc, g.hidden, C, st, bufB, rowstat, kActScale, w.s_h));
   } else {
-  if (nstat) LAUNCH_TRY(linear(c, P_PROJ, EPI_RESID_NORM, 0, bufA, w.proj_w, w.proj_u, w.proj_bgb, x, Tc, C, C, st, nullptr, nstat, s_o));
-  else LAUNCH_TRY(linear(c, P_PROJ, fold ? EPI_RESID : EPI_BIAS, 0, bufA, w.proj_w, w.proj_u, w.proj_b, fold ? (void*)x : y1, Tc, C, C, st, nullptr, nullptr, s_o));
+  if (nstat) LAUNCH_TRY(linear(c, P_PROJ, EPI_RESID_NORM, 0, bufA, w.proj_w, w.proj_u, w.proj_bgb, x, Tc, C, Ca, st, nullptr, nstat, s_o));
+  else LAUNCH_TRY(linear(c, P_PROJ, fold ? EPI_RESID : EPI_BIAS, 0, bufA, w.proj_w, w.proj_u, w.proj_b, fold ? (void*)x : y1, Tc, C, Ca, st, nullptr, nullptr, s_o));
   {
     Scope s(c, P_LN, st);      // xn = LN2(x + y1); x itself stays untouched (the caller's norm pair adds y1 and y)
     LAUNCH_TRY(d3dp_launch_ln(c->act(), x, fold ? nullptr : y1, 0, w.n2w, w.n2b, g.eps_block, bufA, Tc, C, st));

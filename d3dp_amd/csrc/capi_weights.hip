@@ -15,6 +15,37 @@ __global__ void to_bf16_kernel(const float* __restrict__ s, E* __restrict__ d, s
   for (; i < n; i += stride) d[i] = (E)s[i];
 }
 
+// ---- padded heads (ctx.h hdp: D3DP_EXACT_IMPL=f16x2 at channels 192 / 320 / 384 / 448) -------------------------------------------
+// A head of hd columns becomes hdp = 32 or 64 columns, the new ones zero, INSIDE the packed weights: index h hdp + d of the
+// padded axis holds index h hd + d of the source for d < hd.  pad_rows: the padded axis is the ROW axis, in sections of
+// heads x hdp rows (the qkv matrix, 3 sections: row s Cp + h hdp + d <- source row s C + h hd + d); otherwise the column axis (the
+// proj matrix).  The split is d3dp_launch_split2's: src x scale -> hi / lo (split2h_scaled) in the h2i layout of a [rows][cols]
+// matrix (cols % 32 == 0); a pad element is the split of 0, two exact zeros.  One thread per destination element.
+__device__ __forceinline__ int unpad_index(int i, int hd, int hdp, int heads) {   // padded index -> source index, or -1
+  const int per = heads * hdp, s = i / per, r = i - s * per, h = r / hdp, d = r - h * hdp;
+  return d < hd ? s * heads * hd + h * hd + d : -1;
+}
+__global__ void split2h_pad_kernel(const float* __restrict__ src, f16* __restrict__ dst, int rows, int cols, int src_cols,
+                                   int pad_rows, int hd, int hdp, int heads, float scale) {
+  const size_t n = (size_t)rows * cols, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int r = (int)(i / cols), c = (int)(i - (size_t)r * cols);
+    const int sr = pad_rows ? unpad_index(r, hd, hdp, heads) : r, sc = pad_rows ? c : unpad_index(c, hd, hdp, heads);
+    const float v = sr >= 0 && sc >= 0 ? src[(size_t)sr * src_cols + sc] : 0.f;
+    f16 a, b;
+    split2h_scaled(v * scale, a, b);
+    f16* d = dst + (size_t)r * 2 * cols + h2i_col(c);
+    d[0] = a; d[kH2iLo] = b;
+  }
+}
+// the qkv bias with the same row map: dst[i] = src[unpad(i)] or 0
+__global__ void pad_bias_kernel(const float* __restrict__ src, float* __restrict__ dst, int n, int hd, int hdp, int heads) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int si = unpad_index(i, hd, hdp, heads);
+  dst[i] = si >= 0 ? src[si] : 0.f;
+}
+
 }  // namespace
 
 void d3dp_launch_to_bf16(const float* s, void* d, size_t n, hipStream_t st, int f16) {
@@ -111,7 +142,7 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
   // item 5) and the representation error stays <= max(2^-22 |x|, 2^-25 / scale) <= 2^-40 x bound in absolute terms, far below
   // the fp32 rounding of the sums these operands enter.  A LayerNorm whose own output bound reaches 4094 (|gamma| ~ 180),
   // or an out-of-range q/k/v bound where the split-fp16 attention kernels do not apply, switches the whole context to the
-  // six-pass split-bf16 implementation, which has fp32's exponent range.
+  // six-pass split-bf16 implementation, which has fp32's exponent range (a padded-head context: to the fp32 implementation).
   c->range_bound = 0.f;
   c->impl_fallback = false;
   c->plan_total = -1;            // the pass plan depends on the implementation chosen below (x2-tuned or uniform passes)
@@ -162,7 +193,9 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
     }
     c->range_bound = std::min(worst, 3.0e38f);
     if (fallback) {
-      c->exact_impl = 1;                                 // split-bf16, six passes: no range limit
+      // split-bf16, six passes: no range limit.  A padded-head context (a width bf16x3 does not exist at) moves to the fp32
+      // implementation instead: what it would run without its switch.
+      c->exact_impl = c->hdp ? 2 : 1;
       c->impl_fallback = true;
       std::fill(blk_scale.begin(), blk_scale.end(), kActScale);
     }
@@ -220,10 +253,16 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
   // ---- arena layout ----
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-  struct Item { const void* src; size_t n; bool mat; size_t off; };
+  // (pad: 0 = a flat copy / split of n elements; a padded-head context running the split-fp16 implementation packs 1 = the qkv
+  //  matrix as [3 Cp][C], 2 = the proj matrix as [C][Cp], 3 = the qkv bias as [3 Cp] -- n_dst elements from the n of the source)
+  struct Item { const void* src; size_t n; bool mat; size_t off; int pad; size_t n_dst; };
   std::vector<Item> items;
-  auto add = [&](const void* src, size_t n, bool mat) {
-    items.push_back({src, n, mat, take(n * (mat ? ws : 4))});
+  const bool padded = c->x2() && c->hdp != 0;
+  const size_t Cp = padded ? (size_t)c->cp() : C;
+  auto add = [&](const void* src, size_t n, bool mat, int pad = 0, size_t n_dst = 0) {
+    if (!padded) pad = 0;
+    if (!pad) n_dst = n;
+    items.push_back({src, n, mat, take(n_dst * (mat ? ws : 4)), pad, n_dst});
     return items.size() - 1;
   };
   const size_t i_spos = add(w->spatial_pos, J * C, false), i_tpos = add(w->temporal_pos, F * C, false);
@@ -246,8 +285,8 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
       const d3dp_block_weights& b = (kind == 0 ? w->ste : w->tte)[d];
       BI bi;
       bi.v[0] = add(b.norm1_w, C, false); bi.v[1] = add(b.norm1_b, C, false);
-      bi.v[2] = add(b.qkv_w, 3 * C * C, true); bi.v[3] = add(b.qkv_b, 3 * C, false);
-      bi.v[4] = add(b.proj_w, C * C, true); bi.v[5] = add(b.proj_b, C, false);
+      bi.v[2] = add(b.qkv_w, 3 * C * C, true, 1, 3 * Cp * C); bi.v[3] = add(b.qkv_b, 3 * C, false, 3, 3 * Cp);
+      bi.v[4] = add(b.proj_w, C * C, true, 2, C * Cp); bi.v[5] = add(b.proj_b, C, false);
       // defer_norm: gamma / beta of the shared norm in front of the block right behind proj's bias -- one array [b | gamma | beta]
       // (C floats are whole 256-byte units at the widths of the split-fp16 kernels, so the three items lie back to back)
       bi.bgb = c->defer_norm() && (C * 4) % kAlign == 0;
@@ -301,9 +340,17 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
       unscale[i] = ldexpf(1.f, e - 14);
     }
   }
+  const int hd = g.channels / g.heads;
   for (size_t i = 0; i < items.size(); ++i) {
     auto& it = items[i];
-    if (it.mat && c->fast()) d3dp_launch_to_bf16((const float*)it.src, c->arena + it.off, it.n, st, c->fast_f16);
+    if (it.pad == 3)
+      hipLaunchKernelGGL(pad_bias_kernel, dim3(((unsigned)it.n_dst + 255) / 256), dim3(256), 0, st, (const float*)it.src,
+                         (float*)(c->arena + it.off), (int)it.n_dst, hd, c->hdp, g.heads);
+    else if (it.pad)     // (the same split arithmetic and the same per-matrix scale, from the absmax of the caller's unpadded matrix)
+      hipLaunchKernelGGL(split2h_pad_kernel, dim3((unsigned)std::min<size_t>((it.n_dst + 255) / 256, 4096)), dim3(256), 0, st,
+                         (const float*)it.src, (f16*)(c->arena + it.off), it.pad == 1 ? 3 * (int)Cp : (int)C,
+                         it.pad == 1 ? (int)C : (int)Cp, (int)C, it.pad == 1 ? 1 : 0, hd, c->hdp, g.heads, 1.0f / unscale[i]);
+    else if (it.mat && c->fast()) d3dp_launch_to_bf16((const float*)it.src, c->arena + it.off, it.n, st, c->fast_f16);
     else if (it.mat && c->x3()) d3dp_launch_split3((const float*)it.src, c->arena + it.off, it.n, st);
     else if (it.mat && c->x2()) d3dp_launch_split2((const float*)it.src, c->arena + it.off, it.n, 1.0f / unscale[i], st);
     else HIP_TRY(hipMemcpyAsync(c->arena + it.off, it.src, it.n * 4, hipMemcpyDeviceToDevice, st));

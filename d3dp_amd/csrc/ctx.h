@@ -89,7 +89,7 @@ struct d3dp_ctx {
   // and =f32 the plain fp32-MFMA kernels (bitwise an fp32 fmaf chain) -- both kept as cross-checks.
   int exact_impl = 0;   // 0 = f16x2, 1 = bf16x3, 2 = f32
   int exact_impl_req = 0;        // what D3DP_EXACT_IMPL asked for; d3dp_set_weights moves an f16x2 context to bf16x3 when a
-  bool impl_fallback = false;    // LayerNorm's own output bound leaves the split-fp16 range (see there)
+  bool impl_fallback = false;    // LayerNorm's own output bound leaves the split-fp16 range (see there; with padded heads: to f32)
   bool train() const { return cfg.mode == D3DP_MODE_TRAIN; }
   bool exact() const { return !fast() && !train(); }
   bool x2() const { return exact() && exact_impl == 0; }
@@ -98,8 +98,18 @@ struct d3dp_ctx {
   // the range fallback of d3dp_set_weights, which lowers s_kv instead of leaving the split-fp16 implementation wherever these
   // kernels run.  long_rows: D3DP_LONG_ATTN=rows, the row-kernel cross-check (read in d3dp_create).
   bool long_rows = false;
+  // D3DP_EXACT_IMPL=f16x2 at channels in {192, 320, 384, 448} (d3dp_create): the split-fp16 implementation at a width outside the
+  // instantiated set.  The head dim is PADDED inside the packed weights to hdp = 32 or 64 (capi_weights.hip): the qkv Linear writes
+  // packed rows of cp() = heads x hdp columns whose pad columns are exact zeros, the attention kernels run their head dim 32 / 64
+  // instantiations on them (the softmax exponent takes the true head dim) and proj contracts over cp() columns against zero weight
+  // columns.  The residual stream, the LayerNorms and the MLP keep the true width.  0: no padding (every other context).
+  int hdp = 0;
+  int cp() const { return hdp ? cfg.heads * hdp : cfg.channels; }
+  // (the columns of a packed qkv third / of the attention output while the split-fp16 implementation runs; the range fallback of
+  //  a padded context is the fp32 implementation, which knows no padding)
+  int attn_cols() const { return hdp && exact_impl == 0 ? cp() : cfg.channels; }
   AttnRoute route(int axis) const {
-    return attn_route(cfg.mode, exact_impl, cfg.channels / cfg.heads, cfg.frames, cfg.joints, long_rows, axis);
+    return attn_route(cfg.mode, exact_impl, attn_cols() / cfg.heads, cfg.frames, cfg.joints, long_rows, axis);
   }
   bool x2_attn() const { return route(0) == AttnRoute::X2; }
   // proj / fc2 add into the residual stream in their epilogue (x += ...), so the row kernels read x alone
@@ -120,7 +130,8 @@ struct d3dp_ctx {
   // result bit stays.  The boundary that adds Temporal_pos (after STE block 0) keeps the in-place form.  D3DP_DEFER_NORM=0 keeps it
   // everywhere: the cross-check.  Plain-kernel dataflow only (proj's k-loop must cover the statistics' double buffer: C >= 96).
   bool defer_norm() const {
-    return fold_resid() && defer && !fold_ln() && skew_d == 0 && pingpong == 0 && cfg.channels >= 96 && 3 * cfg.channels <= 2048;
+    // (ln2_defer_kernel is width-templated: a padded-head context keeps the in-place norm pair, as width 64 does)
+    return fold_resid() && defer && !fold_ln() && skew_d == 0 && pingpong == 0 && cfg.channels >= 96 && 3 * cfg.channels <= 2048 && !hdp;
   }
   bool defer = true;
   // The EXACT qkv / fc1 Linears run the SKEWED schedule of gemm_x2.hip (a tile's epilogue spread under the k-loop of the
@@ -185,9 +196,10 @@ struct d3dp_ctx {
     // per Linear (qkv, proj, fc1, fc2): column strips, k-depth, and whether it runs the skewed schedule -- there a
     // workgroup owns the row tiles of one row group inside one strip (ceil(R / Q) tiles, Q = n_cu / strips row groups)
     // plus the flush of 3 D k-steps; in the plain schedule tiles are dealt round robin (ceil(R strips / n_cu) rounds)
-    const long tn[4] = {(3 * cfg.channels + 127) / 128, (cfg.channels + 127) / 128, (cfg.hidden + 127) / 128,
+    // (a padded-head context: qkv has 3 cp() columns and proj a k-depth of cp())
+    const long tn[4] = {(3 * attn_cols() + 127) / 128, (cfg.channels + 127) / 128, (cfg.hidden + 127) / 128,
                         (cfg.channels + 127) / 128};
-    const long kd[4] = {cfg.channels, cfg.channels, cfg.channels, cfg.hidden};
+    const long kd[4] = {cfg.channels, attn_cols(), cfg.channels, cfg.hidden};
     const bool sk[4] = {skew(), false, skew(), false};
     std::vector<double> cost(cap + 1, 0.0);
     for (int n = 1; n <= cap; ++n) {

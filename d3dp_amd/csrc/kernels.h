@@ -184,8 +184,10 @@ int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap 
 // with EPI_QKV_PACK or from fp32 rows by d3dp_launch_qkv_pack_x2
 // `act_scale`: the power of two the k / v planes were written at (q and, for plane output, o use the same)
 // act 0: fp32 rows out, 3: the two fp16 planes of the proj Linear's operand.  Any SeqMap, up to 1024 tokens per sequence.
+// hd_true: the head dim of the softmax exponent (hd_true^-0.5) where it is smaller than C / heads -- packed rows whose heads were
+// padded with zero columns to a head dim the kernels are instantiated for (0: C / heads itself)
 int d3dp_launch_attn_x2(int act, int axis, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
-                        float act_scale, hipStream_t st);
+                        float act_scale, hipStream_t st, int hd_true = 0);
 void d3dp_launch_qkv_pack_x2(const float* src, void* dst, size_t T, int C, float act_scale, hipStream_t st);
 
 // ---- pointwise.hip -----------------------------------------------------------------------------

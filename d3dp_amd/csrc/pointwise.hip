@@ -467,7 +467,7 @@ __global__ __launch_bounds__(256) void time_mlp_kernel(const int64_t* __restrict
 // split-fp16 matrix-core kernels.  Other widths run the fp32 implementation (capi.hip read_switches: exact_impl 2 -- fp32-MFMA Linears,
 // fp32 row attention) through the four kernels below: the same arithmetic in the same order per row (two-pass statistics,
 // 1 / C as a multiplied reciprocal, fma with gamma / beta), the width a run-time argument, a lane's NVM slots masked behind it.
-// fp32 activations only (the FAST and split-operand forms exist for the instantiated widths).
+// fp32 activations (the FAST and split-bf16 forms exist for the instantiated widths; split-fp16 rows out: the *_h kernels below).
 // ------------------------------------------------------------------------------------------------
 template <int NVM> struct RowG {
   static __device__ __forceinline__ void load(const float* p, int C, int lane, float* v) {
@@ -629,6 +629,177 @@ __global__ __launch_bounds__(256) void head_g_kernel(const float* __restrict__ x
   if (lane < 3 && fj < FJ) out[((size_t)(tok / SP) * FJ + fj) * 3 + lane] = lane == 0 ? acc[0] : (lane == 1 ? acc[1] : acc[2]);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Run-time width with split-fp16 operand rows out (act 3): the LayerNorm kernels of an EXACT context that runs the split-fp16
+// implementation at a width outside the instantiated set (D3DP_EXACT_IMPL=f16x2 at channels 192 / 320 / 384 / 448, ctx.h hdp).
+// C % 32 == 0 (whole h2i blocks), C <= 512.  A lane owns the 8 CONSECUTIVE columns 8 lane .. 8 lane + 7 (lanes >= C / 8 idle): its
+// fp32 loads are two 16-byte pieces of 32 contiguous bytes, and its 8 hi and 8 lo halves leave as ONE 16-byte store each into
+// h2i_col(8 lane) / + kH2iLo -- four neighbouring lanes fill the 64-byte hi slot of a 32-column block, the same four its lo slot,
+// i.e. whole 128-byte lines per wave-instruction pair (the stride-64 layout of RowG would give 2-byte stores).  The arithmetic per
+// row is that of the kernels above: two-pass fp32 statistics, 1 / C as a multiplied reciprocal, fma with gamma / beta, and the split
+// of the TRUE-scale value with the power-of-two plane scale applied inside it (split2h: y x 16 is exact).
+// ------------------------------------------------------------------------------------------------
+struct RowH {
+  static constexpr int NV = 8;
+  static __device__ __forceinline__ void load(const float* p, int C, int lane, float* v) {
+    if (8 * lane < C) load8(p + 8 * lane, v);
+    else {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) v[i] = 0.f;
+    }
+  }
+  // (the fp32 residual stream: read or written once here and not touched again until kernels later, see Row<C>::load_nt)
+  static __device__ __forceinline__ void load_nt(const float* p, int C, int lane, float* v) {
+    if (8 * lane < C) {
+      const f32x4 a = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + 8 * lane));
+      const f32x4 b = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + 8 * lane + 4));
+      v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+    } else {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) v[i] = 0.f;
+    }
+  }
+  static __device__ __forceinline__ void store(float* p, int C, int lane, const float* v) {
+    if (8 * lane < C) store8(p + 8 * lane, v);
+  }
+  // `row` = start of the token's h2i row of 2 C fp16
+  static __device__ __forceinline__ void store2h(f16* row, int C, int lane, const float* v) {
+    f16x8 a, b;
+#pragma unroll
+    for (int e = 0; e < NV; ++e) { f16 h, l; split2h(v[e], h, l); a[e] = h; b[e] = l; }
+    if (8 * lane < C) {
+      f16* d = row + h2i_col(8 * lane);
+      *reinterpret_cast<f16x8*>(d) = a;
+      *reinterpret_cast<f16x8*>(d + kH2iLo) = b;
+    }
+  }
+  static __device__ __forceinline__ void norm(const float* v, const float* wv, const float* bv, float eps, int C, int lane, float* y) {
+    const float rc = 1.0f / (float)C;
+    const bool live = 8 * lane < C;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) s += v[i];                        // (idle lanes hold 0)
+    const float mean = wave_sum(s) * rc;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) { const float d = live ? v[i] - mean : 0.f; q = fmaf(d, d, q); }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) * rc + eps);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) y[i] = live ? fmaf((v[i] - mean) * rstd, wv[i], bv[i]) : 0.f;
+  }
+};
+
+__global__ __launch_bounds__(256) void ln_h_kernel(float* __restrict__ x, const float* __restrict__ yadd, const float* __restrict__ w,
+                                                   const float* __restrict__ b, float eps, f16* __restrict__ xn, int T, int C,
+                                                   int write_x) {
+  using R = RowH;
+  const int lane = threadIdx.x & 63;
+  const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (tok >= T) return;
+  float v[R::NV], y[R::NV], wv[R::NV], bv[R::NV];
+  R::load_nt(x + (size_t)tok * C, C, lane, v);
+  if (yadd != nullptr) {
+    R::load_nt(yadd + (size_t)tok * C, C, lane, y);
+#pragma unroll
+    for (int i = 0; i < R::NV; ++i) v[i] += y[i];
+    if (write_x) R::store(x + (size_t)tok * C, C, lane, v);
+  }
+  R::load(w, C, lane, wv);
+  R::load(b, C, lane, bv);
+  R::norm(v, wv, bv, eps, C, lane, y);
+  R::store2h(xn + (size_t)tok * 2 * C, C, lane, y);
+}
+
+__global__ __launch_bounds__(256) void ln2_h_kernel(float* __restrict__ x, const float* __restrict__ yadd0, const float* __restrict__ yadd,
+                                                    const float* __restrict__ wa, const float* __restrict__ ba,
+                                                    const float* __restrict__ pos, const float* __restrict__ wb,
+                                                    const float* __restrict__ bb, float eps, f16* __restrict__ xn, int T, int C,
+                                                    int F, int J, int SP) {
+  using R = RowH;
+  const int lane = threadIdx.x & 63;
+  const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (tok >= T) return;
+  float v[R::NV], y[R::NV], z[R::NV], wv[R::NV], bv[R::NV];
+  R::load_nt(x + (size_t)tok * C, C, lane, v);
+  if (yadd0 != nullptr) {
+    R::load_nt(yadd0 + (size_t)tok * C, C, lane, y);
+#pragma unroll
+    for (int i = 0; i < R::NV; ++i) v[i] += y[i];
+  }
+  if (yadd != nullptr) {
+    R::load_nt(yadd + (size_t)tok * C, C, lane, y);
+#pragma unroll
+    for (int i = 0; i < R::NV; ++i) v[i] += y[i];
+  }
+  R::load(wa, C, lane, wv);
+  R::load(ba, C, lane, bv);
+  R::norm(v, wv, bv, eps, C, lane, y);
+  if (pos != nullptr) {
+    const int f = min((tok % SP) / J, F - 1);
+    float pv[R::NV];
+    R::load(pos + (size_t)f * C, C, lane, pv);
+#pragma unroll
+    for (int i = 0; i < R::NV; ++i) y[i] += pv[i];
+  }
+  R::store(x + (size_t)tok * C, C, lane, y);
+  R::load(wb, C, lane, wv);
+  R::load(bb, C, lane, bv);
+  R::norm(y, wv, bv, eps, C, lane, z);
+  R::store2h(xn + (size_t)tok * 2 * C, C, lane, z);
+}
+
+// kRowTokens tokens per wave, the weights of a lane's 8 columns held in registers across them (as embed_ln_kernel)
+__global__ __launch_bounds__(256) void embed_ln_h_kernel(const float* __restrict__ x2d, const float* __restrict__ x3d,
+                                                         const float* __restrict__ temb, const float* __restrict__ ew,
+                                                         const float* __restrict__ eb, const float* __restrict__ spos,
+                                                         const float* __restrict__ lnw, const float* __restrict__ lnb, float eps,
+                                                         float* __restrict__ x, f16* __restrict__ xn, int seq0, int n_seq, int H,
+                                                         int F, int J, int SP, int C) {
+  using R = RowH;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int FJ = F * J, T = n_seq * SP;
+  const bool live = 8 * lane < C;
+  float w5[R::NV][5], ebv[R::NV], lw[R::NV], lb[R::NV];
+#pragma unroll
+  for (int i = 0; i < R::NV; ++i) {
+#pragma unroll
+    for (int k = 0; k < 5; ++k) w5[i][k] = live ? ew[(8 * lane + i) * 5 + k] : 0.f;
+  }
+  R::load(eb, C, lane, ebv);
+  R::load(lnw, C, lane, lw);
+  R::load(lnb, C, lane, lb);
+  for (int it = 0; it < kRowTokens; ++it) {
+    const int tl = (blockIdx.x * kRowTokens + it) * 4 + wave;    // chunk-local row: sequence tl / SP, token tl % SP
+    if (tl >= T) break;
+    const bool pad = (tl % SP) >= FJ;                            // (pad rows: finite filler, see embed_ln_kernel)
+    const int seq = seq0 + tl / SP, fj = pad ? 0 : tl % SP, nj = fj % J;
+    const int b = seq / H;
+    const float* p2 = x2d + ((size_t)b * FJ + fj) * 2;
+    const float* p3 = x3d + ((size_t)seq * FJ + fj) * 3;
+    float in5[5] = {p2[0], p2[1], p3[0], p3[1], p3[2]};
+    if (pad) { in5[0] = in5[1] = in5[2] = in5[3] = in5[4] = 0.f; }
+    float v[R::NV], y[R::NV], sp[R::NV], tb[R::NV];
+    R::load(spos + (size_t)nj * C, C, lane, sp);
+    R::load(temb + (size_t)b * C, C, lane, tb);
+#pragma unroll
+    for (int i = 0; i < R::NV; ++i) {
+      float a = 0.f;
+#pragma unroll
+      for (int k = 0; k < 5; ++k) a = fmaf(in5[k], w5[i][k], a);
+      a += ebv[i];
+      a += sp[i];
+      a += tb[i];
+      v[i] = a;                                                  // (idle lanes: every term is 0)
+    }
+    R::store(x + (size_t)tl * C, C, lane, v);
+    R::norm(v, lw, lb, eps, C, lane, y);
+    R::store2h(xn + (size_t)tl * 2 * C, C, lane, y);
+  }
+}
+// widths the three kernels above take
+__host__ inline bool width_rowh(int C) { return C >= 32 && C <= 512 && C % 32 == 0; }
+
 // widths the instantiated kernels take; everything else goes through the *_g kernels (fp32 activations, C <= 1024)
 __host__ inline bool width_instantiated(int C) { return C == 64 || C == 128 || C == 256 || C == 512; }
 #define DISPATCH_G(C, ...)                                                  \
@@ -666,6 +837,10 @@ int d3dp_launch_embed_ln(int act_bf16, const float* x2d, const float* x3d, const
   dim3 g((T + 3) / 4), blk(256);
   const size_t plane = (size_t)T * C;
   if (!width_instantiated(C)) {
+    if (act_bf16 == 3 && width_rowh(C)) {
+      hipLaunchKernelGGL(embed_ln_h_kernel, dim3((T + 4 * kRowTokens - 1) / (4 * kRowTokens)), blk, 0, st, x2d, x3d, temb, ew, eb, spos, lnw, lnb, eps, x, (f16*)xn, seq0, n_seq, H, F, J, SP, C);
+      return 0;
+    }
     if (act_bf16 != 0) return -2;
     DISPATCH_G(C, hipLaunchKernelGGL((embed_ln_g_kernel<NVM>), g, blk, 0, st, x2d, x3d, temb, ew, eb, spos, lnw, lnb, eps, x, (float*)xn, seq0, n_seq, H, F, J, SP, C))
     return 0;
@@ -685,6 +860,10 @@ int d3dp_launch_ln(int act_bf16, float* x, const void* yadd, int write_x, const 
   dim3 g((T + 3) / 4), blk(256);
   const size_t plane = (size_t)T * C;
   if (!width_instantiated(C)) {
+    if (act_bf16 == 3 && width_rowh(C)) {
+      hipLaunchKernelGGL(ln_h_kernel, g, blk, 0, st, x, (const float*)yadd, w, b, eps, (f16*)xn, T, C, write_x);
+      return 0;
+    }
     if (act_bf16 != 0) return -2;
     DISPATCH_G(C, hipLaunchKernelGGL((ln_g_kernel<NVM>), g, blk, 0, st, x, (const float*)yadd, w, b, eps, (float*)xn, T, C, write_x))
     return 0;
@@ -704,6 +883,10 @@ int d3dp_launch_ln2(int act_bf16, float* x, const void* yadd0, const void* yadd,
   dim3 g((T + 3) / 4), blk(256);
   const size_t plane = (size_t)T * C;
   if (!width_instantiated(C)) {
+    if (act_bf16 == 3 && width_rowh(C)) {
+      hipLaunchKernelGGL(ln2_h_kernel, g, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, pos, wb, bb, eps, (f16*)xn, T, C, F, J, SP);
+      return 0;
+    }
     if (act_bf16 != 0) return -2;
     DISPATCH_G(C, hipLaunchKernelGGL((ln2_g_kernel<NVM>), g, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, pos, wb, bb, eps, (float*)xn, T, C, F, J, SP))
     return 0;

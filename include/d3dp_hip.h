@@ -70,7 +70,8 @@ enum {
   D3DP_MODE_EXACT = 0,   /* fp32-equivalent: Linears on split-fp16 operands (2 planes, 3 fp16-MFMA passes, fp32
                             accumulate), fp32 everything else: <= 1e-3 mm vs the reference.  Linear inputs must stay
                             below 65504 in magnitude.  (env D3DP_EXACT_IMPL=bf16x3 | f32: six-pass split-bf16 /
-                            plain fp32-MFMA Linears, kept as cross-checks)                                        */
+                            plain fp32-MFMA Linears, kept as cross-checks; =f16x2: the split-fp16 implementation,
+                            opt-in at channels 192 / 320 / 384 / 448, see d3dp_create)                            */
   D3DP_MODE_FAST = 1,    /* bf16 activations/weights into v_mfma_f32_16x16x32_bf16, fp32 accumulate/LN/softmax */
   D3DP_MODE_TRAIN = 2,   /* fp32 weights and activations; Linears (forward, dgrad, wgrad) on split-fp16 operands whose scales are
                             found on the device: required by d3dp_train_*; inference also works (fp32-MFMA Linears)          */
@@ -156,6 +157,18 @@ D3DP_API const char* d3dp_last_error(void);
  *                         (fp32-MFMA Linears, fp32 row attention, run-time-width row kernels; d3dp_exact_scales reports
  *                         implementation 2): the same 1e-3 mm tolerance at roughly a fifth of the throughput.  FAST and FAST16
  *                         contexts exist for the instantiated widths only.
+ *   channels in {192, 320, 384, 448} with head dim % 8 == 0 and <= 64 and hidden % 64 == 0, D3DP_MODE_EXACT, with
+ *                         D3DP_EXACT_IMPL=f16x2 in the environment of d3dp_create (OPT-IN: without the switch such a context
+ *                         launches the fp32 implementation above, bit for bit as before): the split-fp16 implementation of the
+ *                         instantiated widths (d3dp_exact_scales reports implementation 0).  The head dim is padded to 32 / 64
+ *                         inside the packed weights -- zero rows of the qkv matrix and bias, zero columns of proj -- so the
+ *                         matrix-core attention kernels run at head dim 32 / 64 with the true head dim in the softmax
+ *                         exponent; the LayerNorms run run-time-width row kernels that write split-fp16 rows.  Where the
+ *                         weights' proven range would move an instantiated width to bf16x3 (a LayerNorm output bound beyond
+ *                         the split range, non-finite weights) this context moves to the fp32 implementation.  At an
+ *                         instantiated width the value names the default.  With any other width, or a TRAIN / FAST / FAST16
+ *                         context of a non-instantiated width, or together with D3DP_LONG_ATTN=rows at these widths, the
+ *                         switch cannot be honoured: D3DP_ENOTSUP, decided before the device is looked for.
  * What a D3DP_MODE_TRAIN context takes, by the attention its training step runs:
  *   channels in {128, 256, 512} with head dim in {16, 32, 64} (`-cs 128 / 256 / 512` with 8 heads): Linears on split-fp16 operands and
  *                         the attention of both axes on the split-fp16 matrix-core kernels (train_attn.hip), which pass keys /
@@ -394,7 +407,8 @@ D3DP_API int d3dp_op_split3(const float* src, void* dst, size_t n, void* stream)
  * (lib/variants/libd3dp_variants.so; tests marked `variants`): here those flags, and the environment switches D3DP_X2_SKEW,
  * D3DP_X2_PP, D3DP_X2_WIDE, D3DP_SEQ_PAD, D3DP_FOLD_LN read by d3dp_create, fail with D3DP_ENOTSUP -- they are never ignored.
  * Cross-check switches the product library does honour (read in d3dp_create): D3DP_EXACT_IMPL=bf16x3|f32, D3DP_NO_FOLD=1
- * (other implementations of EXACT mode's Linears / residual adds, same tolerance), D3DP_DEFER_NORM=0 (the shared norm of every
+ * (other implementations of EXACT mode's Linears / residual adds, same tolerance; D3DP_EXACT_IMPL=f16x2 is the opt-in route of
+ * channels 192 / 320 / 384 / 448 described at d3dp_create), D3DP_DEFER_NORM=0 (the shared norm of every
  * block boundary applied in place by the norm pair instead of inside the next proj Linear: bit-identical), D3DP_TRAIN_IMPL=f32. */
 D3DP_API int d3dp_op_split2(const float* src, void* dst, size_t n, float scale, void* stream);
 D3DP_API int d3dp_op_linear_x2(int32_t epi, const void* A2, const void* W2, const float* bias, float w_scale, void* out, int32_t M,

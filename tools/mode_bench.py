@@ -4,7 +4,9 @@
     python tools/mode_bench.py --numerics fast,fast16 [--steps 20] [--warmup 5] [--rounds 4] [--frames 243] [--cs 512]
 
 `--frames N` runs the same sampler on clips of N frames (1 ... 1024), `--cs C` at a width of C channels (8 heads; 512, 256, 128
-or 64).  A `:rows` suffix on a mode name (`fast:rows`, `exact:rows`)
+or 64, and for `exact` any width the library takes: 192, 320, 384 and 448 have two routes).  An `:f16x2` suffix (`exact:f16x2`)
+creates that model's context with D3DP_EXACT_IMPL=f16x2: at `--cs` 192 / 320 / 384 / 448 the split-fp16 implementation with padded
+heads instead of the fp32 implementation -- `--cs 384 --numerics exact,exact:f16x2` is the A/B of the two.  A `:rows` suffix on a mode name (`fast:rows`, `exact:rows`)
 creates that model's library context with D3DP_LONG_ATTN=rows in the environment: the row attention kernel wherever the mode would
 take a chunked-key or, in the FAST modes, a whole-sequence matrix-core kernel beyond 256 frames / 32 joints, and at head dims 32
 and 16 (`--cs 256`, `--cs 128`) for every attention of a FAST mode -- the A/B of those kernels in one process:
@@ -16,7 +18,8 @@ clock around a device synchronise per visit: drift of the box (clock, temperatur
 back-to-back bench.py runs cannot offer.  Clock and power are sampled the way bench.py samples them (its GpuTelemetry), per mode,
 over that mode's timed visits only.  Prints ONE JSON line: per mode hypothesis-clips/s, ms per step, the per-visit spread, mean
 clock / power; the ratio of every mode to the first; the operand type and proven bound of the FAST modes; the library's sha256;
-and, from one more untimed step per mode under d3dp_profile_read, launches and kernel ms of the two attention classes.
+and, from one more untimed step per mode under d3dp_profile_read, launches and kernel ms of the two attention classes (EXACT
+modes: of every class, with the implementation the context reports).
 """
 import argparse
 import json
@@ -48,23 +51,26 @@ def main():
     from d3dp_amd.weights import flip_2d, synthetic_inputs_2d
     B, H, K = a.batch, a.hyps, a.ksteps
     frames = bench.F_ if a.frames is None else a.frames
-    if not 1 <= frames <= 1024 or any(m.count(":") > 1 or (":" in m and not m.endswith(":rows")) for m in modes):
-        ap.error("--frames must be in [1, 1024]; the only mode suffix is ':rows'")
+    # the switch a suffix sets in the environment while that mode's context is created
+    suffixes = {"rows": ("D3DP_LONG_ATTN", "rows"), "f16x2": ("D3DP_EXACT_IMPL", "f16x2")}
+    if not 1 <= frames <= 1024 or any(m.count(":") > 1 or (":" in m and m.split(":")[1] not in suffixes) for m in modes):
+        ap.error("--frames must be in [1, 1024]; the mode suffixes are ':rows' and ':f16x2'")
     x2d_np = synthetic_inputs_2d(1234, B, frames)
     x2d, x2f = torch.from_numpy(x2d_np).cuda(), torch.from_numpy(flip_2d(x2d_np)).cuda()
     cs = bench.C_ if a.cs is None else a.cs
     models = {m: bench.build_model(H, K, m.split(":")[0], 0, frames=frames, cs=cs) for m in modes}
-    saved = os.environ.get("D3DP_LONG_ATTN")
-    for m in modes:                                    # the contexts, now: a `:rows` one with the switch set for its creation
-        if m.endswith(":rows"):
-            os.environ["D3DP_LONG_ATTN"] = "rows"
+    for m in modes:                                    # the contexts, now: a suffixed one with its switch set for its creation
+        key, val = suffixes[m.split(":")[1]] if ":" in m else (None, None)
+        saved = os.environ.get(key) if key else None
+        if key:
+            os.environ[key] = val
         try:
             models[m].pose_estimator._context(torch.device("cuda", torch.cuda.current_device()))
         finally:
-            if m.endswith(":rows"):
-                os.environ.pop("D3DP_LONG_ATTN")
+            if key:
+                os.environ.pop(key)
                 if saved is not None:
-                    os.environ["D3DP_LONG_ATTN"] = saved
+                    os.environ[key] = saved
     gens = {m: torch.Generator(device="cuda").manual_seed(1) for m in modes}
     teles = {m: bench.GpuTelemetry(torch.cuda.current_device()) for m in modes}
     for m in modes:
@@ -97,6 +103,9 @@ def main():
                            "fast_operands": None if fo is None else {"type": fo[0], "proven_bound": fo[1]},
                            "attention_classes_one_step": {k: {"launches": c, "kernel_ms": round(ms, 3)} for k, (c, ms) in prof.items()
                                                           if k.startswith("attn")}}
+        if m.split(":")[0] == "exact":
+            res["modes"][m]["exact_implementation"] = models[m].pose_estimator.exact_scales()[2]
+            res["modes"][m]["classes_one_step"] = {k: {"launches": c, "kernel_ms": round(ms, 3)} for k, (c, ms) in prof.items() if c}
     base = res["modes"][modes[0]]["value"]
     res["ratio_to_first"] = {m: res["modes"][m]["value"] / base for m in modes}
     print(json.dumps(res))
