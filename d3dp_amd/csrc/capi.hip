@@ -45,9 +45,11 @@ const char* kClassNames[D3DP_PROFILE_CLASSES] = {"gemm_qkv", "gemm_proj", "gemm_
 // The environment switches of a context, read once at d3dp_create: the cross-check implementations, the training step's
 // scheduling switches and the measurement switches of the experiment kernels.  `width_inst`: the width is one the matrix-core
 // kernels are instantiated for, or one the split-fp16 implementation takes with padded heads under D3DP_EXACT_IMPL=f16x2
-// (d3dp_create).  D3DP_OK, or the refusal (the caller deletes the context).
+// (d3dp_create).  `train_split`: the training step may run on split-fp16 operands -- an instantiated width, or a TRAIN context
+// that D3DP_TRAIN_IMPL=f16x2 opted in (d3dp_create); a decision of its own, so that neither switch changes what a context of the
+// other mode does.  D3DP_OK, or the refusal (the caller deletes the context).
 // (D3DP_TRAIN_ATTN_BWD alone is read per call, in train.hip: tests flip it between steps.)
-int read_switches(d3dp_ctx* c, bool width_inst) {
+int read_switches(d3dp_ctx* c, bool width_inst, bool train_split) {
   const d3dp_cfg& g = c->cfg;
   const char* xf = getenv("D3DP_EXACT_IMPL");
   c->exact_impl = c->exact_impl_req = (xf && !strcmp(xf, "bf16x3")) ? 1 : (xf && !strcmp(xf, "f32")) ? 2 : 0;
@@ -63,7 +65,7 @@ int read_switches(d3dp_ctx* c, bool width_inst) {
   const char* dn = getenv("D3DP_DEFER_NORM");            // cross-check: =0 keeps the shared norms in place in the norm pair
   c->defer = !(dn && dn[0] == '0');
   const char* ti = getenv("D3DP_TRAIN_IMPL");
-  c->train_x2 = !(ti && !strcmp(ti, "f32")) && width_inst;     // (a width outside the instantiated set: the fp32 path)
+  c->train_x2 = !(ti && !strcmp(ti, "f32")) && train_split;    // (a width outside the instantiated set, not opted in: the fp32 path)
   const char* ov = getenv("D3DP_TRAIN_OVERLAP");
   c->train_overlap = !(ov && ov[0] == '0');
   c->train_overlap_sets = (ov && ov[0] == '1') ? 1 : 2;
@@ -132,7 +134,9 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   //  through LDS in chunks and takes every length up to 1024; its fp32 attention -- head dim 8, the cross-check switches -- holds a
   //  whole sequence in LDS and d3dp_train_forward refuses more than 256 frames there; a TRAIN context of a width outside the
   //  instantiated set runs that fp32 attention with a run-time head dim and is refused BELOW beyond 256 tokens, 153 at head dims
-  //  above 64.)
+  //  above 64 -- unless D3DP_TRAIN_IMPL=f16x2 opted it into the split-fp16 step (channels in {192, 320, 384, 448}, below): head dims
+  //  24 / 40 / 48 / 56 then run padded forms of the split-fp16 attention and take every length up to 1024 too, and what the
+  //  cross-check switches or head dim 8 leave on the fp32 attention there is refused by d3dp_train_forward like at every width.)
   if (g.frames < 1 || g.frames > 1024) return d3dp_fail(D3DP_ENOTSUP, "frames=%d not in [1,1024]", g.frames);
   // (more than 32 joints: the spatial axis takes the whole-sequence attention kernels the temporal axis runs on, round 6)
   if (g.joints < 1 || g.joints > 256) return d3dp_fail(D3DP_ENOTSUP, "joints=%d not in [1,256]", g.joints);
@@ -173,6 +177,24 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
       hdp = hd <= 32 ? 32 : 64;
     }
   }
+  // D3DP_TRAIN_IMPL=f16x2 (opt-in; read for TRAIN contexts alone): a TRAIN context at the same widths takes the split-fp16 training
+  // step -- X2Train's Linears take any N, K that are multiples of 32, the row kernels of train_g.hip leave the operand absmax
+  // behind, and the attention runs on train_attn.hip with the head padded to 32 / 64 inside its LDS images (no weight, workspace or
+  // Linear knows about the padding).  At an instantiated width the value names the default; anywhere else it is refused here.
+  bool train_widths = false;
+  if (g.mode == D3DP_MODE_TRAIN && !width_inst) {
+    const char* ti = getenv("D3DP_TRAIN_IMPL");
+    if (ti && !strcmp(ti, "f16x2")) {
+      const bool shape = (g.channels == 192 || g.channels == 320 || g.channels == 384 || g.channels == 448) && hd % 8 == 0 &&
+                         hd <= 64 && g.hidden >= 64 && g.hidden % 64 == 0;
+      if (!shape)
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_IMPL=f16x2 outside the instantiated widths exists for D3DP_MODE_TRAIN contexts with channels in "
+                                  "{192,320,384,448}, head dim a multiple of 8 up to 64 and hidden a multiple of 64; channels=%d heads=%d "
+                                  "hidden=%d is not one (unset the switch: such a context trains on the fp32 path)",
+                    g.channels, g.heads, g.hidden);
+      train_widths = true;
+    }
+  }
   if (!width_inst && !hdp) {
     if (g.mode == D3DP_MODE_FAST)
       return d3dp_fail(D3DP_ENOTSUP, "channels=%d heads=%d hidden=%d: FAST contexts exist for channels in {64,128,256,512} with head dim in "
@@ -188,7 +210,7 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
                                 "and hidden a multiple of 4", g.channels, g.heads, g.hidden);
     // (the fp32 attention backward holds two whole-sequence images of its capacity head dim + the statistics in the CU's 160 KiB)
     const int nmax = std::max(g.frames, g.joints), cap = hd <= 16 ? 16 : hd <= 32 ? 32 : hd <= 64 ? 64 : 128;
-    if (g.mode == D3DP_MODE_TRAIN && (nmax > 256 || (size_t)nmax * (8 * (cap + 4) + 12) > 160 * 1024))
+    if (g.mode == D3DP_MODE_TRAIN && !train_widths && (nmax > 256 || (size_t)nmax * (8 * (cap + 4) + 12) > 160 * 1024))
       return d3dp_fail(D3DP_ENOTSUP, "channels=%d heads=%d frames=%d joints=%d: training at a width outside {64,128,256,512} runs the fp32 attention "
                                 "backward, which holds a whole sequence in LDS (<= 256 tokens; <= 153 at head dims above 64)",
                   g.channels, g.heads, g.frames, g.joints);
@@ -200,7 +222,7 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   c->cfg = g;
   c->fast_f16 = c->fast16() ? 1 : (c->fast() ? D3DP_FAST_F16 : 0);   // (FAST16: until d3dp_set_weights has seen the weights)
   c->hdp = hdp;
-  if (const int rc = read_switches(c, width_inst || hdp != 0); rc != D3DP_OK) {
+  if (const int rc = read_switches(c, width_inst || hdp != 0, width_inst || hdp != 0 || train_widths); rc != D3DP_OK) {
     delete c;
     return rc;
   }

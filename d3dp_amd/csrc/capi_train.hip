@@ -4,7 +4,8 @@
 // weight gradients as TN products of two row-form operands (nothing is transposed), one merged launch per block on a second
 // stream; attention on the split-fp16 kernels of train_attn.hip; the rest are row-wise fp32 kernels (train.hip) that leave the
 // next Linear's operand or its absmax behind.  TrainPath (ctx.h) says which of these a context takes: the fp32 matrix-core
-// path (D3DP_TRAIN_IMPL=f32, every width outside {64, 128, 256, 512}) stays as the cross-check.  No float atomics (Reducer).
+// path (D3DP_TRAIN_IMPL=f32, every width outside {64, 128, 256, 512} that D3DP_TRAIN_IMPL=f16x2 has not opted in) stays as the
+// cross-check.  No float atomics (Reducer).
 #include "ctx.h"
 
 namespace {
@@ -431,11 +432,12 @@ int d3dp_train_forward(d3dp_ctx* c, const float* x2d, const float* x3d, const in
   const TrainPath path(*c);
   const bool use_x2 = path.use_x2;
   // clips longer than 256 frames (reference common/arguments.py:58, main.py:325 train at any `-f`): the split-fp16 attention kernels
-  // pass their keys / queries through LDS in chunks (train_attn.hip: head dims 64, 32 and 16); the fp32 kernels hold whole
-  // sequences, and they are what head dim 8, a width outside the instantiated set and the cross-check switches run
+  // pass their keys / queries through LDS in chunks (train_attn.hip: head dims 64, 32 and 16, and 24 / 40 / 48 / 56 at the widths
+  // D3DP_TRAIN_IMPL=f16x2 opts in); the fp32 kernels hold whole sequences, and they are what head dim 8, a width on the fp32 path
+  // and the cross-check switches run
   if (g.frames > 256 && !(path.attn_x2(0) && path.attn_x2(1)))
     return d3dp_fail(D3DP_ENOTSUP, "frames=%d > 256: the training step runs such clips on its split-fp16 attention kernels only, which take "
-                              "head dims 64, 32 and 16 (channels=%d heads=%d is head dim %d) and are switched off by the cross-check "
+                              "head dims 64, 32 and 16 -- 24, 40, 48 and 56 under D3DP_TRAIN_IMPL=f16x2 -- (channels=%d heads=%d is head dim %d) and are switched off by the cross-check "
                               "switches D3DP_TRAIN_IMPL=f32 and D3DP_TRAIN_ATTN=f32|x2t; the fp32 attention holds a whole sequence "
                               "in LDS (<= 256 frames)", g.frames, g.channels, g.heads, g.channels / g.heads);
   const TrainLayout L = train_layout(g, B);

@@ -53,6 +53,9 @@ inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 // Which attention kernel family a context launches on an axis (0 = spatial, 1 = temporal): attn_route(), capi_denoise.hip
 enum class AttnRoute { X2, FAST_SPATIAL, FAST_WHOLE_SEQ, F32_TEMPORAL, ROWS };
 inline bool mfma_head_dim(int hd) { return hd == 64 || hd == 32 || hd == 16; }   // head dims the matrix-core attention kernels take
+// ... and the training step's (train_attn.hip): those, and 24 / 40 / 48 / 56 padded to 32 / 64 inside its kernels -- the head dims of
+// channels in {192, 320, 384, 448} with the model's 8 heads, reached under D3DP_TRAIN_IMPL=f16x2 only (d3dp_create)
+inline bool train_attn_head_dim(int hd) { return mfma_head_dim(hd) || hd == 24 || hd == 40 || hd == 48 || hd == 56; }
 AttnRoute attn_route(int mode, int exact_impl, int hd, int frames, int joints, bool long_rows, int axis);
 
 struct d3dp_ctx {
@@ -148,7 +151,9 @@ struct d3dp_ctx {
     return (pad_override < 0 ? skew() : (pad_override > 0 && x2_attn())) ? (fj + 63) / 64 * 64 : fj;
   }
   int pad_override = -1;         // D3DP_SEQ_PAD=0|1: measurement switch (pad without the skewed schedule, or the reverse)
-  bool train_x2 = true;          // D3DP_TRAIN_IMPL=f32: the training Linears on the fp32 matrix cores (round-1 path, cross-check)
+  bool train_x2 = true;          // D3DP_TRAIN_IMPL=f32: the training Linears on the fp32 matrix cores (round-1 path, cross-check).  Also
+                                 // false at a width outside {64, 128, 256, 512} -- unless D3DP_TRAIN_IMPL=f16x2 opted a TRAIN context
+                                 // at channels in {192, 320, 384, 448} into the split-fp16 step (d3dp_create)
   // The backward pass runs the weight-gradient products (one merged TN launch per block, or one launch per Linear, and the sum of
   // their partial tiles) on a second stream beside the rest of the backward pass: a block's launch goes on while the next block's
   // dgrad products, attention and row kernels run (two operand / partial-tile sets, X2Train::use_set).  Forked and joined with events
@@ -264,11 +269,13 @@ inline SeqMap spatial_map(int F, int J, int sp = 0) { return sp > F * J ? SeqMap
 inline SeqMap temporal_map(int F, int J, int sp = 0) { return SeqMap{F, J, sp > F * J ? sp : F * J, 1, J}; }
 
 // Which path a TRAIN context's step takes, computed once per call from the switches read at d3dp_create.
-//   use_x2     the Linears on split-fp16 operands (X2Train, capi_train.hip); else the fp32 matrix cores
+//   use_x2     the Linears on split-fp16 operands (X2Train, capi_train.hip); else the fp32 matrix cores.  d3dp_ctx::train_x2: the
+//              instantiated widths unless D3DP_TRAIN_IMPL=f32, and channels in {192, 320, 384, 448} under D3DP_TRAIN_IMPL=f16x2
 //   attn_x2(a) axis a's attention on the split-fp16 kernels of train_attn.hip: they need the split Linears' device-side scales
-//              and a head dim the matrix cores take (mfma_head_dim: 64, 32, 16 -- `-cs` 512 / 256 / 128 with the model's 8 heads);
-//              clips of up to 1024 frames (beyond 256 their keys / queries pass through LDS in chunks).  Head dim 8 and the
-//              widths outside the instantiated set stay on the fp32 kernels of train.hip (<= 256 frames)
+//              and a head dim those kernels take (train_attn_head_dim: 64, 32, 16 -- `-cs` 512 / 256 / 128 with the model's 8 heads --
+//              and 56, 48, 40, 24 -- `-cs` 448 / 384 / 320 / 192 -- padded to 64 / 32 inside the kernels); clips of up to 1024 frames
+//              (beyond 256 their keys / queries pass through LDS in chunks).  Head dim 8, the cross-check switches and every
+//              context on the fp32 path stay on the fp32 kernels of train.hip (<= 256 frames)
 //   needs_aux  the backward pass forks its weight-gradient products onto the context's second stream (made by d3dp_create)
 struct TrainPath {
   bool use_x2, attn_x2_t, attn_x2_s, needs_aux;
@@ -276,7 +283,7 @@ struct TrainPath {
   explicit TrainPath(const d3dp_ctx& c) {
     const d3dp_cfg& g = c.cfg;
     use_x2 = c.train_x2 && g.channels % 32 == 0 && g.hidden % 32 == 0;
-    attn_x2_t = use_x2 && c.train_attn_x2 > 0 && mfma_head_dim(g.channels / g.heads) && g.frames <= 1024;
+    attn_x2_t = use_x2 && c.train_attn_x2 > 0 && train_attn_head_dim(g.channels / g.heads) && g.frames <= 1024;
     attn_x2_s = attn_x2_t && c.train_attn_x2 > 1;      // the spatial axis too
     needs_aux = c.train() && use_x2 && c.train_overlap;
   }

@@ -288,7 +288,8 @@ size_t d3dp_train_attn_stats_bytes(int n_seq, int n_tok, int heads);
 int d3dp_train_attn_bwd(const float* qkv, const float* o, const float* dout, float* dqkv, void* stats, int n_seq,
                         SeqMap map, int C, int heads, hipStream_t st);
 constexpr int D3DP_EMBED_BWD_ROWS = 64;
-// ---- train_attn.hip: the training step's attention on split-fp16 operands (head dim 64, 32 or 16: -2 for any other; <= 1024 tokens per sequence) ----
+// ---- train_attn.hip: the training step's attention on split-fp16 operands (head dim 64, 32 or 16, and 24 / 40 / 48 / 56 padded to 32 / 64
+// inside the kernels: -2 for any other; <= 1024 tokens per sequence) ----
 // stats: d3dp_train_attn_x2_stats_bytes per attention (the forward leaves the log-sum-exp of every query for the backward pass);
 // amax_qkv / amax_do: absmax slots of the whole qkv tensor / of dout (left by the Linears that produced them); amax_out
 // (optional): absmax slot of the result.
@@ -299,6 +300,11 @@ int d3dp_train_attn_x2_fwd(const float* qkv, float* out, void* stats, int n_seq,
 int d3dp_train_attn_x2_bwd(const float* qkv, const float* o, const float* dout, float* dqkv, void* stats, int n_seq, SeqMap map,
                            int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
                            hipStream_t st, int part = 0);
+// train_attn_pad.hip: the padded-head instantiations behind the two launchers above (which: 0 = forward, 1 = both backward passes,
+// 2 = pass Q alone, 3 = pass KV alone); called by train_attn.hip only
+int d3dp_train_attn_x2_padded(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats,
+                              int n_seq, SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do,
+                              unsigned* amax_out, hipStream_t st);
 int d3dp_train_embed_bwd(const float* dx, const float* x2d, const float* x3d, float* part, int T, int C, hipStream_t st);
 int d3dp_train_head_linear(const float* z, const float* w, const float* b, float* out, int T, int C, hipStream_t st);
 int d3dp_train_head_bwd(const float* g, const float* z, const float* w, float* dz, float* part, int* rows, int T, int C,
@@ -312,17 +318,19 @@ int d3dp_train_time_mlp_bwd(const int64_t* t, const float* freq, const float* w1
 
 // train_g.hip: the training step's row kernels at a run-time width (any C <= 1024; the fp32 path of capi_train.hip for the widths
 // train.hip does not instantiate).  The d3dp_train_* launchers above forward to these when d3dp_width_instantiated(C) is false.
+// amax (optional, as above): the three kernels that feed a split-fp16 Linear leave the absmax of what its operand pass will split
+// (D3DP_TRAIN_IMPL=f16x2 at -cs 192 / 320 / 384 / 448); null on the fp32 path, whose results it does not touch.  No operand rows.
 inline bool d3dp_width_instantiated(int C) { return C == 64 || C == 128 || C == 256 || C == 512; }
 int d3dp_train_g_add_mask_ln(const float* x_in, const float* y, const float* mask, int axis, int F, int J, const float* w,
-                             const float* b, float eps, float* x_out, float* xn, int T, int C, hipStream_t st);
+                             const float* b, float eps, float* x_out, float* xn, unsigned* amax, int T, int C, hipStream_t st);
 int d3dp_train_g_add_mask_ln2(const float* x_in, const float* y, const float* mask, int axis, int F, int J, const float* wa,
                               const float* ba, float eps_a, const float* pos, const float* wb, const float* bb, float eps_b,
-                              float* x_out, float* x_next, float* xn, int T, int C, hipStream_t st);
+                              float* x_out, float* x_next, float* xn, unsigned* amax, int T, int C, hipStream_t st);
 int d3dp_train_g_ln_pos(const float* x, const float* w, const float* b, float eps, const float* pos, int F, int J, float* y, int T,
                         int C, hipStream_t st);
 int d3dp_train_g_ln_bwd(const float* dy, const float* xb, const float* wb, float eps_b, const float* dres, float* g_out,
                         const float* xa, const float* wa, float eps_a, float* dx, const float* mask, int axis, int F, int J,
-                        float* dxm, float* part_b, float* part_a, int T, int C, int blocks, hipStream_t st);
+                        float* dxm, unsigned* amax, float* part_b, float* part_a, int T, int C, int blocks, hipStream_t st);
 int d3dp_train_g_head_linear(const float* z, const float* w, const float* b, float* out, int T, int C, hipStream_t st);
 int d3dp_train_g_time_mlp_bwd(const int64_t* t, const float* freq, const float* w1, const float* b1, const float* w2,
                               const float* dtemb, float* dw1, float* db1, float* dw2, float* db2, int B, int C, hipStream_t st);

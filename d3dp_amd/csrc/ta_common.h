@@ -59,6 +59,17 @@ template <> struct TAHead<16> {
   static constexpr int ROWB = 32, NQ = 1, ND = 1;
   static constexpr float SCALE = 0.25f;
 };
+// PADDED heads (PAD = true in the staging functions below and in the kernels of train_attn.hip): the true head dim hdt is a
+// multiple of 8 below the image head dim HD (24 -> 32; 40 / 48 / 56 -> 64).  Global memory keeps the true layout -- head h starts
+// at channel h hdt -- and only the LDS images and the register operands are HD wide: an 8-channel slot at or behind hdt is never
+// loaded (it would be the neighbouring head, or lie behind the row for the last head of v) and holds exact zeros, so every
+// product over channels adds zeros and every accumulator of a pad channel is an exact zero.  The softmax exponent is hdt^-0.5.
+// (selected as BITS: the head dim is uniform, so the selects run on the scalar unit and the result stays in a scalar register --
+//  computed as a float it would occupy a vector register in kernels that have none to spare.  ta_dispatch admits these four only.)
+__device__ __forceinline__ float ta_true_scale(int hdt) {
+  const unsigned bits = hdt == 24 ? 0x3e5105ecu : hdt == 40 ? 0x3e21e89bu : hdt == 48 ? 0x3e13cd3au : 0x3e08d677u;   // 24, 40, 48, 56 ^-0.5
+  return __uint_as_float(bits);
+}
 
 // scale of a split operand from its absmax slot (as gemm_x2.hip dyn_scale): the largest magnitude lands in [2^13, 2^14)
 __device__ __forceinline__ float ta_scale(const unsigned* amax) {
@@ -78,8 +89,9 @@ __device__ __forceinline__ void ta_split8(const float4 a, const float4 b, f16x8&
 
 // rows [0, n) x HD channels of an fp32 matrix (row stride `rs` floats) -> the hi / lo images (values x sc); rows [n, NK)
 // zero.  Four 16-byte slots per thread and pass, all loads of a pass in flight before the first conversion.
-template <int NK, int NT, int HD = 64>
-__device__ __forceinline__ void ta_stage(const float* __restrict__ src, size_t rs, int n, float sc, char* img, int tid) {
+// PAD: the matrix has hdt < HD channels; the slots behind them are not loaded and hold zeros.
+template <int NK, int NT, int HD = 64, bool PAD = false>
+__device__ __forceinline__ void ta_stage(const float* __restrict__ src, size_t rs, int n, float sc, char* img, int tid, int hdt = HD) {
   constexpr int ROWB = 2 * HD, SL = HD / 8, LS = HD == 64 ? 3 : HD == 32 ? 2 : 1;   // bytes / 16-byte slots (2^LS) of an image row
   constexpr int PLANE = NK * ROWB;
   constexpr int ITEMS = NK * SL;                       // 16-byte slots of one plane
@@ -92,7 +104,7 @@ __device__ __forceinline__ void ta_stage(const float* __restrict__ src, size_t r
     for (int u = 0; u < 4; ++u) {
       const int idx = i0 + u * NT + tid, row = idx >> LS, slot = idx & (SL - 1);
       a[u] = make_float4(0.f, 0.f, 0.f, 0.f); b[u] = a[u];
-      if (idx < ITEMS && row < n) {
+      if (idx < ITEMS && row < n && (!PAD || slot * 8 < hdt)) {
         const float* p = src + (size_t)row * rs + slot * 8;
         a[u] = *reinterpret_cast<const float4*>(p);
         b[u] = *reinterpret_cast<const float4*>(p + 4);
@@ -119,9 +131,9 @@ __device__ __forceinline__ void ta_stage(const float* __restrict__ src, size_t r
 // The same for NS matrices at once: every matrix's loads of a pass are in flight before the first conversion -- ONE exposed memory round
 // trip per chunk instead of one per operand (round 6: with the operands staged one after the other the loads' latency, not the
 // split arithmetic, was 20 - 40 % of the training attention kernels: D3DP_TA_PROBE builds).  rows [0, n) valid for all of them.
-template <int NK, int NT, int NS, int HD = 64>
+template <int NK, int NT, int NS, int HD = 64, bool PAD = false>
 __device__ __forceinline__ void ta_stage_many(const float* const (&src)[NS], const size_t (&rs)[NS], const float (&sc)[NS],
-                                              char* const (&img)[NS], int n, int tid) {
+                                              char* const (&img)[NS], int n, int tid, int hdt = HD) {
   constexpr int ROWB = 2 * HD, SL = HD / 8, LS = HD == 64 ? 3 : HD == 32 ? 2 : 1;
   constexpr int PLANE = NK * ROWB;
   constexpr int ITEMS = NK * SL;
@@ -136,7 +148,7 @@ __device__ __forceinline__ void ta_stage_many(const float* const (&src)[NS], con
       for (int u = 0; u < 4; ++u) {
         const int idx = i0 + u * NT + tid, row = idx >> LS, slot = idx & (SL - 1);
         a[s][u] = make_float4(0.f, 0.f, 0.f, 0.f); b[s][u] = a[s][u];
-        if (idx < ITEMS && row < n) {
+        if (idx < ITEMS && row < n && (!PAD || slot * 8 < hdt)) {
           const float* p = src[s] + (size_t)row * rs[s] + slot * 8;
           a[s][u] = *reinterpret_cast<const float4*>(p);
           b[s][u] = *reinterpret_cast<const float4*>(p + 4);
@@ -261,9 +273,11 @@ __device__ __forceinline__ void ta_tr_chunk(const TAFragT<HD>& f, int c, const f
 
 // this lane's HD / 4 values of a [.][HD] fp32 row as a split register operand (column operand of ta_rows_pair): channels
 // 8 fg .. + 7 and 32 + 8 fg .. + 7 (HD = 64), 8 fg .. + 7 (HD = 32), 4 fg .. + 3 (HD = 16)
-template <int HD = 64>
+// (PAD: the row has hdt < HD channels; a group of 8 at or behind hdt is not loaded and is zero)
+template <int HD = 64, bool PAD = false>
 __device__ __forceinline__ void ta_load_row_op(const float* row, int fg, float sc, typename TAHead<HD>::frag (&h)[TAHead<HD>::NQ],
-                                               typename TAHead<HD>::frag (&l)[TAHead<HD>::NQ]) {
+                                               typename TAHead<HD>::frag (&l)[TAHead<HD>::NQ], int hdt = HD) {
+  static_assert(!PAD || HD >= 32, "padded heads: 8-channel groups");
   if constexpr (HD == 16) {
     const float4 v = *reinterpret_cast<const float4*>(row + fg * 4);
     const float x[4] = {v.x, v.y, v.z, v.w};
@@ -273,7 +287,13 @@ __device__ __forceinline__ void ta_load_row_op(const float* row, int fg, float s
 #pragma unroll
     for (int half = 0; half < TAHead<HD>::NQ; ++half) {
       const float* p = row + half * 32 + fg * 8;
-      ta_split8(*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4), h[half], l[half], sc);
+      if constexpr (PAD) {
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+        if ((HD == 64 && half == 0) || half * 32 + fg * 8 < hdt) {   // (HD 64: hdt >= 40, the first half lies inside every head)
+          a = *reinterpret_cast<const float4*>(p); b = *reinterpret_cast<const float4*>(p + 4);
+        }
+        ta_split8(a, b, h[half], l[half], sc);
+      } else ta_split8(*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4), h[half], l[half], sc);
     }
   }
 }

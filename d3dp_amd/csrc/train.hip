@@ -920,8 +920,8 @@ static int row_blocks(int T) { return (T + 3) / 4 < kRowBlocks ? (T + 3) / 4 : k
 int d3dp_train_add_mask_ln(const float* x_in, const float* y, const float* mask, int axis, int F, int J, const float* w,
                            const float* b, float eps, float* x_out, float* xn, unsigned* amax, int T, int C, hipStream_t st,
                            void* op, int Tp, float* op_unscale) {
-  if (!d3dp_width_instantiated(C))                     // (the fp32 path: no operand rows, no absmax)
-    return (op || amax) ? -2 : d3dp_train_g_add_mask_ln(x_in, y, mask, axis, F, J, w, b, eps, x_out, xn, T, C, st);
+  if (!d3dp_width_instantiated(C))                     // (a run-time width: no operand rows)
+    return op ? -2 : d3dp_train_g_add_mask_ln(x_in, y, mask, axis, F, J, w, b, eps, x_out, xn, amax, T, C, st);
   if (!w || !b || (!xn && !amax && !op) || (op && (C % 256 != 0 || Tp < T || !op_unscale))) return -1;
   TRAIN_DISPATCH_C(C, hipLaunchKernelGGL((add_mask_ln_kernel<CC>), dim3(row_blocks(T)), dim3(256), 0, st, x_in, y, mask, axis,
                                          F, J, w, b, eps, x_out, xn, amax, T, (f16*)op, Tp, op_unscale))
@@ -932,7 +932,7 @@ int d3dp_train_add_mask_ln2(const float* x_in, const float* y, const float* mask
                             float* x_out, float* x_next, float* xn, unsigned* amax, int T, int C, hipStream_t st, void* op, int Tp,
                             float* op_unscale) {
   if (!d3dp_width_instantiated(C))
-    return (op || amax) ? -2 : d3dp_train_g_add_mask_ln2(x_in, y, mask, axis, F, J, wa, ba, eps_a, pos, wb, bb, eps_b, x_out, x_next, xn, T, C, st);
+    return op ? -2 : d3dp_train_g_add_mask_ln2(x_in, y, mask, axis, F, J, wa, ba, eps_a, pos, wb, bb, eps_b, x_out, x_next, xn, amax, T, C, st);
   if (!wa || !ba || !x_out || !x_next || (xn && !wb) || (wb && !bb) || (op && (C % 256 != 0 || Tp < T || !op_unscale || !wb))) return -1;
   TRAIN_DISPATCH_C(C, hipLaunchKernelGGL((add_mask_ln2_kernel<CC>), dim3(row_blocks(T)), dim3(256), 0, st, x_in, y, mask, axis,
                                          F, J, wa, ba, eps_a, pos, wb, bb, eps_b, x_out, x_next, xn, amax, T, (f16*)op, Tp, op_unscale))
@@ -953,7 +953,7 @@ int d3dp_train_ln_bwd(const float* dy, const float* xb, const float* wb, float e
   if (!dy || !xb || !wb || !dx || !part_b || (xa && (!wa || !part_a))) return -1;
   const int blocks = d3dp_train_ln_bwd_blocks(T);
   if (!d3dp_width_instantiated(C))
-    return amax ? -2 : d3dp_train_g_ln_bwd(dy, xb, wb, eps_b, dres, g_out, xa, wa, eps_a, dx, mask, axis, F, J, dxm, part_b, part_a, T, C, blocks, st);
+    return d3dp_train_g_ln_bwd(dy, xb, wb, eps_b, dres, g_out, xa, wa, eps_a, dx, mask, axis, F, J, dxm, amax, part_b, part_a, T, C, blocks, st);
   if (xa) {
     TRAIN_DISPATCH_C(C, hipLaunchKernelGGL((ln_bwd2_kernel<CC, true>), dim3(blocks), dim3(256), 0, st, dy, xb, wb, eps_b, dres,
                                            g_out, xa, wa, eps_a, dx, mask, axis, F, J, dxm, amax, part_b, part_a, T))

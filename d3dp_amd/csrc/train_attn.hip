@@ -2,6 +2,9 @@
 // main.py:387-401's forward / backward), head dims 64, 32 and 16 (`-cs` 512 / 256 / 128 with the model's 8 heads: HD is a template
 // parameter of every kernel, TAHead<HD> of ta_common.h says what follows from it), sequences of up to 1024 tokens (the temporal
 // axis; beyond 256 every kernel passes its keys / queries through LDS in chunks).  The text below is written at head dim 64.
+// Head dims 24 and 40 / 48 / 56 (`-cs` 192 and 320 / 384 / 448 under D3DP_TRAIN_IMPL=f16x2) run PADDED forms of the head dim 32 / 64
+// kernels (template parameter PAD): the fp32 tensors keep their true layout, the zero channels exist in the LDS images and the
+// register operands only (ta_common.h), the softmax exponent is the true head dim's.
 //
 // Round 4 ran the temporal forward and both backward passes on the FP32 matrix cores (v_mfma_f32_16x16x4_f32: 1/16 of the fp16
 // rate; 5.9 ms of the 27 ms configs[4] step).  Here every product runs on split-fp16 operands like the step's Linears
@@ -50,7 +53,7 @@ __device__ __forceinline__ void ta_block_amax(float am, unsigned* amax, float* p
 // forward
 // (NKC: key tiles per LDS chunk.  Round 6: the images hold 128 keys at a time -- the online softmax runs over key pairs anyway --
 //  so a 243-frame problem needs 64 KiB instead of 128 and TWO workgroups share a CU: four waves per SIMD instead of two)
-template <int NKT, int NW, int NKC, int HD>
+template <int NKT, int NW, int NKC, int HD, bool PAD = false>
 __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                            TAStat* __restrict__ stats, SeqMap map, int C, int heads, int groups,
                                                            int n_work, const unsigned* __restrict__ amax_qkv,
@@ -65,12 +68,14 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t ld = (size_t)3 * C, rs = (size_t)map.tok_stride * ld;
   const float sq = ta_scale(amax_qkv);
+  const int hd = PAD ? C / heads : HD;                 // the head dim of the global layout (PAD: below the image head dim, ta_common.h)
+  const float scale = PAD ? ta_true_scale(hd) : TAHead<HD>::SCALE;
   float am = 0.f;
   // op (round 6): the output ALSO as the split operand rows [Tp][2 C] of the proj Linear behind it (h2i; rows T .. Tp - 1 zero), at
   // the scale of q / k / v -- every output is a convex combination of v rows, so |o| <= max |v| <= the qkv absmax: the bound is
   // known before the first element is written and the operand pass between attention and proj disappears.  op_unscale[0] = 1 /
   // scale, amax_out[0] = the bound.
-  if (op) {
+  if (!PAD && op) {                                    // (padded heads: no operand rows, the launcher refuses them)
     if (blockIdx.x == 0 && tid == 0) { op_unscale[0] = 1.0f / sq; if (amax_out) amax_out[0] = amax_qkv[0]; }
     const size_t n8 = (size_t)(Tp - T) * C / 4;        // 16-byte pieces of the pad rows (2 C fp16 each)
     uint4* z = reinterpret_cast<uint4*>(op + (size_t)T * 2 * C);
@@ -80,16 +85,16 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
   const int prob = unit / groups, group = unit % groups;
   const int seq = prob / heads, head = prob % heads;
   const int base = ta_seq_base(map, seq);
-  const float* p0 = qkv + (size_t)base * ld + (size_t)head * HD;
+  const float* p0 = qkv + (size_t)base * ld + (size_t)head * hd;
   const int qt = group * NW + wave;
   const bool active = qt * 16 < n;                     // (wave-uniform)
   const int fi = lane & 15, fg = lane >> 4;
   const int q = qt * 16 + fi;
   const size_t tok = (size_t)(base + min(q, n - 1) * map.tok_stride);
   typename TAHead<HD>::frag qh[TAHead<HD>::NQ], ql[TAHead<HD>::NQ];
-  if (active) ta_load_row_op<HD>(qkv + tok * ld + head * HD, fg, sq, qh, ql);
+  if (active) ta_load_row_op<HD, PAD>(qkv + tok * ld + head * hd, fg, sq, qh, ql, hd);
   const TAFragT<HD> fk = ta_frag<HD>(kimg, lane), fv = ta_frag<HD>(vimg, lane);
-  const float cexp = TAHead<HD>::SCALE * kLog2e / (sq * sq);     // raw accumulator -> logit in base-2 units
+  const float cexp = scale * kLog2e / (sq * sq);   // raw accumulator -> logit in base-2 units
   float mrun = -INFINITY, lrun = 0.f;                  // running row maximum (base-2 logit units) and denominator
   f32x4 o[ND];
 #pragma unroll
@@ -102,7 +107,7 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
     const size_t rs2[2] = {rs, rs};
     const float sc2[2] = {sq, sq};
     char* const img2[2] = {kimg, vimg};
-    ta_stage_many<NK, NW * 64, 2, HD>(src2, rs2, sc2, img2, n - 16 * kc, tid);
+    ta_stage_many<NK, NW * 64, 2, HD, PAD>(src2, rs2, sc2, img2, n - 16 * kc, tid, hd);
   }
   __syncthreads();
   if (active) {
@@ -152,13 +157,14 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
     // o = (v scale) x 1024 x sum_j p_j v_j against the running maximum; lrun = 1024 x sum_j p_j
     const float inv = 1.0f / (sq * lrun);
     if (q < n) {
-      float* dst = out + tok * C + head * HD + fg * 4;     // O^T[d = dn 16 + 4 fg + i][query fi]
+      float* dst = out + tok * C + head * hd + fg * 4;     // O^T[d = dn 16 + 4 fg + i][query fi]
 #pragma unroll
       for (int dn = 0; dn < ND; ++dn) {
+        if constexpr (PAD) { if (dn * 16 + fg * 4 >= hd) continue; }       // (pad channels: exact zeros, nothing to store)
         const float4 r4 = make_float4(o[dn][0] * inv, o[dn][1] * inv, o[dn][2] * inv, o[dn][3] * inv);
         am = fmaxf(am, fmaxf(fmaxf(fabsf(r4.x), fabsf(r4.y)), fmaxf(fabsf(r4.z), fabsf(r4.w))));
         *reinterpret_cast<float4*>(dst + dn * 16) = r4;
-        if (op) {
+        if (!PAD && op) {
           // (the true-scale value first, the exact power of two inside the split: both halves must round the SAME number)
           const float y[4] = {ta_opaque(r4.x * sq), ta_opaque(r4.y * sq), ta_opaque(r4.z * sq), ta_opaque(r4.w * sq)};
           f16x4 hi, lo;
@@ -173,12 +179,12 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
     }
   }
   }
-  if (amax_out && !op) ta_block_amax<NW>(am, amax_out, part);
+  if (amax_out && (PAD || !op)) ta_block_amax<NW>(am, amax_out, part);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
 // backward, pass Q: dQ (and D_i into the statistics)
-template <int NKT, int NW, int NKC, int WPE, int HD>
+template <int NKT, int NW, int NKC, int WPE, int HD, bool PAD = false>
 __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                              const float* __restrict__ dout, float* __restrict__ dqkv,
                                                              TAStat* __restrict__ stats, SeqMap map, int C, int heads, int groups,
@@ -193,12 +199,14 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t ld = (size_t)3 * C, rs = (size_t)map.tok_stride * ld;
   const float sq = ta_scale(amax_qkv), sg = ta_scale(amax_do);
+  const int hd = PAD ? C / heads : HD;                 // the head dim of the global layout (PAD: below the image head dim, ta_common.h)
+  const float scale = PAD ? ta_true_scale(hd) : TAHead<HD>::SCALE;
   float am = 0.f;
   for (int unit = blockIdx.x; unit < n_work; unit += gridDim.x) {
   const int prob = unit / groups, group = unit % groups;
   const int seq = prob / heads, head = prob % heads;
   const int base = ta_seq_base(map, seq);
-  const float* p0 = qkv + (size_t)base * ld + (size_t)head * HD;
+  const float* p0 = qkv + (size_t)base * ld + (size_t)head * hd;
   const int qt = group * NW + wave;
   const bool active = qt * 16 < n;                     // (wave-uniform)
   const int fi = lane & 15, fg = lane >> 4;
@@ -207,16 +215,17 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
   typename TAHead<HD>::frag qh[TAHead<HD>::NQ], ql[TAHead<HD>::NQ], gh[TAHead<HD>::NQ], gl[TAHead<HD>::NQ];
   float D = 0.f, L = 0.f;
   if (active) {
-    ta_load_row_op<HD>(qkv + tok * ld + head * HD, fg, sq, qh, ql);
-    ta_load_row_op<HD>(dout + tok * C + head * HD, fg, sg, gh, gl);
+    ta_load_row_op<HD, PAD>(qkv + tok * ld + head * hd, fg, sq, qh, ql, hd);
+    ta_load_row_op<HD, PAD>(dout + tok * C + head * hd, fg, sg, gh, gl, hd);
     {
-      const float* gs = dout + tok * C + head * HD;
-      const float* os = o + tok * C + head * HD;
+      const float* gs = dout + tok * C + head * hd;
+      const float* os = o + tok * C + head * hd;
       constexpr int W = HD == 16 ? 4 : 8;              // contiguous channels per lane and half: those of ta_load_row_op, in that order
 #pragma unroll
       for (int half = 0; half < TAHead<HD>::NQ; ++half)
 #pragma unroll
         for (int c4 = 0; c4 < W / 4; ++c4) {
+          if constexpr (PAD) { if (!(HD == 64 && half == 0) && half * 32 + fg * W >= hd) continue; }   // (a group of 8 behind the true head dim: not this head's)
           const float4 g = *reinterpret_cast<const float4*>(gs + half * 32 + fg * W + c4 * 4);
           const float4 ov = *reinterpret_cast<const float4*>(os + half * 32 + fg * W + c4 * 4);
           D = fmaf(g.x, ov.x, D); D = fmaf(g.y, ov.y, D); D = fmaf(g.z, ov.z, D); D = fmaf(g.w, ov.w, D);
@@ -225,10 +234,16 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
       D += __shfl_xor(D, 32, 64);
     }
     L = stats[(size_t)prob * n + min(q, n - 1)].L;
+    // (PAD: D_i leaves here, and the loop below sees D_i and the dP factor with the softmax scale folded in -- the true head dim's
+    //  scale is no inline constant, and this kernel has neither a vector nor a scalar register left to keep it in over the loop)
+    if constexpr (PAD) {
+      if (q < n && fg == 0) stats[(size_t)prob * n + q].D = D;
+      D *= scale;
+    }
   }
   const TAFragT<HD> fk = ta_frag<HD>(kimg, lane), fv = ta_frag<HD>(vimg, lane);
-  const float cexp = TAHead<HD>::SCALE * kLog2e / (sq * sq);
-  const float cdp = 1.0f / (sq * sg);                  // raw dP accumulator -> true scale
+  const float cexp = scale * kLog2e / (sq * sq);
+  const float cdp = PAD ? scale / (sq * sg) : 1.0f / (sq * sg);   // raw dP accumulator -> true scale (PAD: x the softmax scale)
   int eb = 20;                                         // running biased exponent of the row's largest |dS| (floor 2^-107)
   f32x4 dq[ND];
 #pragma unroll
@@ -241,7 +256,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
     const size_t rs2[2] = {rs, rs};
     const float sc2[2] = {sq, sq};
     char* const img2[2] = {kimg, vimg};
-    ta_stage_many<NK, NW * 64, 2, HD>(src2, rs2, sc2, img2, n - 16 * kc, tid);
+    ta_stage_many<NK, NW * 64, 2, HD, PAD>(src2, rs2, sc2, img2, n - 16 * kc, tid, hd);
   }
   __syncthreads();
   if (active) {
@@ -255,8 +270,13 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float pa = __builtin_amdgcn_exp2f(fmaf(a[r], cexp, -L)), pb = __builtin_amdgcn_exp2f(fmaf(b[r], cexp, -L));
-        ds[r] = pa * (fmaf(c[r], cdp, -D)) * TAHead<HD>::SCALE;
-        ds[4 + r] = pb * (fmaf(d[r], cdp, -D)) * TAHead<HD>::SCALE;
+        if constexpr (PAD) {
+          ds[r] = pa * fmaf(c[r], cdp, -D);
+          ds[4 + r] = pb * fmaf(d[r], cdp, -D);
+        } else {
+          ds[r] = pa * (fmaf(c[r], cdp, -D)) * scale;
+          ds[4 + r] = pb * (fmaf(d[r], cdp, -D)) * scale;
+        }
       }
       if (16 * (kc + t + 2) > n) {                     // (uniform: only the last pair(s) hold keys >= n)
 #pragma unroll
@@ -282,15 +302,16 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
   if (active) {
     if (q < n) {
       const float un = 1.0f / sq;
-      float* dst = dqkv + tok * ld + head * HD + fg * 4;
+      float* dst = dqkv + tok * ld + head * hd + fg * 4;
 #pragma unroll
       for (int dn = 0; dn < ND; ++dn) {
+        if constexpr (PAD) { if (dn * 16 + fg * 4 >= hd) continue; }
         const float4 r4 = make_float4(ldexpf(dq[dn][0], eb - 140) * un, ldexpf(dq[dn][1], eb - 140) * un,
                                       ldexpf(dq[dn][2], eb - 140) * un, ldexpf(dq[dn][3], eb - 140) * un);
         am = fmaxf(am, fmaxf(fmaxf(fabsf(r4.x), fabsf(r4.y)), fmaxf(fabsf(r4.z), fabsf(r4.w))));
         *reinterpret_cast<float4*>(dst + dn * 16) = r4;
       }
-      if (fg == 0) stats[(size_t)prob * n + q].D = D;
+      if constexpr (!PAD) { if (fg == 0) stats[(size_t)prob * n + q].D = D; }
     }
   }
   }
@@ -299,7 +320,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
 
 // ------------------------------------------------------------------------------------------------------------------------
 // backward, pass KV: dK, dV
-template <int NKT, int NW, int NKC, int WPE, int HD>
+template <int NKT, int NW, int NKC, int WPE, int HD, bool PAD = false>
 __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                               float* __restrict__ dqkv, const TAStat* __restrict__ stats,
                                                               SeqMap map, int C, int heads, int groups, int n_work,
@@ -315,6 +336,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t ld = (size_t)3 * C, rs = (size_t)map.tok_stride * ld;
   const float sq = ta_scale(amax_qkv), sg = ta_scale(amax_do);
+  const int hd = PAD ? C / heads : HD;                 // the head dim of the global layout (PAD: below the image head dim, ta_common.h)
+  const float scale = PAD ? ta_true_scale(hd) : TAHead<HD>::SCALE;
   float am = 0.f;
   for (int unit = blockIdx.x; unit < n_work; unit += gridDim.x) {
   const int prob = unit / groups, group = unit % groups;
@@ -328,11 +351,11 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
   const size_t tok = (size_t)(base + min(key, n - 1) * map.tok_stride);
   typename TAHead<HD>::frag kh[TAHead<HD>::NQ], kl[TAHead<HD>::NQ], vh[TAHead<HD>::NQ], vl[TAHead<HD>::NQ];
   if (active) {
-    ta_load_row_op<HD>(qkv + tok * ld + C + head * HD, fg, sq, kh, kl);
-    ta_load_row_op<HD>(qkv + tok * ld + 2 * C + head * HD, fg, sq, vh, vl);
+    ta_load_row_op<HD, PAD>(qkv + tok * ld + C + head * hd, fg, sq, kh, kl, hd);
+    ta_load_row_op<HD, PAD>(qkv + tok * ld + 2 * C + head * hd, fg, sq, vh, vl, hd);
   }
   const TAFragT<HD> fq = ta_frag<HD>(qimg, lane), fgr = ta_frag<HD>(gimg, lane);
-  const float cexp = TAHead<HD>::SCALE * kLog2e / (sq * sq);
+  const float cexp = scale * kLog2e / (sq * sq);
   const float cdp = 1.0f / (sq * sg);
   int eb = 20;
   f32x4 dk[ND], dv[ND];
@@ -343,9 +366,9 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
   if (unit != (int)blockIdx.x || qc != 0) __syncthreads();
   // (one operand after the other here: both at once -- ta_stage_many, as in the forward pass and pass Q -- costs this 200-register
   //  kernel more than the second round trip: 98 -> 105 us)
-  ta_stage<NK, NW * 64, HD>(qkv + (size_t)base * ld + (size_t)head * HD + (size_t)qc * 16 * rs, rs, n - 16 * qc, sq, qimg, tid);
-  ta_stage<NK, NW * 64, HD>(dout + (size_t)base * C + (size_t)head * HD + (size_t)qc * 16 * map.tok_stride * C, (size_t)map.tok_stride * C,
-                        n - 16 * qc, sg, gimg, tid);
+  ta_stage<NK, NW * 64, HD, PAD>(qkv + (size_t)base * ld + (size_t)head * hd + (size_t)qc * 16 * rs, rs, n - 16 * qc, sq, qimg, tid, hd);
+  ta_stage<NK, NW * 64, HD, PAD>(dout + (size_t)base * C + (size_t)head * hd + (size_t)qc * 16 * map.tok_stride * C, (size_t)map.tok_stride * C,
+                        n - 16 * qc, sg, gimg, tid, hd);
   for (int i = tid; i < NK; i += NW * 64) {
     // rows >= n: their Q and dO image rows are zero, so any FINITE p and dS contribute nothing: L = +large keeps p = 0
     float2 v = make_float2(1.0e30f, 0.f);
@@ -367,8 +390,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
         const float2 sa = st[16 * t + 4 * fg + r], sb = st[16 * (t + 1) + 4 * fg + r];
         float pa = __builtin_amdgcn_exp2f(fmaf(a[r], cexp, -sa.x)), pb = __builtin_amdgcn_exp2f(fmaf(b[r], cexp, -sb.x));
         if (!live) { pa = 0.f; pb = 0.f; }
-        ds[r] = pa * (fmaf(c[r], cdp, -sa.y)) * TAHead<HD>::SCALE;
-        ds[4 + r] = pb * (fmaf(d[r], cdp, -sb.y)) * TAHead<HD>::SCALE;
+        ds[r] = pa * (fmaf(c[r], cdp, -sa.y)) * scale;
+        ds[4 + r] = pb * (fmaf(d[r], cdp, -sb.y)) * scale;
         const float ya = ta_opaque(pa * 1024.0f), yb = ta_opaque(pb * 1024.0f);
         const f16 ha = (f16)ya, hb = (f16)yb;
         ph[r] = ha; pl[r] = (f16)(ya - (float)ha);
@@ -392,9 +415,10 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
   if (active) {
     if (live) {
       const float uk = 1.0f / sq, uv = 1.0f / (sg * 1024.0f);
-      float* dst = dqkv + tok * ld + C + head * HD + fg * 4;
+      float* dst = dqkv + tok * ld + C + head * hd + fg * 4;
 #pragma unroll
       for (int dn = 0; dn < ND; ++dn) {
+        if constexpr (PAD) { if (dn * 16 + fg * 4 >= hd) continue; }
         const float4 k4 = make_float4(ldexpf(dk[dn][0], eb - 140) * uk, ldexpf(dk[dn][1], eb - 140) * uk,
                                       ldexpf(dk[dn][2], eb - 140) * uk, ldexpf(dk[dn][3], eb - 140) * uk);
         const float4 v4 = make_float4(dv[dn][0] * uv, dv[dn][1] * uv, dv[dn][2] * uv, dv[dn][3] * uv);
@@ -417,7 +441,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
 // are row-fragment reads of the very images the other wave's products contract over -- and D_i = dO_i . O_i goes from pass Q to
 // pass KV through LDS instead of the statistics buffer.  Same products, same splits, same accumulation order as the two
 // kernels: bit-identical gradients (test_attention_backward_on_matrix_cores_matches_the_valu_kernels covers n = 9, 17 through it).
-template <int HD>
+template <int HD, bool PAD = false>
 __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                               const float* __restrict__ dout, float* __restrict__ dqkv,
                                                               const TAStat* __restrict__ stats, SeqMap map, int C, int heads,
@@ -436,7 +460,9 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
   const int fi = lane & 15, fg = lane >> 4;
   const size_t ld = (size_t)3 * C, rs = (size_t)map.tok_stride * ld;
   const float sq = ta_scale(amax_qkv), sg = ta_scale(amax_do);
-  const float cexp = TAHead<HD>::SCALE * kLog2e / (sq * sq);
+  const int hd = PAD ? C / heads : HD;                 // the head dim of the global layout (PAD: below the image head dim, ta_common.h)
+  const float scale = PAD ? ta_true_scale(hd) : TAHead<HD>::SCALE;
+  const float cexp = scale * kLog2e / (sq * sq);
   const float cdp = 1.0f / (sq * sg);                    // raw dP accumulator -> true scale
   const TAFragT<HD> fq = ta_frag<HD>(qimg, lane), fk = ta_frag<HD>(kimg, lane), fv = ta_frag<HD>(vimg, lane), fgr = ta_frag<HD>(gimg, lane);
   typedef typename TAHead<HD>::frag frag;
@@ -453,15 +479,15 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
   for (int unit = blockIdx.x; unit < n_work; unit += gridDim.x) {
     const int seq = unit / heads, head = unit - seq * heads;
     const int base = ta_seq_base(map, seq);
-    const float* p0 = qkv + (size_t)base * ld + (size_t)head * HD;
-    const float* g0 = dout + (size_t)base * C + (size_t)head * HD;
+    const float* p0 = qkv + (size_t)base * ld + (size_t)head * hd;
+    const float* g0 = dout + (size_t)base * C + (size_t)head * hd;
     if (unit != (int)blockIdx.x) __syncthreads();        // every wave is done with the previous unit's images
     {
       const float* const src4[4] = {p0, p0 + C, p0 + 2 * C, g0};
       const size_t rs4[4] = {rs, rs, rs, (size_t)map.tok_stride * C};
       const float sc4[4] = {sq, sq, sq, sg};
       char* const img4[4] = {qimg, kimg, vimg, gimg};
-      ta_stage_many<NK, NW * 64, 4, HD>(src4, rs4, sc4, img4, n, tid);
+      ta_stage_many<NK, NW * 64, 4, HD, PAD>(src4, rs4, sc4, img4, n, tid, hd);
     }
     const int row = wave * 16 + fi;                      // this lane's query (pass Q) and key (pass KV)
     const bool live = row < n;
@@ -469,13 +495,14 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
     {
       // D_i = dO_i . O_i in the channel order of tattn_bwd_q_kernel; rows >= n: L = +large keeps p = 0 in pass KV
       float D = 0.f;
-      const float* gs = dout + tok * C + head * HD;
-      const float* os = o + tok * C + head * HD;
+      const float* gs = dout + tok * C + head * hd;
+      const float* os = o + tok * C + head * hd;
       constexpr int W = HD == 16 ? 4 : 8;
 #pragma unroll
       for (int half = 0; half < NQ; ++half)
 #pragma unroll
         for (int c4 = 0; c4 < W / 4; ++c4) {
+          if constexpr (PAD) { if (!(HD == 64 && half == 0) && half * 32 + fg * W >= hd) continue; }   // (a group of 8 behind the true head dim: not this head's)
           const float4 g = *reinterpret_cast<const float4*>(gs + half * 32 + fg * W + c4 * 4);
           const float4 ov = *reinterpret_cast<const float4*>(os + half * 32 + fg * W + c4 * 4);
           D = fmaf(g.x, ov.x, D); D = fmaf(g.y, ov.y, D); D = fmaf(g.z, ov.z, D); D = fmaf(g.w, ov.w, D);
@@ -499,8 +526,8 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float pa = __builtin_amdgcn_exp2f(fmaf(a[r], cexp, -ld_.x)), pb = __builtin_amdgcn_exp2f(fmaf(b[r], cexp, -ld_.x));
-          ds[r] = pa * (fmaf(c[r], cdp, -ld_.y)) * TAHead<HD>::SCALE;
-          ds[4 + r] = pb * (fmaf(d[r], cdp, -ld_.y)) * TAHead<HD>::SCALE;
+          ds[r] = pa * (fmaf(c[r], cdp, -ld_.y)) * scale;
+          ds[4 + r] = pb * (fmaf(d[r], cdp, -ld_.y)) * scale;
           if (4 * fg + r >= n) ds[r] = 0.f;
           if (16 + 4 * fg + r >= n) ds[4 + r] = 0.f;
         }
@@ -513,9 +540,10 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
         ta_tr_chunk<PLANE>(fk, 0, sh, sl, dq);           // dQ^T[d][query] = K^T dS^T
         if (live) {
           const float un = 1.0f / sq;
-          float* dst = dqkv + tok * ld + head * HD + fg * 4;
+          float* dst = dqkv + tok * ld + head * hd + fg * 4;
 #pragma unroll
           for (int dn = 0; dn < ND; ++dn) {
+            if constexpr (PAD) { if (dn * 16 + fg * 4 >= hd) continue; }
             const float4 r4 = make_float4(ldexpf(dq[dn][0], eb - 140) * un, ldexpf(dq[dn][1], eb - 140) * un,
                                           ldexpf(dq[dn][2], eb - 140) * un, ldexpf(dq[dn][3], eb - 140) * un);
             am = fmaxf(am, fmaxf(fmaxf(fabsf(r4.x), fabsf(r4.y)), fmaxf(fabsf(r4.z), fabsf(r4.w))));
@@ -538,8 +566,8 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
           const float2 sa = st[4 * fg + r], sb = st[16 + 4 * fg + r];
           float pa = __builtin_amdgcn_exp2f(fmaf(a[r], cexp, -sa.x)), pb = __builtin_amdgcn_exp2f(fmaf(b[r], cexp, -sb.x));
           if (!live) { pa = 0.f; pb = 0.f; }
-          ds[r] = pa * (fmaf(c[r], cdp, -sa.y)) * TAHead<HD>::SCALE;
-          ds[4 + r] = pb * (fmaf(d[r], cdp, -sb.y)) * TAHead<HD>::SCALE;
+          ds[r] = pa * (fmaf(c[r], cdp, -sa.y)) * scale;
+          ds[4 + r] = pb * (fmaf(d[r], cdp, -sb.y)) * scale;
           const float ya = ta_opaque(pa * 1024.0f), yb = ta_opaque(pb * 1024.0f);
           const f16 ha = (f16)ya, hb = (f16)yb;
           ph[r] = ha; pl[r] = (f16)(ya - (float)ha);
@@ -555,9 +583,10 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
         ta_tr_chunk<PLANE>(fq, 0, sh, sl, dk);           // dK^T[d][key] = Q^T dS
         if (live) {
           const float uk = 1.0f / sq, uv = 1.0f / (sg * 1024.0f);
-          float* dst = dqkv + tok * ld + C + head * HD + fg * 4;
+          float* dst = dqkv + tok * ld + C + head * hd + fg * 4;
 #pragma unroll
           for (int dn = 0; dn < ND; ++dn) {
+            if constexpr (PAD) { if (dn * 16 + fg * 4 >= hd) continue; }
             const float4 k4 = make_float4(ldexpf(dk[dn][0], eb - 140) * uk, ldexpf(dk[dn][1], eb - 140) * uk,
                                           ldexpf(dk[dn][2], eb - 140) * uk, ldexpf(dk[dn][3], eb - 140) * uk);
             const float4 v4 = make_float4(dv[dn][0] * uv, dv[dn][1] * uv, dv[dn][2] * uv, dv[dn][3] * uv);
@@ -574,7 +603,7 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
 }
 
 struct TAOperand { f16* op; int T, Tp; float* unscale; };   // forward only: the output also as the next Linear's operand rows
-template <int NKT, int HD>
+template <int NKT, int HD, bool PAD = false>
 int ta_launch(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats, int n_seq,
               SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
               hipStream_t st, TAOperand po = {nullptr, 0, 0, nullptr}) {
@@ -589,6 +618,9 @@ int ta_launch(int which, const float* qkv, const float* o, const float* dout, fl
   // forward or pass Q: 32 / 16 KiB) and the accumulators HD / 16 tiles, so every kernel fits 128 registers WITHOUT scratch and pass
   // KV is held to 128 as well and always chunked (compiler's figures: profiles/train_small_heads.md) -- two workgroups of eight
   // waves per CU in all three kernels.
+  // PAD: a true head dim of 24 (HD 32) or 40 / 48 / 56 (HD 64) in the images of HD -- LDS sizes, chunking, waves per workgroup and
+  // register budgets are those of the HD instantiation (compiler's figures: profiles/train_widths.md); no operand rows.
+  if (PAD && po.op) return -1;                         // (never asked: ta_dispatch refuses it)
   constexpr int NKC_KV = (NKT > 16 || (HD < 64 && NKT > 8)) ? 8 : NKT;
   constexpr int WPE_KV = HD < 64 ? 4 : 2;
   constexpr int ROWB = 2 * HD;                         // bytes of an image row
@@ -596,43 +628,44 @@ int ta_launch(int which, const float* qkv, const float* o, const float* dout, fl
   (void)NK;
   static PerDeviceOnce once;
   if (once.get([&](int) {
-        return d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_fwd_kernel<NKT, NW, NKC, HD>), 160 * 1024) < 0 ? -3
-               : d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_bwd_q_kernel<NKT, NW, NKC, 4, HD>), 160 * 1024) < 0 ? -3
-               : d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_bwd_kv_kernel<NKT, NW, NKC_KV, WPE_KV, HD>), 160 * 1024);
+        return d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_fwd_kernel<NKT, NW, NKC, HD, PAD>), 160 * 1024) < 0 ? -3
+               : d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_bwd_q_kernel<NKT, NW, NKC, 4, HD, PAD>), 160 * 1024) < 0 ? -3
+               : d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_bwd_kv_kernel<NKT, NW, NKC_KV, WPE_KV, HD, PAD>), 160 * 1024);
       }) < 0) return -3;
   const int tiles = (map.n_tok + 15) / 16, groups = (tiles + NW - 1) / NW;
   const int n_work = n_seq * heads * groups;
   const dim3 grid(n_work < 2048 ? n_work : 2048), blk(NW * 64);   // (<= 2048 absmax atomics per launch)
   TAStat* s = reinterpret_cast<TAStat*>(stats);
   if (which == 0)
-    hipLaunchKernelGGL((tattn_fwd_kernel<NKT, NW, NKC, HD>), grid, blk, lds_fwd, st, qkv, out, s, map, C, heads, groups, n_work, amax_qkv, amax_out,
+    hipLaunchKernelGGL((tattn_fwd_kernel<NKT, NW, NKC, HD, PAD>), grid, blk, lds_fwd, st, qkv, out, s, map, C, heads, groups, n_work, amax_qkv, amax_out,
                        po.op, po.T, po.Tp, po.unscale);
   else if (NKT == 2) {
     // sequences of at most 32 tokens: both passes in ONE kernel (tattn_bwd_small_kernel); under the per-kernel profile it is timed as
     // pass Q and the pass-KV call is empty
     if (which != 3) {
       const dim3 g2(n_seq * heads < 4096 ? n_seq * heads : 4096);
-      hipLaunchKernelGGL(tattn_bwd_small_kernel<HD>, g2, dim3(128), 0, st, qkv, o, dout, dqkv, (const TAStat*)s, map, C, heads, n_seq * heads,
+      hipLaunchKernelGGL((tattn_bwd_small_kernel<HD, PAD>), g2, dim3(128), 0, st, qkv, o, dout, dqkv, (const TAStat*)s, map, C, heads, n_seq * heads,
                          amax_qkv, amax_do, amax_out);
     }
   } else {                                             // which: 1 = both passes, 2 = pass Q alone, 3 = pass KV alone (needs pass Q's D_i)
     if (which != 3)
-      hipLaunchKernelGGL((tattn_bwd_q_kernel<NKT, NW, NKC, 4, HD>), grid, blk, lds, st, qkv, o, dout, dqkv, s, map, C, heads, groups, n_work,
+      hipLaunchKernelGGL((tattn_bwd_q_kernel<NKT, NW, NKC, 4, HD, PAD>), grid, blk, lds, st, qkv, o, dout, dqkv, s, map, C, heads, groups, n_work,
                          amax_qkv, amax_do, amax_out);
     if (which != 2)
-      hipLaunchKernelGGL((tattn_bwd_kv_kernel<NKT, NW, NKC_KV, WPE_KV, HD>), grid, blk, lds_kv, st, qkv, dout, dqkv, (const TAStat*)s, map, C, heads, groups,
+      hipLaunchKernelGGL((tattn_bwd_kv_kernel<NKT, NW, NKC_KV, WPE_KV, HD, PAD>), grid, blk, lds_kv, st, qkv, dout, dqkv, (const TAStat*)s, map, C, heads, groups,
                          n_work, amax_qkv, amax_do, amax_out);
   }
   return 0;
 }
 
-int ta_dispatch(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats, int n_seq,
-                SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
-                hipStream_t st, TAOperand po = {nullptr, 0, 0, nullptr}) {
-  const int n = map.n_tok;
-  if (heads < 1 || C % heads != 0 || C % 4 != 0 || n < 1 || n > 1024 || !amax_qkv || !stats) return -2;
-  if (po.op && (po.Tp < po.T || !po.unscale || C % 32 != 0)) return -1;
+// The padded forms are compiled in a translation unit of their own (train_attn_pad.hip includes this file with D3DP_TA_PAD_TU
+// defined): beside them in one module the compiler allocated registers differently in 15 of the 57 existing instantiations; apart,
+// every one of those keeps its device code instruction for instruction (profiles/train_widths.md).
+#ifdef D3DP_TA_PAD_TU
+#define TA_CASE(NKT_, HD_) return ta_launch<NKT_, HD_, true>(which, qkv, o, dout, out, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st);
+#else
 #define TA_CASE(NKT_, HD_) return ta_launch<NKT_, HD_>(which, qkv, o, dout, out, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st, po);
+#endif
 #define TA_LENGTHS(HD_)              \
   if (n <= 32) { TA_CASE(2, HD_) }   \
   if (n <= 64) { TA_CASE(4, HD_) }   \
@@ -640,21 +673,53 @@ int ta_dispatch(int which, const float* qkv, const float* o, const float* dout, 
   if (n <= 256) { TA_CASE(16, HD_) } \
   if (n <= 512) { TA_CASE(32, HD_) } \
   TA_CASE(64, HD_)
-  switch (C / heads) {                                 // the head dims these kernels are instantiated for (ctx.h mfma_head_dim)
+
+#ifndef D3DP_TA_PAD_TU
+int ta_dispatch(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats, int n_seq,
+                SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
+                hipStream_t st, TAOperand po = {nullptr, 0, 0, nullptr}) {
+  const int n = map.n_tok;
+  if (heads < 1 || C % heads != 0 || C % 4 != 0 || n < 1 || n > 1024 || !amax_qkv || !stats) return -2;
+  if (po.op && (po.Tp < po.T || !po.unscale || C % 32 != 0)) return -1;
+  switch (C / heads) {                                 // the head dims these kernels take (ctx.h mfma_head_dim, train_attn_head_dim)
     case 64: { TA_LENGTHS(64) }
     case 32: { TA_LENGTHS(32) }
     case 16: { TA_LENGTHS(16) }
-    default: return -2;                                // (head dim 8, or a width outside the instantiated set: the fp32 kernels of train.hip)
+    // `-cs` 448 / 384 / 320 and 192 with the model's 8 heads: the head padded to 64 / 32 inside the images (PAD)
+    case 56: case 48: case 40: case 24:
+      if (po.op) return -1;                            // (no operand rows from the padded forms)
+      return d3dp_train_attn_x2_padded(which, qkv, o, dout, out, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st);
+    default: return -2;                                // (head dim 8 and every other: the fp32 kernels of train.hip)
   }
-#undef TA_LENGTHS
-#undef TA_CASE
 }
+#endif
 
 }  // namespace
 
+#ifdef D3DP_TA_PAD_TU
+// which: 0 = forward, 1 = both backward passes, 2 = pass Q alone, 3 = pass KV alone (ta_dispatch has checked everything else)
+int d3dp_train_attn_x2_padded(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats,
+                              int n_seq, SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do,
+                              unsigned* amax_out, hipStream_t st) {
+  const int n = map.n_tok, hd = heads > 0 ? C / heads : 0;
+  if (heads < 1 || hd * heads != C || n < 1 || n > 1024 || !amax_qkv || !stats) return -2;
+  if (hd == 24) { TA_LENGTHS(32) }
+  if (hd == 40 || hd == 48 || hd == 56) {
+    // (33 .. 64 tokens take the 128-token instantiation: padded, pass Q of the 64-token one needs 6 dwords of scratch where its
+    //  unpadded counterpart needs 3 -- the 128-token one needs the 5 of its counterpart -- and a few idle waves cost less)
+    if (n <= 32) { TA_CASE(2, 64) }
+    if (n <= 128) { TA_CASE(8, 64) }
+    if (n <= 256) { TA_CASE(16, 64) }
+    if (n <= 512) { TA_CASE(32, 64) }
+    TA_CASE(64, 64)
+  }
+  return -2;
+}
+#else
 size_t d3dp_train_attn_x2_stats_bytes(int n_seq, int n_tok, int heads) { return (size_t)n_seq * heads * n_tok * sizeof(TAStat); }
 
-// out [T, C] = softmax(q k^T HD^-0.5) v per (sequence, head), HD = C / heads in {64, 32, 16} (-2 for any other); stats: n_seq x heads x n_tok (L, D) pairs for the backward pass;
+// out [T, C] = softmax(q k^T HD^-0.5) v per (sequence, head), HD = C / heads in {64, 32, 16} or, with the head padded inside the kernels,
+// {24, 40, 48, 56} (-2 for any other; the padded forms write no operand rows: -1 if `op` is asked of them); stats: n_seq x heads x n_tok (L, D) pairs for the backward pass;
 // amax_qkv: absmax slot of the whole qkv tensor (the qkv Linear's epilogue); amax_out (optional): absmax slot of `out`
 // op (optional): the output also as split operand rows [Tp][2 C] (rows T .. Tp - 1 zero; T = all token rows of the batch) at the
 // scale of q / k / v, op_unscale[0] = 1 / scale, amax_out[0] = the bound (the qkv absmax) -- see tattn_fwd_kernel
@@ -675,3 +740,6 @@ int d3dp_train_attn_x2_bwd(const float* qkv, const float* o, const float* dout, 
   if (!qkv || !o || !dout || !dqkv || !amax_do || part < 0 || part > 2) return -1;
   return ta_dispatch(1 + part, qkv, o, dout, nullptr, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st);
 }
+#endif
+#undef TA_LENGTHS
+#undef TA_CASE

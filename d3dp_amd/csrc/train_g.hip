@@ -5,9 +5,13 @@
 // Any other width trains on the fp32 path of capi_train.hip (D3DP_TRAIN_IMPL=f32's path: gemm_f32_kernel forward / dgrad / split-K wgrad,
 // fp32 row attention forward, VALU attention backward with a run-time head dim) through the kernels below: the formulas of
 // train.hip's kernels (same order per row: two-pass statistics, 1 / C as a multiplied reciprocal, fma with gamma / beta; the
-// LayerNorm backward in the same three steps), the width an argument, a lane's NVM slots masked behind it.  No operand rows, no
-// absmax (the fp32 path has no operand scales).  [dgamma | dbeta] leave as per-workgroup partial rows like in train.hip: the
-// fixed-order reduction of capi_train.hip adds them -- no float atomics here either.
+// LayerNorm backward in the same three steps), the width an argument, a lane's NVM slots masked behind it.  No operand rows.
+// [dgamma | dbeta] leave as per-workgroup partial rows like in train.hip: the fixed-order reduction of capi_train.hip adds them -- no
+// float atomics here either.
+// The widths 192 / 320 / 384 / 448 also train on split-fp16 Linears (D3DP_TRAIN_IMPL=f16x2, capi.hip): the three kernels in front of
+// a Linear's operand pass then leave the absmax of the tensor that pass will split in `amax`, as their width-templated twins do
+// (train.hip block_amax_commit: one integer atomicMax per workgroup on the bit pattern of a non-negative float).  amax null -- the
+// fp32 path, which has no operand scales -- stores exactly what these kernels stored before they had the argument.
 #include "common.h"
 #include "kernels.h"
 
@@ -48,17 +52,29 @@ template <int NVM> struct GRow {
 
 constexpr int kRowBlocksG = 1024;
 
+// (train.hip block_amax_commit; every thread of the 256 must arrive)
+__device__ __forceinline__ void block_amax_commit_g(float m, unsigned* amax) {
+  __shared__ float part_amax[4];
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) part_amax[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    atomicMax(amax, __float_as_uint(fmaxf(fmaxf(part_amax[0], part_amax[1]), fmaxf(part_amax[2], part_amax[3]))));
+}
+
 // x_out = x_in + m[sample] y ; xn = LN(x_out)                                                    (train.hip add_mask_ln_kernel)
 template <int NVM>
 __global__ __launch_bounds__(256) void add_mask_ln_g_kernel(const float* __restrict__ x_in, const float* __restrict__ y,
                                                             const float* __restrict__ mask, int axis, int F, int J,
                                                             const float* __restrict__ w, const float* __restrict__ b, float eps,
-                                                            float* __restrict__ x_out, float* __restrict__ xn, int T, int C) {
+                                                            float* __restrict__ x_out, float* __restrict__ xn,
+                                                            unsigned* __restrict__ amax, int T, int C) {
   using R = GRow<NVM>;
   const int lane = threadIdx.x & 63;
   float wl[NVM], bl[NVM];
   R::load(w, C, lane, wl);
   R::load(b, C, lane, bl);
+  float am = 0.f;
   for (int tok = blockIdx.x * 4 + (threadIdx.x >> 6); tok < T; tok += gridDim.x * 4) {
     const float m = mask ? mask[sample_of(tok, axis, F, J)] : 1.0f;
     float v[NVM], yy[NVM];
@@ -71,7 +87,12 @@ __global__ __launch_bounds__(256) void add_mask_ln_g_kernel(const float* __restr
     R::stats(v, eps, C, lane, mean, rstd);
     R::affine(v, mean, rstd, wl, bl, C, lane);
     if (xn) R::store(xn + (size_t)tok * C, C, lane, v);
+    if (amax) {                                          // (masked slots hold 0)
+#pragma unroll
+      for (int i = 0; i < NVM; ++i) am = fmaxf(am, fabsf(v[i]));
+    }
   }
+  if (amax) block_amax_commit_g(am, amax);               // (uniform over the launch)
 }
 
 // x_out = x_in + m[sample] y ; x_next = LN_a(x_out) (+ pos[f]) ; xn = LN_b(x_next)              (train.hip add_mask_ln2_kernel)
@@ -81,7 +102,8 @@ __global__ __launch_bounds__(256) void add_mask_ln2_g_kernel(const float* __rest
                                                              const float* __restrict__ wa, const float* __restrict__ ba, float eps_a,
                                                              const float* __restrict__ pos, const float* __restrict__ wb,
                                                              const float* __restrict__ bb, float eps_b, float* __restrict__ x_out,
-                                                             float* __restrict__ x_next, float* __restrict__ xn, int T, int C) {
+                                                             float* __restrict__ x_next, float* __restrict__ xn,
+                                                             unsigned* __restrict__ amax, int T, int C) {
   using R = GRow<NVM>;
   const int lane = threadIdx.x & 63;
   float wal[NVM], bal[NVM], wbl[NVM], bbl[NVM];
@@ -90,6 +112,7 @@ __global__ __launch_bounds__(256) void add_mask_ln2_g_kernel(const float* __rest
 #pragma unroll
   for (int i = 0; i < NVM; ++i) { wbl[i] = 0.f; bbl[i] = 0.f; }
   if (wb) { R::load(wb, C, lane, wbl); R::load(bb, C, lane, bbl); }
+  float am = 0.f;
   for (int tok = blockIdx.x * 4 + (threadIdx.x >> 6); tok < T; tok += gridDim.x * 4) {
     const float m = mask ? mask[sample_of(tok, axis, F, J)] : 1.0f;
     float v[NVM], yy[NVM];
@@ -108,12 +131,17 @@ __global__ __launch_bounds__(256) void add_mask_ln2_g_kernel(const float* __rest
       for (int i = 0; i < NVM; ++i) v[i] += pp[i];
     }
     R::store(x_next + (size_t)tok * C, C, lane, v);
-    if (wb && xn) {
+    if (wb && (xn || amax)) {                            // (xn null: only the absmax of LN_b's output is wanted)
       R::stats(v, eps_b, C, lane, mean, rstd);
       R::affine(v, mean, rstd, wbl, bbl, C, lane);
-      R::store(xn + (size_t)tok * C, C, lane, v);
+      if (xn) R::store(xn + (size_t)tok * C, C, lane, v);
+      if (amax) {
+#pragma unroll
+        for (int i = 0; i < NVM; ++i) am = fmaxf(am, fabsf(v[i]));
+      }
     }
   }
+  if (amax) block_amax_commit_g(am, amax);
 }
 
 // y = LN(x) (+ pos[f])                                                                           (train.hip ln_pos_kernel)
@@ -150,7 +178,8 @@ __global__ __launch_bounds__(256) void ln_bwd2_g_kernel(const float* dy, const f
                                                         float eps_b, const float* __restrict__ dres, float* __restrict__ g_out,
                                                         const float* __restrict__ xa, const float* __restrict__ wa, float eps_a,
                                                         float* __restrict__ dx, const float* __restrict__ mask, int axis, int F, int J,
-                                                        float* dxm, float* __restrict__ part_b, float* __restrict__ part_a, int T, int C) {
+                                                        float* dxm, unsigned* __restrict__ amax, float* __restrict__ part_b,
+                                                        float* __restrict__ part_a, int T, int C) {
   using R = GRow<NVM>;
   __shared__ float sg[4][NVM * 64], sb[4][NVM * 64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -165,6 +194,7 @@ __global__ __launch_bounds__(256) void ln_bwd2_g_kernel(const float* dy, const f
 #pragma unroll
     for (int i = 0; i < NVM; ++i) { aga[i] = 0.f; aba[i] = 0.f; }
   }
+  float am = 0.f;
   for (int tok = blockIdx.x * 4 + wv; tok < T; tok += gridDim.x * 4) {
     float v[NVM], d[NVM];
     R::load(xb + (size_t)tok * C, C, lane, v);
@@ -212,11 +242,11 @@ __global__ __launch_bounds__(256) void ln_bwd2_g_kernel(const float* dy, const f
       for (int i = 0; i < NVM; ++i) d[i] = (i * 64 + lane < C) ? rstd * (d[i] - s1 - va[i] * s2) : 0.f;
     }
     R::store(dx + (size_t)tok * C, C, lane, d);
-    if (dxm) {
+    if (dxm || amax) {                                   // (the absmax is that of the DropPath-scaled gradient: the next dY)
       const float k = mask ? mask[sample_of(tok, axis, F, J)] : 1.0f;
 #pragma unroll
-      for (int i = 0; i < NVM; ++i) d[i] *= k;
-      R::store(dxm + (size_t)tok * C, C, lane, d);
+      for (int i = 0; i < NVM; ++i) { d[i] *= k; am = fmaxf(am, fabsf(d[i])); }
+      if (dxm) R::store(dxm + (size_t)tok * C, C, lane, d);
     }
   }
   // this workgroup's [dgamma | dbeta] rows: the four waves' sums in the order 0, 1, 2, 3
@@ -233,6 +263,7 @@ __global__ __launch_bounds__(256) void ln_bwd2_g_kernel(const float* dy, const f
   };
   flush(agb, abb, part_b);
   if constexpr (TWO) flush(aga, aba, part_a);
+  if (amax) block_amax_commit_g(am, amax);
 }
 
 // pred[t, o] = sum_c z[t, c] W[o, c] + b[o]  (o < 3)                                             (train.hip head_linear_kernel)
@@ -332,18 +363,18 @@ int row_blocks_g(int T) { return (T + 3) / 4 < kRowBlocksG ? (T + 3) / 4 : kRowB
   else { constexpr int NVM = 16; __VA_ARGS__; }
 
 int d3dp_train_g_add_mask_ln(const float* x_in, const float* y, const float* mask, int axis, int F, int J, const float* w,
-                             const float* b, float eps, float* x_out, float* xn, int T, int C, hipStream_t st) {
+                             const float* b, float eps, float* x_out, float* xn, unsigned* amax, int T, int C, hipStream_t st) {
   if (!w || !b || !x_out) return -1;
   TRAIN_DISPATCH_G(C, hipLaunchKernelGGL((add_mask_ln_g_kernel<NVM>), dim3(row_blocks_g(T)), dim3(256), 0, st, x_in, y, mask, axis, F, J,
-                                         w, b, eps, x_out, xn, T, C))
+                                         w, b, eps, x_out, xn, amax, T, C))
   return 0;
 }
 int d3dp_train_g_add_mask_ln2(const float* x_in, const float* y, const float* mask, int axis, int F, int J, const float* wa,
                               const float* ba, float eps_a, const float* pos, const float* wb, const float* bb, float eps_b,
-                              float* x_out, float* x_next, float* xn, int T, int C, hipStream_t st) {
+                              float* x_out, float* x_next, float* xn, unsigned* amax, int T, int C, hipStream_t st) {
   if (!wa || !ba || !x_out || !x_next || (xn && !wb) || (wb && !bb)) return -1;
   TRAIN_DISPATCH_G(C, hipLaunchKernelGGL((add_mask_ln2_g_kernel<NVM>), dim3(row_blocks_g(T)), dim3(256), 0, st, x_in, y, mask, axis, F, J,
-                                         wa, ba, eps_a, pos, wb, bb, eps_b, x_out, x_next, xn, T, C))
+                                         wa, ba, eps_a, pos, wb, bb, eps_b, x_out, x_next, xn, amax, T, C))
   return 0;
 }
 int d3dp_train_g_ln_pos(const float* x, const float* w, const float* b, float eps, const float* pos, int F, int J, float* y, int T,
@@ -353,13 +384,13 @@ int d3dp_train_g_ln_pos(const float* x, const float* w, const float* b, float ep
 }
 int d3dp_train_g_ln_bwd(const float* dy, const float* xb, const float* wb, float eps_b, const float* dres, float* g_out,
                         const float* xa, const float* wa, float eps_a, float* dx, const float* mask, int axis, int F, int J,
-                        float* dxm, float* part_b, float* part_a, int T, int C, int blocks, hipStream_t st) {
+                        float* dxm, unsigned* amax, float* part_b, float* part_a, int T, int C, int blocks, hipStream_t st) {
   if (xa) {
     TRAIN_DISPATCH_G(C, hipLaunchKernelGGL((ln_bwd2_g_kernel<NVM, true>), dim3(blocks), dim3(256), 0, st, dy, xb, wb, eps_b, dres, g_out, xa,
-                                           wa, eps_a, dx, mask, axis, F, J, dxm, part_b, part_a, T, C))
+                                           wa, eps_a, dx, mask, axis, F, J, dxm, amax, part_b, part_a, T, C))
   } else {
     TRAIN_DISPATCH_G(C, hipLaunchKernelGGL((ln_bwd2_g_kernel<NVM, false>), dim3(blocks), dim3(256), 0, st, dy, xb, wb, eps_b, dres, nullptr,
-                                           nullptr, nullptr, 0.f, dx, mask, axis, F, J, dxm, part_b, nullptr, T, C))
+                                           nullptr, nullptr, 0.f, dx, mask, axis, F, J, dxm, amax, part_b, nullptr, T, C))
   }
   return 0;
 }

@@ -526,7 +526,12 @@ class MixSTE2(nn.Module):
     def train_arithmetic(self) -> str:
         """What the training step's Linears run on (bench.py reports it next to the step time)."""
         ta = os.environ.get("D3DP_TRAIN_ATTN", "")
-        x2_ok = self.embed_dim // self.num_heads in (64, 32, 16) and self.num_frame <= 1024   # (ctx.h TrainPath)
+        hd = self.embed_dim // self.num_heads
+        inst = self.embed_dim in (64, 128, 256, 512) and hd in (8, 16, 32, 64) and self.hidden >= 64 and self.hidden % 64 == 0
+        # D3DP_TRAIN_IMPL=f16x2 (capi.hip d3dp_create): the split-fp16 step at channels 192 / 320 / 384 / 448, heads padded to 32 / 64
+        widths = (not inst and os.environ.get("D3DP_TRAIN_IMPL") == "f16x2" and self.embed_dim in (192, 320, 384, 448)
+                  and hd % 8 == 0 and hd <= 64 and self.hidden >= 64 and self.hidden % 64 == 0)
+        x2_ok = hd in ((64, 32, 16, 56, 48, 40, 24) if widths else (64, 32, 16)) and self.num_frame <= 1024   # (ctx.h TrainPath)
         if ta == "f32" or not x2_ok:
             attn = "fp32 attention (fp32 MFMA: temporal forward, backward of both axes; spatial forward on the VALU)"
         elif ta == "x2t":
@@ -537,8 +542,12 @@ class MixSTE2(nn.Module):
                     "power-of-two scale for dS)")
         if os.environ.get("D3DP_TRAIN_ATTN_BWD", "")[:1] == "v":
             attn += "; D3DP_TRAIN_ATTN_BWD=valu: every fp32 attention backward on the VALU kernels instead"
-        hd = self.embed_dim // self.num_heads
-        inst = self.embed_dim in (64, 128, 256, 512) and hd in (8, 16, 32, 64) and self.hidden >= 64 and self.hidden % 64 == 0
+        if widths:
+            pad = f"; head dim {hd} padded to {32 if hd <= 32 else 64} inside the attention kernels' LDS images" if hd in (56, 48, 40, 24) else ""
+            return (f"split-fp16 route of D3DP_TRAIN_IMPL=f16x2 (cs = {self.embed_dim}): split-fp16 Linears (three fp16-MFMA passes, fp32 "
+                    "accumulate, device-side operand scales; an operand pass in front of every Linear, weight gradients as TN products "
+                    "where N % 256 == 0 and K % 128 == 0 and on transposed operands elsewhere, partial tiles summed in a fixed order; "
+                    "run-time-width row kernels that leave the operand absmax), " + attn + pad)
         if not inst:       # (include/d3dp_hip.h d3dp_create: a width outside the instantiated set trains on the fp32 path)
             return (f"fp32 path of a width outside {{64, 128, 256, 512}} (cs = {self.embed_dim}): fp32-MFMA Linears (weight gradients split-K, "
                     "chunks added in a fixed order), fp32 row attention forward, VALU attention backward with a run-time head dim, "

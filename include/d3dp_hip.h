@@ -155,8 +155,9 @@ D3DP_API const char* d3dp_last_error(void);
  *   any other width the reference's 8 heads divide (common/arguments.py:49, mixste.py:46-62) with channels <= 1024,
  *                         head dim % 4 == 0 and <= 128, hidden % 4 == 0: D3DP_MODE_EXACT on the fp32 implementation
  *                         (fp32-MFMA Linears, fp32 row attention, run-time-width row kernels; d3dp_exact_scales reports
- *                         implementation 2): the same 1e-3 mm tolerance at roughly a fifth of the throughput.  FAST and FAST16
- *                         contexts exist for the instantiated widths only.
+ *                         implementation 2): the same 1e-3 mm tolerance at roughly a fifth of the throughput; and
+ *                         D3DP_MODE_TRAIN on the fp32 path of the training step, with the token limits listed under "What a
+ *                         D3DP_MODE_TRAIN context takes" below.  FAST and FAST16 contexts exist for the instantiated widths only.
  *   channels in {192, 320, 384, 448} with head dim % 8 == 0 and <= 64 and hidden % 64 == 0, D3DP_MODE_EXACT, with
  *                         D3DP_EXACT_IMPL=f16x2 in the environment of d3dp_create (OPT-IN: without the switch such a context
  *                         launches the fp32 implementation above, bit for bit as before): the split-fp16 implementation of the
@@ -181,7 +182,21 @@ D3DP_API const char* d3dp_last_error(void);
  *                         (what D3DP_TRAIN_IMPL=f32 selects for the instantiated widths: fp32-MFMA Linears, run-time-width row
  *                         kernels, VALU attention backward with a run-time head dim).  There d3dp_create itself refuses
  *                         max(frames, joints) > 256 tokens, and > 153 tokens at head dims above 64 (two whole-sequence images
- *                         of the capacity head dim + the statistics in 160 KiB of LDS).
+ *                         of the capacity head dim + the statistics in 160 KiB of LDS);
+ *   channels in {192, 320, 384, 448} with head dim % 8 == 0 and <= 64 and hidden % 64 == 0, with D3DP_TRAIN_IMPL=f16x2 in the
+ *                         environment of d3dp_create (OPT-IN: without the switch such a context is the line above, bit for bit
+ *                         as before): the split-fp16 training step of the instantiated widths -- every Linear (forward, dgrad,
+ *                         wgrad) on split-fp16 operands, the run-time-width row kernels leaving the operand absmax, and at head
+ *                         dims 24 / 40 / 48 / 56 (8 heads) the attention of both axes on the split-fp16 kernels with the head
+ *                         padded to 32 / 64 inside their LDS images (no weight, gradient or workspace region is padded;
+ *                         d3dp_train_workspace_bytes is unchanged): every frames <= 1024 and joints <= 256.  Head dims 64, 32
+ *                         and 16 there (3, 6, 12 heads at 192, ...) run the unpadded kernels; head dim 8 and
+ *                         D3DP_TRAIN_ATTN=f32|x2t beside the switch keep split Linears around the fp32 attention, as `-cs 64`
+ *                         does, and d3dp_train_forward answers D3DP_ENOTSUP beyond 256 frames.  At an instantiated width the
+ *                         value names the default.  A TRAIN context of any other width cannot honour it: D3DP_ENOTSUP, decided
+ *                         before the device is looked for.  Contexts of the other modes do not read D3DP_TRAIN_IMPL, and
+ *                         D3DP_EXACT_IMPL=f16x2 keeps refusing a TRAIN context at these widths: a process that keeps a train
+ *                         and an eval context sets each switch around the creation of its own context.
  * A D3DP_MODE_TRAIN context whose backward pass overlaps (split-fp16 Linears, D3DP_TRAIN_OVERLAP not 0) gets its second stream
  * and three events here, so that d3dp_train_backward never creates anything. */
 D3DP_API int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out);
@@ -312,8 +327,9 @@ D3DP_API int d3dp_jpma_ex(const float* pred, const float* traj, const float* cam
  * stream) -- see Conventions: the caller orders against `stream` alone.
  * No gradient is accumulated with float atomics: the same inputs give the same bits.
  * Clip length: any F <= 1024 like inference (reference common/arguments.py:58); beyond 256 frames the step needs its split-fp16
- * attention kernels (head dims 64, 32 and 16; keys / queries through LDS in chunks) -- head dim 8 and the fp32 cross-check
- * implementations (D3DP_TRAIN_IMPL=f32, D3DP_TRAIN_ATTN=f32|x2t) hold whole sequences and answer D3DP_ENOTSUP there (d3dp_create). */
+ * attention kernels (head dims 64, 32 and 16, and 24 / 40 / 48 / 56 under D3DP_TRAIN_IMPL=f16x2; keys / queries through LDS in
+ * chunks) -- head dim 8, the fp32 path of the other widths and the fp32 cross-check implementations (D3DP_TRAIN_IMPL=f32,
+ * D3DP_TRAIN_ATTN=f32|x2t) hold whole sequences and answer D3DP_ENOTSUP there (d3dp_create). */
 D3DP_API int d3dp_train_workspace_bytes(const d3dp_ctx* ctx, int32_t B, size_t* bytes);
 D3DP_API int d3dp_train_forward(d3dp_ctx* ctx, const float* x2d, const float* x3d, const int64_t* t, const float* masks, float* out,
                        int32_t B, void* workspace, size_t workspace_bytes, void* stream);
