@@ -25,6 +25,22 @@
 #include "ta_common.h"
 #include "attn_frag.h"
 
+// The padded forms (attention_fast_pad.hip includes this file with D3DP_FAST_PAD_TU defined): the same three kernels on rows whose heads
+// were padded with zero columns from a TRUE head dim HDT = 24 to HD = 32, or from 40 / 48 / 56 to 64 -- channels 192 / 320 / 384 / 448
+// with the model's 8 heads in a FAST / FAST16 context under D3DP_FAST_IMPL=mfma (ctx.h hdp).  The zero columns add nothing to S^T and
+// come back as exact zeros of O^T; HDT enters the exponent alone.  There every kernel and launcher template below carries HDT as one
+// more parameter; here the AF_ macros expand to nothing, the instantiations are the ones this file always had and keep their device
+// code (profiles/fast_widths.md).
+#ifdef D3DP_FAST_PAD_TU
+#define AF_HDT_PARAM , int HDT
+#define AF_HDT_ARG , HDT
+#define AF_SCALE (HDT == 24 ? 0.20412414523193151f : HDT == 40 ? 0.15811388300841897f : HDT == 48 ? 0.14433756729740643f : 0.1336306209562122f)
+#else
+#define AF_HDT_PARAM
+#define AF_HDT_ARG
+#define AF_SCALE (HD == 64 ? 0.125f : HD == 32 ? 0.17677669529663689f : 0.25f)
+#endif
+
 namespace {
 
 // What follows from the head dim: bytes per K / V row, log2 of its 16-byte slots, and the fragments of S^T = K Q^T -- NQ per
@@ -63,14 +79,17 @@ __device__ __forceinline__ void pv_chunks(const FragBasesT<HD>& fb, const typena
 // ONLINE (the chunked-key kernel below): the resident keys are one chunk of a longer row.  `mrun` is the running row maximum
 // in base-2 logit units (-inf before the first chunk); the probabilities are formed against the larger of it and this chunk's
 // maximum, and `o` / `denom` -- the sums over the earlier chunks -- are rescaled to that maximum and added to.
-template <typename E, int HD, int NKT, bool ONLINE>
+template <typename E, int HD, int NKT, bool ONLINE AF_HDT_PARAM>
 __device__ __forceinline__ void attn_tile(const FragBasesT<HD>& fb, const typename Head<E, HD>::frag (&q)[Head<E, HD>::NQ], int n,
                                           int lane, f32x4 (&o)[HD / 16], float& denom, float& mrun) {
   using e8 = typename Op2<E>::x8;
   using kfrag = typename Head<E, HD>::frag;
   constexpr int TILE = 16 * Head<E, HD>::ROWB;           // bytes of one 16-key tile of the K image
   const int fg = lane >> 4;
-  const float cexp = (HD == 64 ? 0.125f : HD == 32 ? 0.17677669529663689f : 0.25f) * 1.44269504088896340736f;   // HD^-0.5 * log2(e)
+#ifdef D3DP_FAST_PAD_TU
+  static_assert((HD == 32 && HDT == 24) || (HD == 64 && (HDT == 40 || HDT == 48 || HDT == 56)), "AF_SCALE holds these true head dims");
+#endif
+  const float cexp = AF_SCALE * 1.44269504088896340736f;   // HD^-0.5 * log2(e) (padded heads: of the true head dim)
   f32x4 s[NKT];
 #pragma unroll
   for (int t = 0; t < NKT; ++t) {
@@ -129,11 +148,11 @@ __device__ __forceinline__ void attn_tile(const FragBasesT<HD>& fb, const typena
   }
   pv_chunks<E, HD, NKT, 0>(fb, pf, o);
 }
-template <typename E, int HD, int NKT>
+template <typename E, int HD, int NKT AF_HDT_PARAM>
 __device__ __forceinline__ void attn_tile(const FragBasesT<HD>& fb, const typename Head<E, HD>::frag (&q)[Head<E, HD>::NQ], int n,
                                           int lane, f32x4 (&o)[HD / 16], float& denom) {
   float m = 0.f;
-  attn_tile<E, HD, NKT, false>(fb, q, n, lane, o, denom, m);
+  attn_tile<E, HD, NKT, false AF_HDT_ARG>(fb, q, n, lane, o, denom, m);
 }
 
 // rows [0, n) of K and V (2 HD bytes per row for this head = HD / 8 16-byte slots) -> swizzled LDS images; rows [n, NK) zeroed.
@@ -154,7 +173,7 @@ __device__ __forceinline__ void stage_kv(const E* __restrict__ kbase, size_t row
   }
 }
 
-template <typename E, int HD, int NKT>   // temporal axis: one workgroup per (sequence, head), 8 waves share the K/V images
+template <typename E, int HD, int NKT AF_HDT_PARAM>   // temporal axis: one workgroup per (sequence, head), 8 waves share the K/V images
 __global__ __launch_bounds__(512, 4) void attn_temporal2_bf16_kernel(const E* __restrict__ qkv, E* __restrict__ out,
                                                                      SeqMap map, int C, int heads) {
   using e4 = typename Op2<E>::x4;
@@ -191,7 +210,7 @@ __global__ __launch_bounds__(512, 4) void attn_temporal2_bf16_kernel(const E* __
     const int q = qt * 16 + fi;
     f32x4 o[HD / 16];
     float denom;
-    attn_tile<E, HD, NKT>(fb, qf[i], n, lane, o, denom);
+    attn_tile<E, HD, NKT AF_HDT_ARG>(fb, qf[i], n, lane, o, denom);
     if (q < n) {
       const float inv = 1.0f / denom;
       E* dst = out + (size_t)(base + q * ts) * C + head * HD + fg * 4;
@@ -220,7 +239,7 @@ __global__ __launch_bounds__(512, 4) void attn_temporal2_bf16_kernel(const E* __
 #ifndef D3DP_FAST_LONG_NKT
 #define D3DP_FAST_LONG_NKT 8
 #endif
-template <typename E, int HD, int NKT>
+template <typename E, int HD, int NKT AF_HDT_PARAM>
 __global__ __launch_bounds__(512, NKT == 8 ? 4 : 2) void attn_long2_bf16_kernel(const E* __restrict__ qkv, E* __restrict__ out,
                                                                                   SeqMap map, int C, int heads, int groups,
                                                                                   int n_work) {
@@ -291,7 +310,7 @@ __global__ __launch_bounds__(512, NKT == 8 ? 4 : 2) void attn_long2_bf16_kernel(
       if (active) {
         const int off = (c & 1) * BUF, rem = n - c * NK; // (rem >= 1: the chunk holds a key, its maximum is finite)
         const FragBasesT<HD> fb = make_frag_bases<HD>(smem + off, smem + off + IMG, lane);
-        attn_tile<E, HD, NKT, true>(fb, qf, rem, lane, o, lrun, mrun);
+        attn_tile<E, HD, NKT, true AF_HDT_ARG>(fb, qf, rem, lane, o, lrun, mrun);
       }
       if (c + 1 < n_chunks) commit(smem + ((c + 1) & 1) * BUF);
     }
@@ -309,7 +328,7 @@ __global__ __launch_bounds__(512, NKT == 8 ? 4 : 2) void attn_long2_bf16_kernel(
 
 // spatial axis (<= 32 tokens per sequence): one WAVE per (sequence, head) with a private K/V image of 32 rows each (8 KiB at
 // head dim 64, 4 / 2 KiB at 32 / 16); a 256-thread workgroup covers 4 heads of one sequence.
-template <typename E, int HD>
+template <typename E, int HD AF_HDT_PARAM>
 __global__ __launch_bounds__(256) void attn_spatial_bf16_kernel(const E* __restrict__ qkv, E* __restrict__ out,
                                                                 int n_prob, SeqMap map, int C, int heads) {
   using e4 = typename Op2<E>::x4;
@@ -343,7 +362,7 @@ __global__ __launch_bounds__(256) void attn_spatial_bf16_kernel(const E* __restr
     const int q = qt * 16 + fi;
     f32x4 o[HD / 16];
     float denom;
-    attn_tile<E, HD, 2>(fb, qf[qt], n, lane, o, denom);
+    attn_tile<E, HD, 2 AF_HDT_ARG>(fb, qf[qt], n, lane, o, denom);
     if (q < n) {
       const float inv = 1.0f / denom;
       E* dst = out + (size_t)(base + q * ts) * C + head * HD + fg * 4;
@@ -356,11 +375,11 @@ __global__ __launch_bounds__(256) void attn_spatial_bf16_kernel(const E* __restr
   }
 }
 
-template <typename E, int HD, int NKT>
+template <typename E, int HD, int NKT AF_HDT_PARAM>
 int launch_temporal2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
   constexpr int NK = 16 * NKT;
   const size_t lds = (size_t)NK * 2 * Head<E, HD>::ROWB;           // the K and the V image
-  auto kern = attn_temporal2_bf16_kernel<E, HD, NKT>;
+  auto kern = attn_temporal2_bf16_kernel<E, HD, NKT AF_HDT_ARG>;
   static PerDeviceOnce once;                          // (one per template instantiation = per kernel)
   if (once.get([&](int) { return d3dp_lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024); }) < 0) return -3;
   hipLaunchKernelGGL(kern, dim3(n_seq * heads), dim3(512), lds, st, (const E*)qkv, (E*)out, map, C, heads);
@@ -369,12 +388,12 @@ int launch_temporal2(const void* qkv, void* out, int n_seq, SeqMap map, int C, i
 
 // n_tok > 256: the chunked-key kernel; a persistent grid of two workgroups per CU (64 KiB of LDS each at head dim 64, 32 / 16 KiB
 // at 32 / 16: the register budget of its launch bounds, not the LDS, is what holds two)
-template <typename E, int HD>
+template <typename E, int HD AF_HDT_PARAM>
 int launch_long2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
   constexpr int NKT = D3DP_FAST_LONG_NKT;
   static_assert(NKT == 8 || NKT == 16, "chunks of 128 or 256 keys");
   const int groups = ((map.n_tok + 15) / 16 + 7) / 8, n_work = n_seq * heads * groups;
-  auto kern = attn_long2_bf16_kernel<E, HD, NKT>;
+  auto kern = attn_long2_bf16_kernel<E, HD, NKT AF_HDT_ARG>;
   static PerDeviceOnce once;                          // (one per template instantiation = per kernel)
   const int cus = once.get([&](int dev) {
     const int r = d3dp_lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024);
@@ -388,31 +407,52 @@ int launch_long2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int h
   return 0;
 }
 
-template <typename E, int HD>
+template <typename E, int HD AF_HDT_PARAM>
 int attn_temporal2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
   const int n = map.n_tok;
-  if (n > 256) return launch_long2<E, HD>(qkv, out, n_seq, map, C, heads, st);
-  if (n <= 32) return launch_temporal2<E, HD, 2>(qkv, out, n_seq, map, C, heads, st);
-  if (n <= 64) return launch_temporal2<E, HD, 4>(qkv, out, n_seq, map, C, heads, st);
-  if (n <= 128) return launch_temporal2<E, HD, 8>(qkv, out, n_seq, map, C, heads, st);
-  return launch_temporal2<E, HD, 16>(qkv, out, n_seq, map, C, heads, st);
+  if (n > 256) return launch_long2<E, HD AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st);
+  if (n <= 32) return launch_temporal2<E, HD, 2 AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st);
+  if (n <= 64) return launch_temporal2<E, HD, 4 AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st);
+  if (n <= 128) return launch_temporal2<E, HD, 8 AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st);
+  return launch_temporal2<E, HD, 16 AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st);
 }
 
-template <typename E, int HD>
+template <typename E, int HD AF_HDT_PARAM>
 int attn_spatial(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
   const int n_prob = n_seq * heads;
-  hipLaunchKernelGGL((attn_spatial_bf16_kernel<E, HD>), dim3((n_prob + 3) / 4), dim3(256), 0, st, (const E*)qkv, (E*)out, n_prob, map,
+  hipLaunchKernelGGL((attn_spatial_bf16_kernel<E, HD AF_HDT_ARG>), dim3((n_prob + 3) / 4), dim3(256), 0, st, (const E*)qkv, (E*)out, n_prob, map,
                      C, heads);
   return 0;
 }
 
 }  // namespace
 
+#ifdef D3DP_FAST_PAD_TU
+// rows of C = heads x hdp columns per third, hdp = 32 with hd_true = 24 or hdp = 64 with hd_true in {40, 48, 56}; axis 0: the spatial
+// kernel (<= 32 tokens), otherwise the whole-sequence / chunked-key kernels (<= 1024 tokens, any SeqMap); -2 for any other shape
+#define AF_PAD(HD_, HDT_)                                                                                                        \
+  return axis == 0 ? (f16 ? attn_spatial<_Float16, HD_, HDT_>(qkv, out, n_seq, map, C, heads, st)                                \
+                          : attn_spatial<__bf16, HD_, HDT_>(qkv, out, n_seq, map, C, heads, st))                                 \
+                   : (f16 ? attn_temporal2<_Float16, HD_, HDT_>(qkv, out, n_seq, map, C, heads, st)                              \
+                          : attn_temporal2<__bf16, HD_, HDT_>(qkv, out, n_seq, map, C, heads, st));
+int d3dp_attn_fast_padded(int axis, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st, int f16,
+                          int hd_true) {
+  if (heads < 1 || C % heads || map.n_tok < 1 || map.n_tok > (axis == 0 ? 32 : 1024)) return -2;
+  const int hdp = C / heads;
+  if (hdp == 32 && hd_true == 24) { AF_PAD(32, 24) }
+  if (hdp == 64 && hd_true == 40) { AF_PAD(64, 40) }
+  if (hdp == 64 && hd_true == 48) { AF_PAD(64, 48) }
+  if (hdp == 64 && hd_true == 56) { AF_PAD(64, 56) }
+  return -2;
+}
+#undef AF_PAD
+#else
 // (f16: 0 = bf16 rows in and out, 1 = IEEE fp16.  Head dim 64, 32 or 16.  Any SeqMap: <= 256 tokens the whole-sequence kernel, up
-//  to 1024 the chunked-key one)
+//  to 1024 the chunked-key one.  hd_true: kernels.h)
 int d3dp_launch_attn_temporal_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
-                                   hipStream_t st, int f16) {
+                                   hipStream_t st, int f16, int hd_true) {
   if (heads < 1 || C % heads || map.n_tok > 1024 || map.n_tok < 1) return -2;
+  if (hd_true && hd_true != C / heads) return d3dp_attn_fast_padded(1, qkv, out, n_seq, map, C, heads, st, f16, hd_true);
   switch (C / heads) {
     case 64: return f16 ? attn_temporal2<_Float16, 64>(qkv, out, n_seq, map, C, heads, st) : attn_temporal2<__bf16, 64>(qkv, out, n_seq, map, C, heads, st);
     case 32: return f16 ? attn_temporal2<_Float16, 32>(qkv, out, n_seq, map, C, heads, st) : attn_temporal2<__bf16, 32>(qkv, out, n_seq, map, C, heads, st);
@@ -422,8 +462,10 @@ int d3dp_launch_attn_temporal_bf16(const void* qkv, void* out, int n_seq, SeqMap
 }
 
 // spatial axis on MFMA (bf16 or, f16 == 1, IEEE fp16 rows; head dim 64, 32 or 16, <= 32 tokens per sequence)
-int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st, int f16) {
+int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st, int f16,
+                                  int hd_true) {
   if (heads < 1 || C % heads || map.n_tok > 32 || map.n_tok < 1) return -2;
+  if (hd_true && hd_true != C / heads) return d3dp_attn_fast_padded(0, qkv, out, n_seq, map, C, heads, st, f16, hd_true);
   switch (C / heads) {
     case 64: return f16 ? attn_spatial<_Float16, 64>(qkv, out, n_seq, map, C, heads, st) : attn_spatial<__bf16, 64>(qkv, out, n_seq, map, C, heads, st);
     case 32: return f16 ? attn_spatial<_Float16, 32>(qkv, out, n_seq, map, C, heads, st) : attn_spatial<__bf16, 32>(qkv, out, n_seq, map, C, heads, st);
@@ -431,3 +473,7 @@ int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap 
   }
   return -2;
 }
+#endif
+#undef AF_HDT_PARAM
+#undef AF_HDT_ARG
+#undef AF_SCALE

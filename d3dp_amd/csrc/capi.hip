@@ -153,7 +153,8 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   // implementation D3DP_EXACT_IMPL=f32 selects by hand for the instantiated widths: same tolerance, roughly a fifth of the
   // throughput.  A TRAIN context of such a width (the reference trains at any `-cs` too: main.py:325) takes the fp32 path of the
   // training step -- what D3DP_TRAIN_IMPL=f32 selects for the instantiated widths -- through the run-time-width row kernels of
-  // train_g.hip and the VALU attention backward with a run-time head dim.  FAST contexts exist for the instantiated widths only.
+  // train_g.hip and the VALU attention backward with a run-time head dim.  FAST / FAST16 contexts exist for the instantiated
+  // widths and, under D3DP_FAST_IMPL=mfma, for channels in {192, 320, 384, 448} (below).
   const bool width_inst = (g.channels == 64 || g.channels == 128 || g.channels == 256 || g.channels == 512) &&
                           (hd == 8 || hd == 16 || hd == 32 || hd == 64) && g.hidden >= 64 && g.hidden % 64 == 0;
   // D3DP_EXACT_IMPL=f16x2 (opt-in): an EXACT context at channels in {192, 320, 384, 448} runs the split-fp16 implementation with
@@ -193,6 +194,34 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
                                   "hidden=%d is not one (unset the switch: such a context trains on the fp32 path)",
                     g.channels, g.heads, g.hidden);
       train_widths = true;
+    }
+  }
+  // D3DP_FAST_IMPL=mfma (opt-in; read for FAST / FAST16 contexts alone): such a context at the same widths runs the mode's dataflow -- 2-byte
+  // weights and activations, fp32 residual stream, both attentions and all four Linears on the matrix cores -- with the head dim padded
+  // to 32 / 64 inside the packed 2-byte weights (ctx.h hdp).  hidden = 2 x channels (what MixSTE2 builds): the k-depths the streaming
+  // Linear is instantiated for.  Head dims 24 / 40 / 48 / 56 (the model's 8 heads) are the ones the padded attention kernels carry the
+  // exponent of (attention_fast_pad.hip); 32 and 64 (6 or 3 heads at 192, ...) need no padding and run the kernels of the instantiated
+  // widths; 8 and 16 (12, 24, ... heads) have no kernel behind this route and are refused here.  At an instantiated width the value names the default; any other value, width or shape is refused
+  // here, before the device is looked for -- never ignored.
+  if (g.mode == D3DP_MODE_FAST || g.mode == D3DP_MODE_FAST16) {
+    if (const char* fi = getenv("D3DP_FAST_IMPL")) {
+      if (strcmp(fi, "mfma"))
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_FAST_IMPL=%.32s: the one value a FAST / FAST16 context takes is D3DP_FAST_IMPL=mfma (channels=%d)", fi,
+                    g.channels);
+      if (!width_inst) {
+        const bool shape = (g.channels == 192 || g.channels == 320 || g.channels == 384 || g.channels == 448) &&
+                           (hd == 24 || hd == 32 || hd == 40 || hd == 48 || hd == 56 || hd == 64) && g.hidden == 2 * g.channels;
+        if (!shape)
+          return d3dp_fail(D3DP_ENOTSUP, "D3DP_FAST_IMPL=mfma outside the instantiated widths exists for FAST / FAST16 contexts with channels in "
+                                    "{192,320,384,448}, head dim in {24,32,40,48,56,64} and hidden = 2 x channels; channels=%d heads=%d "
+                                    "hidden=%d is not one (such a width runs in D3DP_MODE_EXACT / D3DP_MODE_TRAIN)",
+                      g.channels, g.heads, g.hidden);
+        const char* lr = getenv("D3DP_LONG_ATTN");
+        if (lr && !strcmp(lr, "rows"))
+          return d3dp_fail(D3DP_ENOTSUP, "D3DP_LONG_ATTN=rows with D3DP_FAST_IMPL=mfma at channels=%d: the row attention kernel would take the padded "
+                                    "head dim for its exponent", g.channels);
+        hdp = hd <= 32 ? 32 : 64;
+      }
     }
   }
   if (!width_inst && !hdp) {

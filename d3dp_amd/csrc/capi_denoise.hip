@@ -9,7 +9,7 @@
 //                        adds them in the proj / fc2 epilogues (x += ...) and leaves both regions unused
 // A padded-head context (D3DP_EXACT_IMPL=f16x2 at channels 192 / 320 / 384 / 448, ctx.h hdp): qkv rows hold 3 Cp columns and the
 // attention output Cp = heads x hdp, so bufA holds max(C, Cp) columns (LayerNorm rows at pitch 2 C, attention output rows at pitch
-// 2 Cp fp16) and bufB max(3 Cp, hidden).
+// 2 Cp fp16) and bufB max(3 Cp, hidden).  The same under D3DP_FAST_IMPL=mfma in the FAST modes: 2-byte rows of C, Cp and 3 Cp columns.
 // The reference keeps two physical layouts and transposes between them 16 times per call (mixste.py:244,270,274); here spatial
 // and temporal attention both index the single layout by stride.
 #include "ctx.h"
@@ -102,8 +102,8 @@ int attention(d3dp_ctx* c, int axis, const void* qkv, void* out, int n_bh, float
   const SeqMap map = axis == 0 ? spatial_map(g.frames, g.joints, c->seq_pitch()) : temporal_map(g.frames, g.joints, c->seq_pitch());
   switch (c->route(axis)) {
     case AttnRoute::X2: return d3dp_launch_attn_x2(3, axis, qkv, out, n, map, C, g.heads, s_kv, st, g.channels / g.heads);
-    case AttnRoute::FAST_SPATIAL: return d3dp_launch_attn_spatial_bf16(qkv, out, n, map, C, g.heads, st, c->fast_f16);
-    case AttnRoute::FAST_WHOLE_SEQ: return d3dp_launch_attn_temporal_bf16(qkv, out, n, map, C, g.heads, st, c->fast_f16);
+    case AttnRoute::FAST_SPATIAL: return d3dp_launch_attn_spatial_bf16(qkv, out, n, map, C, g.heads, st, c->fast_f16, g.channels / g.heads);
+    case AttnRoute::FAST_WHOLE_SEQ: return d3dp_launch_attn_temporal_bf16(qkv, out, n, map, C, g.heads, st, c->fast_f16, g.channels / g.heads);
     case AttnRoute::F32_TEMPORAL: return d3dp_launch_attn_temporal_f32(act, qkv, out, n, map, C, g.heads, st);
     case AttnRoute::ROWS: break;
   }

@@ -95,6 +95,16 @@ int d3dp_op_attention(int32_t act_bf16, int32_t impl, int32_t axis, const void* 
   hipStream_t st = (hipStream_t)stream;
   if (act_bf16 != 0 && act_bf16 != 1 && act_bf16 != 4) return d3dp_fail(D3DP_EINVAL, "act_bf16 must be 0, 1 or 4 (fp16)");
   const int f16 = act_bf16 == 4;
+  // impl = 1 | (true head dim << 8) on 2-byte rows: the padded forms of the FAST attention kernels (attention_fast_pad.hip) -- C / heads is
+  // the padded head dim 32 / 64, whose columns beyond the true head dim are zeros in `qkv` and come back as zeros in `out`
+  const int hd_true = (impl & 255) == 1 ? impl >> 8 : 0;
+  if (hd_true) {
+    impl = 1;
+    const int hdp = heads > 0 && C % heads == 0 ? C / heads : 0;
+    if (!act_bf16 || !((hdp == 32 && hd_true == 24) || (hdp == 64 && (hd_true == 40 || hd_true == 48 || hd_true == 56))))
+      return d3dp_fail(D3DP_ENOTSUP, "impl 1 | (true head dim << 8) takes 2-byte rows of head dim 32 holding 24 or 64 holding 40 / 48 / 56; C=%d "
+                                "heads=%d true head dim %d is not one", C, heads, hd_true);
+  }
   if (impl == 2) {       // EXACT mode: split-fp16 operands on the fp16 matrix cores, fp32 in / fp32 out
     if (act_bf16) return d3dp_fail(D3DP_EINVAL, "split-fp16 attention takes fp32 activations");
     // (refused here, before the temporary exists and the repack kernel runs)
@@ -115,15 +125,15 @@ int d3dp_op_attention(int32_t act_bf16, int32_t impl, int32_t axis, const void* 
                               "impl 0, takes it)", C, heads, heads > 0 ? C / heads : 0);
   } else if (axis == 0 && impl == 1) {
     if (!act_bf16) return d3dp_fail(D3DP_EINVAL, "MFMA spatial attention needs bf16 activations");
-    if (J <= 32) LAUNCH_TRY(d3dp_launch_attn_spatial_bf16(qkv, out, n_bh * F, spatial_map(F, J), C, heads, st, f16));
+    if (J <= 32) LAUNCH_TRY(d3dp_launch_attn_spatial_bf16(qkv, out, n_bh * F, spatial_map(F, J), C, heads, st, f16, hd_true));
     else if (J > 256) return d3dp_fail(D3DP_ENOTSUP, "MFMA spatial attention takes up to 256 joints; J=%d", J);
-    else LAUNCH_TRY(d3dp_launch_attn_temporal_bf16(qkv, out, n_bh * F, spatial_map(F, J), C, heads, st, f16));   // whole-sequence kernel
+    else LAUNCH_TRY(d3dp_launch_attn_temporal_bf16(qkv, out, n_bh * F, spatial_map(F, J), C, heads, st, f16, hd_true));   // whole-sequence kernel
   } else if (axis == 0) LAUNCH_TRY(d3dp_launch_attn_rows(act_bf16, qkv, out, n_bh * F, spatial_map(F, J), C, heads, st));
   else if (impl == 1 && !act_bf16) {
     LAUNCH_TRY(d3dp_launch_attn_temporal_f32(0, qkv, out, n_bh * J, temporal_map(F, J), C, heads, st));   // fp32 MFMA
   } else if (impl == 1) {
     if (!act_bf16) return d3dp_fail(D3DP_EINVAL, "MFMA temporal attention needs bf16 activations");
-    LAUNCH_TRY(d3dp_launch_attn_temporal_bf16(qkv, out, n_bh * J, temporal_map(F, J), C, heads, st, f16));
+    LAUNCH_TRY(d3dp_launch_attn_temporal_bf16(qkv, out, n_bh * J, temporal_map(F, J), C, heads, st, f16, hd_true));
   } else LAUNCH_TRY(d3dp_launch_attn_rows(act_bf16, qkv, out, n_bh * J, temporal_map(F, J), C, heads, st));
   HIP_TRY(hipGetLastError());
   return D3DP_OK;

@@ -46,7 +46,28 @@ __global__ void pad_bias_kernel(const float* __restrict__ src, float* __restrict
   dst[i] = si >= 0 ? src[si] : 0.f;
 }
 
+// the plain cast of to_bf16_kernel with the same head map (a FAST / FAST16 context with padded heads): dst [rows][cols] of E, a pad
+// element an exact zero.  One thread per destination element.
+template <typename E>
+__global__ void to_bf16_pad_kernel(const float* __restrict__ src, E* __restrict__ dst, int rows, int cols, int src_cols, int pad_rows,
+                                   int hd, int hdp, int heads) {
+  const size_t n = (size_t)rows * cols, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int r = (int)(i / cols), c = (int)(i - (size_t)r * cols);
+    const int sr = pad_rows ? unpad_index(r, hd, hdp, heads) : r, sc = pad_rows ? c : unpad_index(c, hd, hdp, heads);
+    dst[i] = (E)(sr >= 0 && sc >= 0 ? src[(size_t)sr * src_cols + sc] : 0.f);
+  }
+}
+
 }  // namespace
+
+void d3dp_launch_to_bf16_pad(const float* s, void* d, int rows, int cols, int src_cols, int pad_rows, int hd, int hdp, int heads,
+                             hipStream_t st, int f16) {
+  const size_t n = (size_t)rows * cols;
+  const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
+  if (f16) hipLaunchKernelGGL(to_bf16_pad_kernel<_Float16>, dim3(blocks ? blocks : 1), dim3(256), 0, st, s, (_Float16*)d, rows, cols, src_cols, pad_rows, hd, hdp, heads);
+  else hipLaunchKernelGGL(to_bf16_pad_kernel<__bf16>, dim3(blocks ? blocks : 1), dim3(256), 0, st, s, (__bf16*)d, rows, cols, src_cols, pad_rows, hd, hdp, heads);
+}
 
 void d3dp_launch_to_bf16(const float* s, void* d, size_t n, hipStream_t st, int f16) {
   const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
@@ -253,11 +274,11 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
   // ---- arena layout ----
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-  // (pad: 0 = a flat copy / split of n elements; a padded-head context running the split-fp16 implementation packs 1 = the qkv
+  // (pad: 0 = a flat copy / split of n elements; a padded-head context running the split-fp16 implementation or a FAST mode packs 1 = the qkv
   //  matrix as [3 Cp][C], 2 = the proj matrix as [C][Cp], 3 = the qkv bias as [3 Cp] -- n_dst elements from the n of the source)
   struct Item { const void* src; size_t n; bool mat; size_t off; int pad; size_t n_dst; };
   std::vector<Item> items;
-  const bool padded = c->x2() && c->hdp != 0;
+  const bool padded = (c->x2() || c->fast()) && c->hdp != 0;
   const size_t Cp = padded ? (size_t)c->cp() : C;
   auto add = [&](const void* src, size_t n, bool mat, int pad = 0, size_t n_dst = 0) {
     if (!padded) pad = 0;
@@ -346,6 +367,9 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
     if (it.pad == 3)
       hipLaunchKernelGGL(pad_bias_kernel, dim3(((unsigned)it.n_dst + 255) / 256), dim3(256), 0, st, (const float*)it.src,
                          (float*)(c->arena + it.off), (int)it.n_dst, hd, c->hdp, g.heads);
+    else if (it.pad && c->fast())   // (the plain cast of every FAST weight, to the type the range proof above chose)
+      d3dp_launch_to_bf16_pad((const float*)it.src, c->arena + it.off, it.pad == 1 ? 3 * (int)Cp : (int)C, it.pad == 1 ? (int)C : (int)Cp,
+                              (int)C, it.pad == 1 ? 1 : 0, hd, c->hdp, g.heads, st, c->fast_f16);
     else if (it.pad)     // (the same split arithmetic and the same per-matrix scale, from the absmax of the caller's unpadded matrix)
       hipLaunchKernelGGL(split2h_pad_kernel, dim3((unsigned)std::min<size_t>((it.n_dst + 255) / 256, 4096)), dim3(256), 0, st,
                          (const float*)it.src, (f16*)(c->arena + it.off), it.pad == 1 ? 3 * (int)Cp : (int)C,

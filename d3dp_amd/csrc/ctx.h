@@ -106,11 +106,15 @@ struct d3dp_ctx {
   // packed rows of cp() = heads x hdp columns whose pad columns are exact zeros, the attention kernels run their head dim 32 / 64
   // instantiations on them (the softmax exponent takes the true head dim) and proj contracts over cp() columns against zero weight
   // columns.  The residual stream, the LayerNorms and the MLP keep the true width.  0: no padding (every other context).
+  // D3DP_FAST_IMPL=mfma at the same widths (d3dp_create; FAST / FAST16 contexts): the same padding inside 2-byte weights -- the streaming
+  // Linear at the k-depths of these widths (gemm_stream_widths.hip), the FAST attention kernels' head dim 32 / 64 forms with the true head
+  // dim in the exponent (attention_fast_pad.hip) and run-time-width row kernels with 2-byte rows (pointwise_rows2.hip).  Such a context
+  // has no fallback implementation: FAST16's range fallback is the same route on bf16.
   int hdp = 0;
   int cp() const { return hdp ? cfg.heads * hdp : cfg.channels; }
   // (the columns of a packed qkv third / of the attention output while the split-fp16 implementation runs; the range fallback of
   //  a padded context is the fp32 implementation, which knows no padding)
-  int attn_cols() const { return hdp && exact_impl == 0 ? cp() : cfg.channels; }
+  int attn_cols() const { return hdp && (fast() || exact_impl == 0) ? cp() : cfg.channels; }
   AttnRoute route(int axis) const {
     return attn_route(cfg.mode, exact_impl, attn_cols() / cfg.heads, cfg.frames, cfg.joints, long_rows, axis);
   }

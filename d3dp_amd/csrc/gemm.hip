@@ -165,6 +165,9 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 
 }  // namespace
 
+// (gemm_stream_widths.hip includes this file with D3DP_STREAM_WIDTHS_TU defined for the streaming kernel's template alone: see
+//  the bottom of the file)
+#ifndef D3DP_STREAM_WIDTHS_TU
 // ------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------
@@ -374,6 +377,7 @@ void d3dp_launch_split3(const float* src, void* dst, size_t n, hipStream_t st) {
   const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
   hipLaunchKernelGGL(split3_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, st, src, (bf16*)dst, n);
 }
+#endif  // D3DP_STREAM_WIDTHS_TU
 
 // ================================================================================================
 // FAST mode, persistent streaming GEMM ("v2"): the kernel the denoiser launches for every Linear.
@@ -593,13 +597,17 @@ __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(c
         for (int r = 0; r < UPS; ++r) drain_one(unit++);
       }
     } else {
+      // NK does not divide the queue (K / 64 = 3, 5, 6, 7, 10, 12, 14: gemm_stream_widths.hip): UPD units, the next power of two
+      // above NU / NK, behind each of the first NU / UPD k-steps and none behind the rest (uniform scalar branch)
+      constexpr int UPD = UPS <= 1 ? 1 : UPS <= 2 ? 2 : UPS <= 4 ? 4 : UPS <= 8 ? 8 : 16;
       int unit = 0;
-#pragma unroll
+#pragma unroll 1
       for (int ks = 0; ks < NK; ++ks) {
         kstep(g0 + ks);
+        if (unit < NU) {
 #pragma unroll
-        for (int r = 0; r < UPS; ++r)
-          if (unit < NU) { drain_one(unit); ++unit; }
+          for (int r = 0; r < UPD; ++r) drain_one(unit++);
+        }
       }
     }
     const int t = L + ti * G;
@@ -650,6 +658,31 @@ int launch_stream_nk(const void* A, const void* W, const float* bias, void* out,
   return launch_stream_nk_mi<E, EPI, OutT, NK, 4>(A, W, bias, out, M, N, st);
 }
 
+// K / 64 outside {1, 2, 4, 8, 16}: the k-depths of channels 192 / 320 / 384 / 448 (FAST / FAST16 contexts under D3DP_FAST_IMPL=mfma)
+// are instantiations of the same template in a translation unit of their own, gemm_stream_widths.hip, which includes this file
+// with D3DP_STREAM_WIDTHS_TU defined -- the instantiations below keep their device code (profiles/fast_widths.md).  NK need not be a
+// power of two: `g` counts k-steps across tile boundaries in the loaders and the compute waves alike, so the tile index g / NK and
+// the ring stage g % 3 stay in step, and the drain stores UPD units of the finished tile -- the next power of two above 16 / NK --
+// behind each of the first 16 / UPD k-steps of the next tile and none behind the rest (the kernel's last drain form).
+#ifdef D3DP_STREAM_WIDTHS_TU
+template <typename E, int EPI>
+int launch_stream_widths(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, hipStream_t st) {
+  switch (K / SBK) {                                  // C = 192 / 320 / 384 / 448 (qkv, fc1) and 2 C (fc2: EPI_BIAS only)
+    case 3: return launch_stream_nk<E, EPI, E, 3>(A, W, bias, out, M, N, st);
+    case 5: return launch_stream_nk<E, EPI, E, 5>(A, W, bias, out, M, N, st);
+    case 6: return launch_stream_nk<E, EPI, E, 6>(A, W, bias, out, M, N, st);
+    case 7: return launch_stream_nk<E, EPI, E, 7>(A, W, bias, out, M, N, st);
+  }
+  if constexpr (EPI == EPI_BIAS) {
+    switch (K / SBK) {
+      case 10: return launch_stream_nk<E, EPI, E, 10>(A, W, bias, out, M, N, st);
+      case 12: return launch_stream_nk<E, EPI, E, 12>(A, W, bias, out, M, N, st);
+      case 14: return launch_stream_nk<E, EPI, E, 14>(A, W, bias, out, M, N, st);
+    }
+  }
+  return -1;
+}
+#else
 template <typename E, int EPI, typename OutT>
 int launch_stream(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, hipStream_t st) {
   switch (K / SBK) {
@@ -658,12 +691,27 @@ int launch_stream(const void* A, const void* W, const float* bias, void* out, in
     case 4: return launch_stream_nk<E, EPI, OutT, 4>(A, W, bias, out, M, N, st);
     case 8: return launch_stream_nk<E, EPI, OutT, 8>(A, W, bias, out, M, N, st);
     case 16: return launch_stream_nk<E, EPI, OutT, 16>(A, W, bias, out, M, N, st);
-    default: return -1;
+    default:                                           // (2-byte rows out alone: what a FAST context's qkv, fc1 and fc2 write)
+      if constexpr (sizeof(OutT) == 2) return d3dp_linear_stream_widths(EPI, A, W, bias, out, M, N, K, st, std::is_same<E, _Float16>::value);
+      return -1;
   }
 }
+#endif
 
 }  // namespace
 
+#ifdef D3DP_STREAM_WIDTHS_TU
+// out[M,N] = epi(A W^T + bias) in the operand type, K / 64 in {3, 5, 6, 7} (EPI_BIAS, EPI_GELU) or {10, 12, 14} (EPI_BIAS); -1 for
+// any other (d3dp_launch_linear_bf16_stream has checked M, N and K % 64)
+int d3dp_linear_stream_widths(int epi, const void* A, const void* W, const float* bias, void* out, int M, int N, int K,
+                              hipStream_t st, int f16) {
+  if (epi == EPI_BIAS) return f16 ? launch_stream_widths<_Float16, EPI_BIAS>(A, W, bias, out, M, N, K, st)
+                                  : launch_stream_widths<__bf16, EPI_BIAS>(A, W, bias, out, M, N, K, st);
+  if (epi == EPI_GELU) return f16 ? launch_stream_widths<_Float16, EPI_GELU>(A, W, bias, out, M, N, K, st)
+                                  : launch_stream_widths<__bf16, EPI_GELU>(A, W, bias, out, M, N, K, st);
+  return -1;
+}
+#else
 // out[M,N] = epi(A W^T + bias); epi in {EPI_BIAS, EPI_GELU}; operands bf16 (f16 == 0) or IEEE fp16 (f16 == 1); out of the
 // operand type or fp32.
 template <typename E>
@@ -680,3 +728,4 @@ int d3dp_launch_linear_bf16_stream(int epi, int out_f32, const void* A, const vo
   return f16 ? linear_stream<_Float16>(epi, out_f32, A, W, bias, out, M, N, K, st)
              : linear_stream<__bf16>(epi, out_f32, A, W, bias, out, M, N, K, st);
 }
+#endif

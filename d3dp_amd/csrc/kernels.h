@@ -43,6 +43,10 @@ enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_PARTIAL = 3, EPI_QKV_PACK 
 // (f16: the 2-byte type of A, W and a 2-byte out -- 0 = bf16, 1 = IEEE fp16)
 int d3dp_launch_linear_bf16_stream(int epi, int out_f32, const void* A, const void* W, const float* bias, void* out,
                                    int M, int N, int K, hipStream_t st, int f16 = 0);
+// (K / 64 in {1, 2, 4, 8, 16}: gemm.hip itself; 2-byte rows out at K / 64 in {3, 5, 6, 7} and, EPI_BIAS, {10, 12, 14} -- the k-depths of
+//  channels 192 / 320 / 384 / 448 -- through gemm_stream_widths.hip, the same kernel template at those NK; -1 for any other)
+int d3dp_linear_stream_widths(int epi, const void* A, const void* W, const float* bias, void* out, int M, int N, int K,
+                              hipStream_t st, int f16);
 int d3dp_launch_linear_bf16x3(int epi, const void* A3, const void* W3, const float* bias, float* outf, void* out3, int M,
                               int N, int K, hipStream_t st);
 void d3dp_launch_split3(const float* src, void* dst, size_t n, hipStream_t st);
@@ -175,10 +179,15 @@ int d3dp_launch_attn_temporal_f32(int act, const void* qkv, void* out, int n_seq
                                   hipStream_t st);
 // ---- attention_fast.hip: FAST / FAST16 on the 2-byte matrix cores -------------------------------
 // (the MFMA kernels of the FAST modes -- f16: 0 = bf16 rows in and out, 1 = IEEE fp16; d3dp_launch_attn_rows: act 1 / act 4)
+// hd_true: the head dim of the softmax exponent (hd_true^-0.5) where it is smaller than C / heads -- rows whose heads were padded with
+// zero columns to head dim 32 (hd_true 24) or 64 (hd_true 40 / 48 / 56): attention_fast_pad.hip; 0 = C / heads itself
 int d3dp_launch_attn_temporal_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads,
-                                   hipStream_t st, int f16 = 0);
+                                   hipStream_t st, int f16 = 0, int hd_true = 0);
 int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st,
-                                  int f16 = 0);
+                                  int f16 = 0, int hd_true = 0);
+// (attention_fast_pad.hip: the padded forms behind the two launchers above; axis 0 = the spatial kernel, <= 32 tokens)
+int d3dp_attn_fast_padded(int axis, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st, int f16,
+                          int hd_true);
 // ---- attention_x2.hip: EXACT on split-fp16 operands (head dim 64, 32 or 16; -2 for any other) ----
 // split-fp16 attention: `qkv` = PACKED rows of 12 C bytes (q fp32 | k hi | k lo | v hi | v lo), written by the qkv Linear
 // with EPI_QKV_PACK or from fp32 rows by d3dp_launch_qkv_pack_x2
@@ -212,6 +221,18 @@ int d3dp_launch_ln2(int act_bf16, float* x, const void* yadd0, const void* yadd,
 // next Linear that adds into x applies LN_a itself (EPI_RESID_NORM).  act_bf16 = 3 (split-fp16 planes) only.
 int d3dp_launch_ln2_defer(int act_bf16, const float* x, const float* wa, const float* ba, const float* wb, const float* bb, float eps,
                           void* xn, float* stat, int T, int C, hipStream_t st);
+// ---- pointwise_rows2.hip: the four row kernels at a run-time width with 2-byte rows (act 1 = bf16, 4 = IEEE fp16; C % 32 == 0,
+// C <= 512; -2 otherwise) -- xn and the yadd rows have the type; reached through the four launchers around this block
+int d3dp_rows2_embed_ln(int act, const float* x2d, const float* x3d, const float* temb, const float* ew, const float* eb,
+                        const float* spos, const float* lnw, const float* lnb, float eps, float* x, void* xn, int seq0, int n_seq,
+                        int H, int F, int J, int C, hipStream_t st, int SP);
+int d3dp_rows2_ln(int act, float* x, const void* yadd, int write_x, const float* w, const float* b, float eps, void* xn, int T, int C,
+                  hipStream_t st);
+int d3dp_rows2_ln2(int act, float* x, const void* yadd0, const void* yadd, const float* wa, const float* ba, const float* pos,
+                   const float* wb, const float* bb, float eps, void* xn, int T, int C, int F, int J, hipStream_t st, int SP);
+int d3dp_rows2_head(int act, const float* x, const void* yadd0, const void* yadd, const float* wa, const float* ba, float eps_a,
+                    const float* wh, const float* bh, float eps_h, const float* w, const float* b, float* out, int T, int C,
+                    hipStream_t st, int FJ, int SP);
 // out[T,3] = Linear(LN_head(LN_a(x)))
 int d3dp_launch_head(int act_bf16, const float* x, const void* yadd0, const void* yadd, const float* wa, const float* ba, float eps_a, const float* wh,
                      const float* bh, float eps_h, const float* w, const float* b, float* out, int T, int C,
@@ -236,6 +257,10 @@ int d3dp_launch_jpma(const float* pred, const float* traj, const float* cam, con
 // ---- capi_weights.hip ------------------------------------------------------------------------------------------
 // fp32 -> bf16 (f16: IEEE fp16), a plain cast: the FAST / FAST16 weight matrices (d3dp_set_weights) and d3dp_op_to_bf16
 void d3dp_launch_to_bf16(const float* s, void* d, size_t n, hipStream_t st, int f16 = 0);
+// ... with padded heads (ctx.h hdp): dst [rows][cols] of the 2-byte type from src [.][src_cols]; pad_rows: the row axis is padded, in
+// sections of heads x hdp rows (the qkv matrix), otherwise the column axis (the proj matrix); a pad element is an exact zero
+void d3dp_launch_to_bf16_pad(const float* s, void* d, int rows, int cols, int src_cols, int pad_rows, int hd, int hdp, int heads,
+                             hipStream_t st, int f16);
 
 // ---- capi.hip helpers shared with caller.hip ---------------------------------------------------------------------
 int d3dp_set_error(int code, const char* msg);        // records the message for d3dp_last_error(), returns code

@@ -841,6 +841,9 @@ int d3dp_launch_embed_ln(int act_bf16, const float* x2d, const float* x3d, const
       hipLaunchKernelGGL(embed_ln_h_kernel, dim3((T + 4 * kRowTokens - 1) / (4 * kRowTokens)), blk, 0, st, x2d, x3d, temb, ew, eb, spos, lnw, lnb, eps, x, (f16*)xn, seq0, n_seq, H, F, J, SP, C);
       return 0;
     }
+    // (2-byte rows at a run-time width: pointwise_rows2.hip)
+    if ((act_bf16 == 1 || act_bf16 == 4) && width_rowh(C))
+      return d3dp_rows2_embed_ln(act_bf16, x2d, x3d, temb, ew, eb, spos, lnw, lnb, eps, x, xn, seq0, n_seq, H, F, J, C, st, SP);
     if (act_bf16 != 0) return -2;
     DISPATCH_G(C, hipLaunchKernelGGL((embed_ln_g_kernel<NVM>), g, blk, 0, st, x2d, x3d, temb, ew, eb, spos, lnw, lnb, eps, x, (float*)xn, seq0, n_seq, H, F, J, SP, C))
     return 0;
@@ -864,6 +867,7 @@ int d3dp_launch_ln(int act_bf16, float* x, const void* yadd, int write_x, const 
       hipLaunchKernelGGL(ln_h_kernel, g, blk, 0, st, x, (const float*)yadd, w, b, eps, (f16*)xn, T, C, write_x);
       return 0;
     }
+    if ((act_bf16 == 1 || act_bf16 == 4) && width_rowh(C)) return d3dp_rows2_ln(act_bf16, x, yadd, write_x, w, b, eps, xn, T, C, st);
     if (act_bf16 != 0) return -2;
     DISPATCH_G(C, hipLaunchKernelGGL((ln_g_kernel<NVM>), g, blk, 0, st, x, (const float*)yadd, w, b, eps, (float*)xn, T, C, write_x))
     return 0;
@@ -887,6 +891,8 @@ int d3dp_launch_ln2(int act_bf16, float* x, const void* yadd0, const void* yadd,
       hipLaunchKernelGGL(ln2_h_kernel, g, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, pos, wb, bb, eps, (f16*)xn, T, C, F, J, SP);
       return 0;
     }
+    if ((act_bf16 == 1 || act_bf16 == 4) && width_rowh(C))
+      return d3dp_rows2_ln2(act_bf16, x, yadd0, yadd, wa, ba, pos, wb, bb, eps, xn, T, C, F, J, st, SP);
     if (act_bf16 != 0) return -2;
     DISPATCH_G(C, hipLaunchKernelGGL((ln2_g_kernel<NVM>), g, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, pos, wb, bb, eps, (float*)xn, T, C, F, J, SP))
     return 0;
@@ -917,6 +923,9 @@ int d3dp_launch_head(int act_bf16, const float* x, const void* yadd0, const void
   if (FJ <= 0 || SP <= 0) { FJ = SP = 1 << 30; }       // compact rows: out row = input row
   dim3 g((T + 3) / 4), blk(256);
   if (!width_instantiated(C)) {
+    // (2-byte yadd rows at a run-time width: pointwise_rows2.hip)
+    if ((act_bf16 == 1 || act_bf16 == 4) && width_rowh(C))
+      return d3dp_rows2_head(act_bf16, x, yadd0, yadd, wa, ba, eps_a, wh, bh, eps_h, w, b, out, T, C, st, FJ, SP);
     if (act_bf16 != 0) return -2;
     DISPATCH_G(C, hipLaunchKernelGGL((head_g_kernel<NVM>), g, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, eps_a, wh, bh, eps_h, w, b, out, T, C, FJ, SP))
     return 0;

@@ -157,7 +157,8 @@ D3DP_API const char* d3dp_last_error(void);
  *                         (fp32-MFMA Linears, fp32 row attention, run-time-width row kernels; d3dp_exact_scales reports
  *                         implementation 2): the same 1e-3 mm tolerance at roughly a fifth of the throughput; and
  *                         D3DP_MODE_TRAIN on the fp32 path of the training step, with the token limits listed under "What a
- *                         D3DP_MODE_TRAIN context takes" below.  FAST and FAST16 contexts exist for the instantiated widths only.
+ *                         D3DP_MODE_TRAIN context takes" below.  FAST and FAST16 contexts exist for the instantiated widths and,
+ *                         opt-in, for the four widths of the line after next.
  *   channels in {192, 320, 384, 448} with head dim % 8 == 0 and <= 64 and hidden % 64 == 0, D3DP_MODE_EXACT, with
  *                         D3DP_EXACT_IMPL=f16x2 in the environment of d3dp_create (OPT-IN: without the switch such a context
  *                         launches the fp32 implementation above, bit for bit as before): the split-fp16 implementation of the
@@ -170,6 +171,21 @@ D3DP_API const char* d3dp_last_error(void);
  *                         instantiated width the value names the default.  With any other width, or a TRAIN / FAST / FAST16
  *                         context of a non-instantiated width, or together with D3DP_LONG_ATTN=rows at these widths, the
  *                         switch cannot be honoured: D3DP_ENOTSUP, decided before the device is looked for.
+ *   channels in {192, 320, 384, 448} with head dim in {24, 32, 40, 48, 56, 64} and hidden == 2 x channels (what MixSTE2 builds), D3DP_MODE_FAST
+ *                         or D3DP_MODE_FAST16, with D3DP_FAST_IMPL=mfma in the environment of d3dp_create (OPT-IN: without the
+ *                         switch such a context is refused as before, with the same message): the mode's dataflow as at the
+ *                         instantiated widths -- 2-byte weights and activations (bf16, or fp16 behind FAST16's range proof, which
+ *                         runs on the caller's unpadded weights), fp32 residual stream, LayerNorm and softmax in fp32, both
+ *                         attentions and all four Linears on the matrix cores.  The head dim is padded to 32 / 64 inside the
+ *                         packed 2-byte weights as above, the attention kernels take the true head dim in the exponent, the
+ *                         row kernels are run-time-width forms with 2-byte rows.  (Head dims 24 / 40 / 48 / 56 -- 8 heads -- are
+ *                         padded; 32 and 64 need no padding and run the attention kernels of the instantiated widths; 8 and 16
+ *                         -- 12, 24, ... heads -- have no kernel behind this route and are refused.)  FAST16's fallback there is the same route on
+ *                         bf16, bit for bit a FAST context.  Frames <= 1024 and joints <= 256 as everywhere.  At an instantiated
+ *                         width the value names the default.  Any other value of the variable in a FAST / FAST16 context, any
+ *                         other width, head dim or hidden, or D3DP_LONG_ATTN=rows beside it at these widths (the row kernel would take the
+ *                         padded head dim for its exponent): D3DP_ENOTSUP, decided before the device is looked for.  EXACT and
+ *                         TRAIN contexts do not read the variable.
  * What a D3DP_MODE_TRAIN context takes, by the attention its training step runs:
  *   channels in {128, 256, 512} with head dim in {16, 32, 64} (`-cs 128 / 256 / 512` with 8 heads): Linears on split-fp16 operands and
  *                         the attention of both axes on the split-fp16 matrix-core kernels (train_attn.hip), which pass keys /
@@ -391,9 +407,15 @@ D3DP_API int d3dp_op_linear(int32_t mode, int32_t epi, const void* A, const void
  * and nothing is launched).  Inside
  * the denoiser those read the packed rows of its qkv Linear (d3dp_op_linear_x2, epi 4); this entry point takes plain fp32
  * rows and repacks them into a stream-ordered temporary (hipMallocAsync) first.
+ * impl = 1 | (d << 8) on 2-byte rows: the padded-head forms of the FAST / FAST16 kernels (D3DP_FAST_IMPL=mfma at d3dp_create) --
+ * C = heads x hdp is the PADDED width, hdp = 32 with true head dim d = 24 or hdp = 64 with d in {40, 48, 56}; the columns d .. hdp - 1
+ * of every head are zeros in qkv and come back as exact zeros in out; the softmax scale is d^-0.5.  Any other (hdp, d):
+ * D3DP_ENOTSUP.  Plain impl 1 takes C / heads itself as the head dim, as before.
  * act_bf16: 0 fp32 rows, 1 bf16 rows, 4 IEEE fp16 rows (impl 0 and 1: the kernels of a FAST16 context).
  * d3dp_op_layernorm out_bf16: the activation code of the row kernels -- 0 fp32, 1 bf16, 2 three split-bf16 planes, 3 two
- * split-fp16 planes (h2i), 4 IEEE fp16. */
+ * split-fp16 planes (h2i), 4 IEEE fp16.  Codes 1 and 4 take the instantiated widths and any C % 32 == 0, C <= 512 (the run-time-width
+ * kernels of the FAST modes at channels 192 / 320 / 384 / 448).  d3dp_op_linear in FAST mode / mode 4 takes K / 64 in {1, 2, 4, 8, 16}
+ * and, with a 2-byte out, {3, 5, 6, 7} (epi 0, 1) and {10, 12, 14} (epi 0): the k-depths of those widths. */
 D3DP_API int d3dp_op_attention(int32_t act_bf16, int32_t impl, int32_t axis, const void* qkv, void* out, int32_t n_bh,
                       int32_t F, int32_t J, int32_t C, int32_t heads, void* stream);
 D3DP_API int d3dp_op_layernorm(int32_t out_bf16, const float* x, const float* w, const float* b, float eps, void* out,

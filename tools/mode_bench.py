@@ -6,7 +6,9 @@
 `--frames N` runs the same sampler on clips of N frames (1 ... 1024), `--cs C` at a width of C channels (8 heads; 512, 256, 128
 or 64, and for `exact` any width the library takes: 192, 320, 384 and 448 have two routes).  An `:f16x2` suffix (`exact:f16x2`)
 creates that model's context with D3DP_EXACT_IMPL=f16x2: at `--cs` 192 / 320 / 384 / 448 the split-fp16 implementation with padded
-heads instead of the fp32 implementation -- `--cs 384 --numerics exact,exact:f16x2` is the A/B of the two.  A `:rows` suffix on a mode name (`fast:rows`, `exact:rows`)
+heads instead of the fp32 implementation -- `--cs 384 --numerics exact,exact:f16x2` is the A/B of the two.  An `:mfma` suffix on a
+FAST mode (`fast:mfma`, `fast16:mfma`) creates that model's context with D3DP_FAST_IMPL=mfma: the only way such a context exists at
+`--cs` 192 / 320 / 384 / 448 -- `--cs 384 --numerics exact:f16x2,fast:mfma,fast16:mfma` compares the three opt-in routes there.  A `:rows` suffix on a mode name (`fast:rows`, `exact:rows`)
 creates that model's library context with D3DP_LONG_ATTN=rows in the environment: the row attention kernel wherever the mode would
 take a chunked-key or, in the FAST modes, a whole-sequence matrix-core kernel beyond 256 frames / 32 joints, and at head dims 32
 and 16 (`--cs 256`, `--cs 128`) for every attention of a FAST mode -- the A/B of those kernels in one process:
@@ -52,9 +54,9 @@ def main():
     B, H, K = a.batch, a.hyps, a.ksteps
     frames = bench.F_ if a.frames is None else a.frames
     # the switch a suffix sets in the environment while that mode's context is created
-    suffixes = {"rows": ("D3DP_LONG_ATTN", "rows"), "f16x2": ("D3DP_EXACT_IMPL", "f16x2")}
+    suffixes = {"rows": ("D3DP_LONG_ATTN", "rows"), "f16x2": ("D3DP_EXACT_IMPL", "f16x2"), "mfma": ("D3DP_FAST_IMPL", "mfma")}
     if not 1 <= frames <= 1024 or any(m.count(":") > 1 or (":" in m and m.split(":")[1] not in suffixes) for m in modes):
-        ap.error("--frames must be in [1, 1024]; the mode suffixes are ':rows' and ':f16x2'")
+        ap.error("--frames must be in [1, 1024]; the mode suffixes are ':rows', ':f16x2' and ':mfma'")
     x2d_np = synthetic_inputs_2d(1234, B, frames)
     x2d, x2f = torch.from_numpy(x2d_np).cuda(), torch.from_numpy(flip_2d(x2d_np)).cuda()
     cs = bench.C_ if a.cs is None else a.cs
