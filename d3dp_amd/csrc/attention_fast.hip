@@ -31,14 +31,30 @@
 // come back as exact zeros of O^T; HDT enters the exponent alone.  There every kernel and launcher template below carries HDT as one
 // more parameter; here the AF_ macros expand to nothing, the instantiations are the ones this file always had and keep their device
 // code (profiles/fast_widths.md).
+//
+// The scaled forms (attention_fast_scaled.hip includes this file with D3DP_FAST_SCALED_TU defined): the same three kernels for a FAST16
+// context under D3DP_FAST16_RANGE=scale, whose q, k and v rows hold 2^-s times their value (ctx.h BlockDev::r_qkv).  S^T then comes out
+// at 2^-2s, so the exponent scale is a RUN-TIME argument `escale` = HD^-0.5 2^(2s) that every kernel and launcher template below carries
+// (with a tag parameter that keeps their symbols apart); nothing else moves -- scores and sums are fp32, the probabilities are at
+// most 1, and O^T leaves at v's scale.  Here and in the padded forms the AF_ESC_ macros expand to nothing.
 #ifdef D3DP_FAST_PAD_TU
 #define AF_HDT_PARAM , int HDT
 #define AF_HDT_ARG , HDT
 #define AF_SCALE (HDT == 24 ? 0.20412414523193151f : HDT == 40 ? 0.15811388300841897f : HDT == 48 ? 0.14433756729740643f : 0.1336306209562122f)
+#define AF_ESC_PARAM
+#define AF_ESC_ARG
+#elif defined(D3DP_FAST_SCALED_TU)
+#define AF_HDT_PARAM , int SCALED
+#define AF_HDT_ARG , SCALED
+#define AF_SCALE escale
+#define AF_ESC_PARAM , float escale
+#define AF_ESC_ARG , escale
 #else
 #define AF_HDT_PARAM
 #define AF_HDT_ARG
 #define AF_SCALE (HD == 64 ? 0.125f : HD == 32 ? 0.17677669529663689f : 0.25f)
+#define AF_ESC_PARAM
+#define AF_ESC_ARG
 #endif
 
 namespace {
@@ -81,7 +97,7 @@ __device__ __forceinline__ void pv_chunks(const FragBasesT<HD>& fb, const typena
 // maximum, and `o` / `denom` -- the sums over the earlier chunks -- are rescaled to that maximum and added to.
 template <typename E, int HD, int NKT, bool ONLINE AF_HDT_PARAM>
 __device__ __forceinline__ void attn_tile(const FragBasesT<HD>& fb, const typename Head<E, HD>::frag (&q)[Head<E, HD>::NQ], int n,
-                                          int lane, f32x4 (&o)[HD / 16], float& denom, float& mrun) {
+                                          int lane, f32x4 (&o)[HD / 16], float& denom, float& mrun AF_ESC_PARAM) {
   using e8 = typename Op2<E>::x8;
   using kfrag = typename Head<E, HD>::frag;
   constexpr int TILE = 16 * Head<E, HD>::ROWB;           // bytes of one 16-key tile of the K image
@@ -150,9 +166,9 @@ __device__ __forceinline__ void attn_tile(const FragBasesT<HD>& fb, const typena
 }
 template <typename E, int HD, int NKT AF_HDT_PARAM>
 __device__ __forceinline__ void attn_tile(const FragBasesT<HD>& fb, const typename Head<E, HD>::frag (&q)[Head<E, HD>::NQ], int n,
-                                          int lane, f32x4 (&o)[HD / 16], float& denom) {
+                                          int lane, f32x4 (&o)[HD / 16], float& denom AF_ESC_PARAM) {
   float m = 0.f;
-  attn_tile<E, HD, NKT, false AF_HDT_ARG>(fb, q, n, lane, o, denom, m);
+  attn_tile<E, HD, NKT, false AF_HDT_ARG>(fb, q, n, lane, o, denom, m AF_ESC_ARG);
 }
 
 // rows [0, n) of K and V (2 HD bytes per row for this head = HD / 8 16-byte slots) -> swizzled LDS images; rows [n, NK) zeroed.
@@ -175,7 +191,7 @@ __device__ __forceinline__ void stage_kv(const E* __restrict__ kbase, size_t row
 
 template <typename E, int HD, int NKT AF_HDT_PARAM>   // temporal axis: one workgroup per (sequence, head), 8 waves share the K/V images
 __global__ __launch_bounds__(512, 4) void attn_temporal2_bf16_kernel(const E* __restrict__ qkv, E* __restrict__ out,
-                                                                     SeqMap map, int C, int heads) {
+                                                                     SeqMap map, int C, int heads AF_ESC_PARAM) {
   using e4 = typename Op2<E>::x4;
   using H = Head<E, HD>;
   constexpr int NK = 16 * NKT;
@@ -210,7 +226,7 @@ __global__ __launch_bounds__(512, 4) void attn_temporal2_bf16_kernel(const E* __
     const int q = qt * 16 + fi;
     f32x4 o[HD / 16];
     float denom;
-    attn_tile<E, HD, NKT AF_HDT_ARG>(fb, qf[i], n, lane, o, denom);
+    attn_tile<E, HD, NKT AF_HDT_ARG>(fb, qf[i], n, lane, o, denom AF_ESC_ARG);
     if (q < n) {
       const float inv = 1.0f / denom;
       E* dst = out + (size_t)(base + q * ts) * C + head * HD + fg * 4;
@@ -242,7 +258,7 @@ __global__ __launch_bounds__(512, 4) void attn_temporal2_bf16_kernel(const E* __
 template <typename E, int HD, int NKT AF_HDT_PARAM>
 __global__ __launch_bounds__(512, NKT == 8 ? 4 : 2) void attn_long2_bf16_kernel(const E* __restrict__ qkv, E* __restrict__ out,
                                                                                   SeqMap map, int C, int heads, int groups,
-                                                                                  int n_work) {
+                                                                                  int n_work AF_ESC_PARAM) {
   using e4 = typename Op2<E>::x4;
   using H = Head<E, HD>;
   // a pass of the 512 threads moves RPP rows; NLD passes per chunk (HD = 16, chunks of 128 keys: half a pass, PART)
@@ -310,7 +326,7 @@ __global__ __launch_bounds__(512, NKT == 8 ? 4 : 2) void attn_long2_bf16_kernel(
       if (active) {
         const int off = (c & 1) * BUF, rem = n - c * NK; // (rem >= 1: the chunk holds a key, its maximum is finite)
         const FragBasesT<HD> fb = make_frag_bases<HD>(smem + off, smem + off + IMG, lane);
-        attn_tile<E, HD, NKT, true AF_HDT_ARG>(fb, qf, rem, lane, o, lrun, mrun);
+        attn_tile<E, HD, NKT, true AF_HDT_ARG>(fb, qf, rem, lane, o, lrun, mrun AF_ESC_ARG);
       }
       if (c + 1 < n_chunks) commit(smem + ((c + 1) & 1) * BUF);
     }
@@ -330,7 +346,7 @@ __global__ __launch_bounds__(512, NKT == 8 ? 4 : 2) void attn_long2_bf16_kernel(
 // head dim 64, 4 / 2 KiB at 32 / 16); a 256-thread workgroup covers 4 heads of one sequence.
 template <typename E, int HD AF_HDT_PARAM>
 __global__ __launch_bounds__(256) void attn_spatial_bf16_kernel(const E* __restrict__ qkv, E* __restrict__ out,
-                                                                int n_prob, SeqMap map, int C, int heads) {
+                                                                int n_prob, SeqMap map, int C, int heads AF_ESC_PARAM) {
   using e4 = typename Op2<E>::x4;
   using H = Head<E, HD>;
   constexpr int IMG = 32 * H::ROWB;
@@ -362,7 +378,7 @@ __global__ __launch_bounds__(256) void attn_spatial_bf16_kernel(const E* __restr
     const int q = qt * 16 + fi;
     f32x4 o[HD / 16];
     float denom;
-    attn_tile<E, HD, 2 AF_HDT_ARG>(fb, qf[qt], n, lane, o, denom);
+    attn_tile<E, HD, 2 AF_HDT_ARG>(fb, qf[qt], n, lane, o, denom AF_ESC_ARG);
     if (q < n) {
       const float inv = 1.0f / denom;
       E* dst = out + (size_t)(base + q * ts) * C + head * HD + fg * 4;
@@ -376,20 +392,20 @@ __global__ __launch_bounds__(256) void attn_spatial_bf16_kernel(const E* __restr
 }
 
 template <typename E, int HD, int NKT AF_HDT_PARAM>
-int launch_temporal2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
+int launch_temporal2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st AF_ESC_PARAM) {
   constexpr int NK = 16 * NKT;
   const size_t lds = (size_t)NK * 2 * Head<E, HD>::ROWB;           // the K and the V image
   auto kern = attn_temporal2_bf16_kernel<E, HD, NKT AF_HDT_ARG>;
   static PerDeviceOnce once;                          // (one per template instantiation = per kernel)
   if (once.get([&](int) { return d3dp_lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024); }) < 0) return -3;
-  hipLaunchKernelGGL(kern, dim3(n_seq * heads), dim3(512), lds, st, (const E*)qkv, (E*)out, map, C, heads);
+  hipLaunchKernelGGL(kern, dim3(n_seq * heads), dim3(512), lds, st, (const E*)qkv, (E*)out, map, C, heads AF_ESC_ARG);
   return 0;
 }
 
 // n_tok > 256: the chunked-key kernel; a persistent grid of two workgroups per CU (64 KiB of LDS each at head dim 64, 32 / 16 KiB
 // at 32 / 16: the register budget of its launch bounds, not the LDS, is what holds two)
 template <typename E, int HD AF_HDT_PARAM>
-int launch_long2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
+int launch_long2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st AF_ESC_PARAM) {
   constexpr int NKT = D3DP_FAST_LONG_NKT;
   static_assert(NKT == 8 || NKT == 16, "chunks of 128 or 256 keys");
   const int groups = ((map.n_tok + 15) / 16 + 7) / 8, n_work = n_seq * heads * groups;
@@ -403,25 +419,25 @@ int launch_long2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int h
   const int wgs = (NKT == 8 ? 2 : 1) * cus;
   const size_t lds = (size_t)NKT * 16 * 4 * Head<E, HD>::ROWB;     // two buffers of a K and a V image
   hipLaunchKernelGGL(kern, dim3(n_work < wgs ? n_work : wgs), dim3(512), lds, st, (const E*)qkv, (E*)out, map, C, heads, groups,
-                     n_work);
+                     n_work AF_ESC_ARG);
   return 0;
 }
 
 template <typename E, int HD AF_HDT_PARAM>
-int attn_temporal2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
+int attn_temporal2(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st AF_ESC_PARAM) {
   const int n = map.n_tok;
-  if (n > 256) return launch_long2<E, HD AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st);
-  if (n <= 32) return launch_temporal2<E, HD, 2 AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st);
-  if (n <= 64) return launch_temporal2<E, HD, 4 AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st);
-  if (n <= 128) return launch_temporal2<E, HD, 8 AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st);
-  return launch_temporal2<E, HD, 16 AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st);
+  if (n > 256) return launch_long2<E, HD AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st AF_ESC_ARG);
+  if (n <= 32) return launch_temporal2<E, HD, 2 AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st AF_ESC_ARG);
+  if (n <= 64) return launch_temporal2<E, HD, 4 AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st AF_ESC_ARG);
+  if (n <= 128) return launch_temporal2<E, HD, 8 AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st AF_ESC_ARG);
+  return launch_temporal2<E, HD, 16 AF_HDT_ARG>(qkv, out, n_seq, map, C, heads, st AF_ESC_ARG);
 }
 
 template <typename E, int HD AF_HDT_PARAM>
-int attn_spatial(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st) {
+int attn_spatial(const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st AF_ESC_PARAM) {
   const int n_prob = n_seq * heads;
   hipLaunchKernelGGL((attn_spatial_bf16_kernel<E, HD AF_HDT_ARG>), dim3((n_prob + 3) / 4), dim3(256), 0, st, (const E*)qkv, (E*)out, n_prob, map,
-                     C, heads);
+                     C, heads AF_ESC_ARG);
   return 0;
 }
 
@@ -446,6 +462,22 @@ int d3dp_attn_fast_padded(int axis, const void* qkv, void* out, int n_seq, SeqMa
   return -2;
 }
 #undef AF_PAD
+#elif defined(D3DP_FAST_SCALED_TU)
+// fp16 rows whose q, k and v hold 2^-s times their value: the kernels above with the exponent scale (C / heads)^-0.5 x `emul`, emul =
+// 2^(2s).  Head dim 64, 32 or 16; axis 0: the spatial kernel (<= 32 tokens), otherwise the whole-sequence / chunked-key kernels
+// (<= 1024 tokens, any SeqMap); -2 for any other shape
+int d3dp_attn_fast_scaled(int axis, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st, float emul) {
+  if (heads < 1 || C % heads || map.n_tok < 1 || map.n_tok > (axis == 0 ? 32 : 1024)) return -2;
+  switch (C / heads) {
+    case 64: return axis == 0 ? attn_spatial<_Float16, 64, 1>(qkv, out, n_seq, map, C, heads, st, 0.125f * emul)
+                              : attn_temporal2<_Float16, 64, 1>(qkv, out, n_seq, map, C, heads, st, 0.125f * emul);
+    case 32: return axis == 0 ? attn_spatial<_Float16, 32, 1>(qkv, out, n_seq, map, C, heads, st, 0.17677669529663689f * emul)
+                              : attn_temporal2<_Float16, 32, 1>(qkv, out, n_seq, map, C, heads, st, 0.17677669529663689f * emul);
+    case 16: return axis == 0 ? attn_spatial<_Float16, 16, 1>(qkv, out, n_seq, map, C, heads, st, 0.25f * emul)
+                              : attn_temporal2<_Float16, 16, 1>(qkv, out, n_seq, map, C, heads, st, 0.25f * emul);
+  }
+  return -2;
+}
 #else
 // (f16: 0 = bf16 rows in and out, 1 = IEEE fp16.  Head dim 64, 32 or 16.  Any SeqMap: <= 256 tokens the whole-sequence kernel, up
 //  to 1024 the chunked-key one.  hd_true: kernels.h)
@@ -477,3 +509,5 @@ int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap 
 #undef AF_HDT_PARAM
 #undef AF_HDT_ARG
 #undef AF_SCALE
+#undef AF_ESC_PARAM
+#undef AF_ESC_ARG

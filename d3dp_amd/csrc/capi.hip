@@ -224,6 +224,33 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
       }
     }
   }
+  // D3DP_FAST16_RANGE=scale (opt-in; read for FAST16 contexts alone): a block whose proven bound reaches 65504 stores the tensors that
+  // bound covers at a power-of-two multiple of their value instead of moving the whole context to bf16 (ctx.h fast16_scale; chosen at
+  // d3dp_set_weights).  The scaled kernels exist on the matrix-core route of the instantiated widths: the streaming Linear at K / 64
+  // in {1, 2, 4, 8, 16}, the three attention kernels at head dims 64 / 32 / 16, the row kernels at widths 64 ... 512.  Any other value,
+  // head dim 8 and the row attention kernel (no scaled form), and the padded widths of D3DP_FAST_IMPL=mfma are refused here, before
+  // the device is looked for -- never ignored.
+  bool fast16_scale = false;
+  if (g.mode == D3DP_MODE_FAST16) {
+    if (const char* fr = getenv("D3DP_FAST16_RANGE")) {
+      if (strcmp(fr, "scale"))
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_FAST16_RANGE=%.32s: the one value a FAST16 context takes is D3DP_FAST16_RANGE=scale", fr);
+      if (hdp)
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_FAST16_RANGE=scale with D3DP_FAST_IMPL=mfma at channels=%d: the padded-head kernels have no scaled "
+                                  "form", g.channels);
+      if (width_inst && !mfma_head_dim(hd))
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_FAST16_RANGE=scale at head dim %d (channels=%d heads=%d): the scaled attention kernels exist at head "
+                                  "dims 64, 32 and 16", hd, g.channels, g.heads);
+      const char* lr = getenv("D3DP_LONG_ATTN");
+      if (width_inst && lr && !strcmp(lr, "rows"))
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_FAST16_RANGE=scale with D3DP_LONG_ATTN=rows: the row attention kernel has no scaled form");
+      auto depth = [](int k) { return k == 64 || k == 128 || k == 256 || k == 512 || k == 1024; };
+      if (width_inst && !depth(g.hidden))
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_FAST16_RANGE=scale with hidden=%d: the scaled streaming Linear exists at k-depths 64, 128, 256, 512 "
+                                  "and 1024", g.hidden);
+      fast16_scale = width_inst;         // (any other width: refused below like every FAST16 context there)
+    }
+  }
   if (!width_inst && !hdp) {
     if (g.mode == D3DP_MODE_FAST)
       return d3dp_fail(D3DP_ENOTSUP, "channels=%d heads=%d hidden=%d: FAST contexts exist for channels in {64,128,256,512} with head dim in "
@@ -251,6 +278,7 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   c->cfg = g;
   c->fast_f16 = c->fast16() ? 1 : (c->fast() ? D3DP_FAST_F16 : 0);   // (FAST16: until d3dp_set_weights has seen the weights)
   c->hdp = hdp;
+  c->fast16_scale = fast16_scale;
   if (const int rc = read_switches(c, width_inst || hdp != 0, width_inst || hdp != 0 || train_widths); rc != D3DP_OK) {
     delete c;
     return rc;

@@ -93,13 +93,28 @@ int linear(d3dp_ctx* c, int cls, int epi, int out_f32, const void* A, const void
   return d3dp_launch_linear_f32(epi, (const float*)A, (const float*)W, bias, (float*)out, M, N, K, st);
 }
 
-int attention(d3dp_ctx* c, int axis, const void* qkv, void* out, int n_bh, float s_kv, hipStream_t st) {
+// A FAST16 Linear of a block under D3DP_FAST16_RANGE=scale: the A operand holds 2^-r_in times its value (0: a LayerNorm output, never
+// scaled) and the fp16 rows leave at 2^-r_out.  Both 0: the plain kernel, as in every other context.
+int linear_f16(d3dp_ctx* c, int cls, int epi, int r_in, int r_out, const void* A, const void* W, const float* bias, void* out, int M, int N,
+               int K, hipStream_t st) {
+  if (r_in == 0 && r_out == 0) return linear(c, cls, epi, 0, A, W, 1.f, bias, out, M, N, K, st);
+  Scope s(c, cls, st);
+  return d3dp_linear_stream_scaled(epi, A, W, bias, out, M, N, K, st, ldexpf(1.f, r_in - r_out), ldexpf(1.f, -r_out), ldexpf(1.f, r_out));
+}
+
+// (r_qkv: BlockDev's -- q, k and v at 2^-r_qkv in a FAST16 context under D3DP_FAST16_RANGE=scale; 0 everywhere else)
+int attention(d3dp_ctx* c, int axis, const void* qkv, void* out, int n_bh, float s_kv, hipStream_t st, int r_qkv = 0) {
   const d3dp_cfg& g = c->cfg;
   Scope s(c, axis == 0 ? P_ATTN_S : P_ATTN_T, st);
   // (seq_pitch() exceeds F J on the X2 route alone: every other kernel sees the unpadded map)
   // (a padded-head context: rows of attn_cols() = heads x hdp columns, the true head dim in the softmax exponent)
   const int n = axis == 0 ? n_bh * g.frames : n_bh * g.joints, act = c->act(), C = c->attn_cols();
   const SeqMap map = axis == 0 ? spatial_map(g.frames, g.joints, c->seq_pitch()) : temporal_map(g.frames, g.joints, c->seq_pitch());
+  if (r_qkv != 0) {          // (d3dp_create let the switch through for the matrix-core routes alone)
+    const AttnRoute r = c->route(axis);
+    if (r != AttnRoute::FAST_SPATIAL && r != AttnRoute::FAST_WHOLE_SEQ) return -2;
+    return d3dp_attn_fast_scaled(r == AttnRoute::FAST_SPATIAL ? 0 : 1, qkv, out, n, map, C, g.heads, st, ldexpf(1.f, 2 * r_qkv));
+  }
   switch (c->route(axis)) {
     case AttnRoute::X2: return d3dp_launch_attn_x2(3, axis, qkv, out, n, map, C, g.heads, s_kv, st, g.channels / g.heads);
     case AttnRoute::FAST_SPATIAL: return d3dp_launch_attn_spatial_bf16(qkv, out, n, map, C, g.heads, st, c->fast_f16, g.channels / g.heads);
@@ -124,6 +139,22 @@ int run_block(d3dp_ctx* c, const BlockDev& w, int axis, float* x, void* y1, void
   // (s_kv / s_h differ from kActScale only in EXACT f16x2 contexts whose weights asked for it, and s_kv only with the x2
   //  attention kernels: the other attention kernels write their output planes at kActScale)
   const float s_o = c->x2_attn() ? w.s_kv : kActScale;
+  if (w.r_qkv | w.r_proj | w.r_h | w.r_fc2) {
+    // FAST16 under D3DP_FAST16_RANGE=scale, a block with a bound beyond 65504: the FAST dataflow below with this block's four
+    // multipliers (BlockDev::r_*).  proj takes the attention output's scale out as it applies its own, fc2 the hidden's; norm2 adds
+    // y1 2^r_proj, and the caller's norm pair / head adds y1 2^r_proj and y 2^r_fc2.  A class whose exponent is 0 runs the plain kernel.
+    LAUNCH_TRY(linear_f16(c, P_QKV, EPI_BIAS, 0, w.r_qkv, bufA, w.qkv_w, w.qkv_b, bufB, Tc, 3 * Ca, C, st));
+    LAUNCH_TRY(attention(c, axis, bufB, bufA, n_bh, s_o, st, w.r_qkv));
+    LAUNCH_TRY(linear_f16(c, P_PROJ, EPI_BIAS, w.r_qkv, w.r_proj, bufA, w.proj_w, w.proj_b, y1, Tc, C, Ca, st));
+    {
+      Scope s(c, P_LN, st);
+      if (w.r_proj) LAUNCH_TRY(d3dp_launch_ln_scaled(x, y1, ldexpf(1.f, w.r_proj), w.n2w, w.n2b, g.eps_block, bufA, Tc, C, st));
+      else LAUNCH_TRY(d3dp_launch_ln(c->act(), x, y1, 0, w.n2w, w.n2b, g.eps_block, bufA, Tc, C, st));
+    }
+    LAUNCH_TRY(linear_f16(c, P_FC1, EPI_GELU, 0, w.r_h, bufA, w.fc1_w, w.fc1_b, bufB, Tc, g.hidden, C, st));
+    LAUNCH_TRY(linear_f16(c, P_FC2, EPI_BIAS, w.r_h, w.r_fc2, bufB, w.fc2_w, w.fc2_b, y, Tc, C, g.hidden, st));
+    return 0;
+  }
   LAUNCH_TRY(linear(c, P_QKV, EPI_BIAS, 0, bufA, w.qkv_w, w.qkv_u, w.qkv_b, bufB, Tc, 3 * Ca, C, st, nullptr, nullptr, kActScale, s_o));
   LAUNCH_TRY(attention(c, axis, bufB, bufA, n_bh, s_o, st));
   const bool fold = c->fold_resid();   // EXACT split-fp16 Linears: x += proj / fc2 inside their epilogues
@@ -197,8 +228,12 @@ int d3dp_denoise(d3dp_ctx* c, const float* x2d, const float* x_t, const int64_t*
         LAUNCH_TRY(d3dp_launch_ln2_defer(c->act(), x, c->snw, c->snb, c->tte[d].n1w, c->tte[d].n1b, g.eps_block, bufA, nstat, Tc, C, st));
       } else {
         Scope s(c, P_LN2, st);   // x += fc2 out; Spatial_norm (+ Temporal_pos after block 0); TTE block d's norm1
-        LAUNCH_TRY(d3dp_launch_ln2(c->act(), x, fold ? nullptr : y1, fold ? nullptr : y, c->snw, c->snb, d == 0 ? c->tpos : nullptr, c->tte[d].n1w,
-                                   c->tte[d].n1b, g.eps_block, bufA, Tc, C, F, J, st, SP));
+        if (const BlockDev& p = c->ste[d]; p.r_proj | p.r_fc2)      // (FAST16, scaled branch outputs of the block in front)
+          LAUNCH_TRY(d3dp_launch_ln2_scaled(x, y1, ldexpf(1.f, p.r_proj), y, ldexpf(1.f, p.r_fc2), c->snw, c->snb, d == 0 ? c->tpos : nullptr,
+                                            c->tte[d].n1w, c->tte[d].n1b, g.eps_block, bufA, Tc, C, F, J, st, SP));
+        else
+          LAUNCH_TRY(d3dp_launch_ln2(c->act(), x, fold ? nullptr : y1, fold ? nullptr : y, c->snw, c->snb, d == 0 ? c->tpos : nullptr, c->tte[d].n1w,
+                                     c->tte[d].n1b, g.eps_block, bufA, Tc, C, F, J, st, SP));
       }
       r = run_block(c, c->tte[d], 1, x, y1, y, bufA, bufB, slices, rowstat, n, st, defer && d > 0 ? nstat : nullptr);
       if (r) return r;
@@ -207,14 +242,22 @@ int d3dp_denoise(d3dp_ctx* c, const float* x2d, const float* x_t, const int64_t*
         LAUNCH_TRY(d3dp_launch_ln2_defer(c->act(), x, c->tnw, c->tnb, c->ste[d + 1].n1w, c->ste[d + 1].n1b, g.eps_block, bufA, nstat, Tc, C, st));
       } else if (d + 1 < g.depth) {
         Scope s(c, P_LN2, st);   // x += fc2 out; Temporal_norm; STE block d+1's norm1
-        LAUNCH_TRY(d3dp_launch_ln2(c->act(), x, fold ? nullptr : y1, fold ? nullptr : y, c->tnw, c->tnb, nullptr, c->ste[d + 1].n1w, c->ste[d + 1].n1b,
-                                   g.eps_block, bufA, Tc, C, F, J, st, SP));
+        if (const BlockDev& p = c->tte[d]; p.r_proj | p.r_fc2)
+          LAUNCH_TRY(d3dp_launch_ln2_scaled(x, y1, ldexpf(1.f, p.r_proj), y, ldexpf(1.f, p.r_fc2), c->tnw, c->tnb, nullptr, c->ste[d + 1].n1w,
+                                            c->ste[d + 1].n1b, g.eps_block, bufA, Tc, C, F, J, st, SP));
+        else
+          LAUNCH_TRY(d3dp_launch_ln2(c->act(), x, fold ? nullptr : y1, fold ? nullptr : y, c->tnw, c->tnb, nullptr, c->ste[d + 1].n1w, c->ste[d + 1].n1b,
+                                     g.eps_block, bufA, Tc, C, F, J, st, SP));
       }
     }
     {
       Scope s(c, P_HEAD, st);    // x += fc2 out; Temporal_norm; head LayerNorm; Linear(C,3)
-      LAUNCH_TRY(d3dp_launch_head(c->fast() ? c->act() : 0, x, fold ? nullptr : y1, fold ? nullptr : y, c->tnw, c->tnb, g.eps_block, c->hnw, c->hnb, g.eps_head, c->hw, c->hb,
-                                  out + (size_t)seq0 * FJ * 3, Tc, C, st, FJ, SP));
+      if (const BlockDev& p = c->tte[g.depth - 1]; p.r_proj | p.r_fc2)
+        LAUNCH_TRY(d3dp_launch_head_scaled(x, y1, ldexpf(1.f, p.r_proj), y, ldexpf(1.f, p.r_fc2), c->tnw, c->tnb, g.eps_block, c->hnw, c->hnb,
+                                           g.eps_head, c->hw, c->hb, out + (size_t)seq0 * FJ * 3, Tc, C, st, FJ, SP));
+      else
+        LAUNCH_TRY(d3dp_launch_head(c->fast() ? c->act() : 0, x, fold ? nullptr : y1, fold ? nullptr : y, c->tnw, c->tnb, g.eps_block, c->hnw, c->hnb, g.eps_head, c->hw, c->hb,
+                                    out + (size_t)seq0 * FJ * 3, Tc, C, st, FJ, SP));
     }
     seq0 += n;
   }

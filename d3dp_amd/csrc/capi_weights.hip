@@ -234,6 +234,12 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
   // (or with a non-finite weight): the bf16 kernels, i.e. exactly what a D3DP_MODE_FAST context launches on these weights --
   // never an error, never an inf that FAST would not give.  Both types are 2 bytes, so nothing below depends on the outcome
   // but the conversion kernel's and the launchers' type argument.
+  // D3DP_FAST16_RANGE=scale (c->fast16_scale): the four bounds a weight edit can push out of range -- b_qkv, b_proj, b_h, b_fc2 -- lower
+  // their block's power-of-two multiplier for the tensors they cover instead (shift(): the smallest s >= 0 with bound x 2^-s < 65504;
+  // ctx.h BlockDev::r_*), as pick() above does for EXACT.  LayerNorm outputs and the weight matrices are never scaled: L1, L2 and the
+  // four max |w| must stay below 65504, every weight finite and every s <= kFast16MaxShift -- otherwise the bf16 kernels, as without
+  // the switch.  fast_bound keeps its meaning: the proven maximum of the VALUES, so 'fp16' beside a bound >= 65504 means scaled.
+  std::vector<int> blk_shift(8 * (size_t)g.depth, 0);                // [kind][d][r_qkv, r_proj, r_h, r_fc2]
   if (c->fast16()) {
     const size_t nb = 2 * (size_t)g.depth;
     unsigned* dbound = nullptr;
@@ -269,6 +275,25 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
     }
     c->fast_bound = finite ? worst : INFINITY;
     c->fast_f16 = (finite && worst < 65504.0f) ? 1 : 0;
+    if (c->fast16_scale && finite && !c->fast_f16) {
+      auto shift = [](float bound) {                     // (finite bounds only: at most 128 halvings)
+        int sh = 0;
+        while (!(ldexpf(bound, -sh) < 65504.0f)) ++sh;
+        return sh;
+      };
+      bool ok = true;
+      for (size_t i = 0; i < nb && ok; ++i) {
+        const float* o = hb.data() + i * kF16Slots;     // (slots: fast16_bound_kernel's launches above)
+        const int unscaled[] = {0, 4, 7, 8, 9, 10}, scaled[] = {1, 3, 5, 6};
+        for (const int k : unscaled) ok = ok && o[k] < 65504.0f;
+        for (int k = 0; k < 4; ++k) {
+          blk_shift[4 * i + k] = shift(o[scaled[k]]);
+          ok = ok && blk_shift[4 * i + k] <= kFast16MaxShift;
+        }
+      }
+      if (ok) c->fast_f16 = 1;
+      else std::fill(blk_shift.begin(), blk_shift.end(), 0);
+    }
   }
   const size_t ws = c->fast() ? 2 : (c->x3() ? 6 : 4);   // bytes per weight-matrix element (bf16 or fp16 / 3 bf16 planes / fp32)
   // ---- arena layout ----
@@ -395,6 +420,7 @@ int d3dp_set_weights(d3dp_ctx* c, const d3dp_weights* w, void* stream) {
                unscale[bi.v[2]], unscale[bi.v[4]], unscale[bi.v[8]], unscale[bi.v[10]], F32(bi.v[12]),
                blk_scale[2 * k], blk_scale[2 * k + 1]};
     if (bi.bgb) b.proj_bgb = F32(bi.v[5]);
+    b.r_qkv = blk_shift[4 * k]; b.r_proj = blk_shift[4 * k + 1]; b.r_h = blk_shift[4 * k + 2]; b.r_fc2 = blk_shift[4 * k + 3];
     (k < (size_t)g.depth ? c->ste : c->tte).push_back(b);
   }
   c->weights_set = true;

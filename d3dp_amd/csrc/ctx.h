@@ -45,7 +45,18 @@ struct BlockDev {
   // (LayerNorm outputs always use 2^4: their bound is sqrt(C-1) |gamma| + |beta|).
   float s_kv = kActScale, s_h = kActScale;
   const float* proj_bgb = nullptr;  // defer_norm: [proj_b | gamma | beta] of the shared norm in FRONT of the block (EPI_RESID_NORM)
+  // FAST16 under D3DP_FAST16_RANGE=scale (d3dp_ctx::fast16_scale): the exponents s of the power-of-two multipliers 2^-s at which this
+  // block's four classes of fp16 tensors are stored -- q / k / v and the attention output (r_qkv, from b_qkv), the proj output
+  // (r_proj, from b_proj), the MLP hidden and the pre-activation parked in front of the GELU (r_h, from b_h), the fc2 output (r_fc2,
+  // from b_fc2) -- each the smallest s >= 0 with bound x 2^-s < 65504, chosen at d3dp_set_weights (at most kFast16MaxShift, or the
+  // context falls back to bf16).  All 0 in every other context, and wherever the bound is below 65504: the plain kernels.
+  int r_qkv = 0, r_proj = 0, r_h = 0, r_fc2 = 0;
 };
+// The largest exponent D3DP_FAST16_RANGE=scale takes.  An fp16 emulation on a CPU that stores all four classes of EVERY block at
+// 2^-s stays within 1.17x of the unscaled emulation's distance to the fp32 oracle for every s <= 12 and is 2.2 - 2.6x away at s = 14
+// (what 2^-s pushes into fp16's subnormal range is, up to there, far below the rounding of the large values it is added to); 8
+// leaves 2^4 of that (profiles/fast16_scaled.md)
+constexpr int kFast16MaxShift = 8;
 
 constexpr size_t kAlign = 256;
 inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
@@ -87,6 +98,11 @@ struct d3dp_ctx {
   bool fast() const { return cfg.mode == D3DP_MODE_FAST || fast16(); }
   int fast_f16 = 0;
   float fast_bound = 0.f;
+  // D3DP_FAST16_RANGE=scale (opt-in, read at d3dp_create for FAST16 contexts alone): a per-block bound that reaches 65504 lowers that
+  // block's power-of-two scale for the tensor class it bounds (BlockDev::r_*) instead of moving the whole context to bf16 -- what
+  // EXACT does with s_kv / s_h.  The context still falls back when a weight is non-finite, when a LayerNorm output bound or a
+  // max |w| reaches 65504 (neither is scaled), or when a class would need more than 2^-kFast16MaxShift.
+  bool fast16_scale = false;
   // EXACT mode runs its Linears on split-fp16 operands (2 planes, 3 fp16-MFMA passes, gemm_x2.hip); activations that
   // feed a Linear are then two fp16 planes.  env D3DP_EXACT_IMPL=bf16x3 selects the round-1 six-pass split-bf16 kernels
   // and =f32 the plain fp32-MFMA kernels (bitwise an fp32 fmaf chain) -- both kept as cross-checks.

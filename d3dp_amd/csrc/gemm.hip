@@ -165,9 +165,9 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 
 }  // namespace
 
-// (gemm_stream_widths.hip includes this file with D3DP_STREAM_WIDTHS_TU defined for the streaming kernel's template alone: see
-//  the bottom of the file)
-#ifndef D3DP_STREAM_WIDTHS_TU
+// (gemm_stream_widths.hip and gemm_stream_scaled.hip include this file with D3DP_STREAM_WIDTHS_TU / D3DP_STREAM_SCALED_TU defined for
+//  the streaming kernel's template alone: see the bottom of the file)
+#if !defined(D3DP_STREAM_WIDTHS_TU) && !defined(D3DP_STREAM_SCALED_TU)
 // ------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------
@@ -377,7 +377,7 @@ void d3dp_launch_split3(const float* src, void* dst, size_t n, hipStream_t st) {
   const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
   hipLaunchKernelGGL(split3_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, st, src, (bf16*)dst, n);
 }
-#endif  // D3DP_STREAM_WIDTHS_TU
+#endif  // D3DP_STREAM_WIDTHS_TU, D3DP_STREAM_SCALED_TU
 
 // ================================================================================================
 // FAST mode, persistent streaming GEMM ("v2"): the kernel the denoiser launches for every Linear.
@@ -392,6 +392,32 @@ void d3dp_launch_split3(const float* src, void* dst, size_t n, hipStream_t st) {
 //     in vmcnt on gfx950) cannot stall the operand pipeline.  One raw s_barrier per k-step.
 //   * bias sits in LDS (read with ds_read, lgkmcnt), so the epilogue issues no vector loads at all.
 // ================================================================================================
+// The SCALED epilogue (gemm_stream_scaled.hip includes this file with D3DP_STREAM_SCALED_TU defined): a FAST16 context under
+// D3DP_FAST16_RANGE=scale keeps a block's q / k / v, proj output, MLP hidden and fc2 output in fp16 at a power-of-two multiple 2^-s of
+// their value (ctx.h BlockDev::r_*).  Three powers of two arrive by value: the finished tile leaves as fma(acc, m_acc, bias m_bias)
+// -- m_acc = 2^(s_in - s_out) takes the A operand's own scale out and puts the output's in, m_bias = 2^-s_out is multiplied into
+// the bias as it is copied to LDS -- and the GELU form, whose parked fp16 pre-activation carries m_acc = m_bias = 2^-s_h, evaluates
+// gelu_fast on the value multiplied back by m_inv = 2^s_h in fp32 and stores gelu x m_acc.  There the kernel and launcher templates
+// carry one more template parameter and these arguments; here the GS_ macros expand to the plain forms, the instantiations are the
+// ones this file always had and keep their device code (profiles/fast16_scaled.md).
+#ifdef D3DP_STREAM_SCALED_TU
+#define GS_TPARAM , int SCALED = 1
+#define GS_KPARAM , float m_acc, float m_bias, float m_inv
+#define GS_KTYPES , float, float, float
+#define GS_KARGS , m_acc, m_bias, m_inv
+#define GS_BIAS(b) ((b) * m_bias)
+#define GS_OUT(a, b) fmaf((a), m_acc, (b))
+#define GS_GELU(pre) (gelu_fast((pre) * m_inv) * m_acc)
+#else
+#define GS_TPARAM
+#define GS_KPARAM
+#define GS_KTYPES
+#define GS_KARGS
+#define GS_BIAS(b) (b)
+#define GS_OUT(a, b) ((a) + (b))
+#define GS_GELU(pre) gelu_fast(pre)
+#endif
+
 namespace {
 
 constexpr int SBM = 256, SBN = 128, SBK = 64;
@@ -440,10 +466,10 @@ __device__ __forceinline__ int sperm(int q) {   // q = ni*16 + i in [0,64)
 // contention between compute waves, 0.375 instead of 0.5 LDS fragment reads per MFMA).
 // WIDE is a name tag only (same code): the qkv Linear (N = 3K) is instantiated as its own kernel symbol so that
 // rocprofv3 --stats reports it separately from the proj Linear, which shares EPI / OutT / NK with it.
-template <typename E, int EPI, typename OutT, int NK, int MI, int WIDE = 0>
+template <typename E, int EPI, typename OutT, int NK, int MI, int WIDE = 0 GS_TPARAM>
 __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(const E* __restrict__ A, const E* __restrict__ W,
                                                                const float* __restrict__ bias, OutT* __restrict__ out,
-                                                               int M, int N, int tiles_n, int total_tiles) {
+                                                               int M, int N, int tiles_n, int total_tiles GS_KPARAM) {
   using e4 = typename Op2<E>::x4;
   using e8 = typename Op2<E>::x8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -460,7 +486,7 @@ __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(c
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  for (int i = tid; i < N; i += (NCW + 4) * 64) sbias[i] = bias[i];
+  for (int i = tid; i < N; i += (NCW + 4) * 64) sbias[i] = GS_BIAS(bias[i]);
   __syncthreads();
 
   if (wave >= NCW) {
@@ -524,7 +550,7 @@ __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(c
     if constexpr (EPI == EPI_GELU) {
       const f16x4 pre = pend[0];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (E)gelu_fast((float)pre[e]);
+      for (int e = 0; e < 4; ++e) v[e] = (E)GS_GELU((float)pre[e]);
       // keep the activation OUT of the store's bounds branch (LLVM would sink it there, behind the MFMA block)
       asm volatile("" : "+v"(v));
     } else {
@@ -619,8 +645,8 @@ __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(c
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          pend[mi * 4 + r] = (pend_t){(pelt_t)(acc[mi][0][r] + b.x), (pelt_t)(acc[mi][1][r] + b.y),
-                                      (pelt_t)(acc[mi][2][r] + b.z), (pelt_t)(acc[mi][3][r] + b.w)};
+          pend[mi * 4 + r] = (pend_t){(pelt_t)GS_OUT(acc[mi][0][r], b.x), (pelt_t)GS_OUT(acc[mi][1][r], b.y),
+                                      (pelt_t)GS_OUT(acc[mi][2][r], b.z), (pelt_t)GS_OUT(acc[mi][3][r], b.w)};
     }
     have_pend = true;
   }
@@ -631,10 +657,10 @@ __global__ __launch_bounds__(MI == 4 ? 768 : 512) void gemm_bf16_stream_kernel(c
 }
 
 template <typename E, int EPI, typename OutT, int NK, int MI>
-int launch_stream_nk_mi(const void* A, const void* W, const float* bias, void* out, int M, int N, hipStream_t st) {
+int launch_stream_nk_mi(const void* A, const void* W, const float* bias, void* out, int M, int N, hipStream_t st GS_KPARAM) {
   const int tm = (M + SBM - 1) / SBM, tn = (N + SBN - 1) / SBN;
   const int total = tm * tn;
-  void (*kern)(const E*, const E*, const float*, OutT*, int, int, int, int) =
+  void (*kern)(const E*, const E*, const float*, OutT*, int, int, int, int GS_KTYPES) =
       gemm_bf16_stream_kernel<E, EPI, OutT, NK, MI, 0>;
   if constexpr (EPI == EPI_BIAS && sizeof(OutT) == 2 && NK == 8) {
     if (N == 3 * NK * SBK) kern = gemm_bf16_stream_kernel<E, EPI, OutT, NK, MI, 1>;
@@ -647,15 +673,15 @@ int launch_stream_nk_mi(const void* A, const void* W, const float* bias, void* o
   if (n_cu < 0) return -3;
   const int grid = total < n_cu ? total : n_cu;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(MI == 4 ? 768 : 512), SLDS_BYTES, st, (const E*)A, (const E*)W, bias,
-                     (OutT*)out, M, N, tn, total);
+                     (OutT*)out, M, N, tn, total GS_KARGS);
   return 0;
 }
 
 template <typename E, int EPI, typename OutT, int NK>
-int launch_stream_nk(const void* A, const void* W, const float* bias, void* out, int M, int N, hipStream_t st) {
+int launch_stream_nk(const void* A, const void* W, const float* bias, void* out, int M, int N, hipStream_t st GS_KPARAM) {
   // MI = 8 (four compute waves of 128x64, one per SIMD) was measured: slower on qkv (a lone wave cannot hide its own
   // ds_read latency), within noise elsewhere -- not instantiated.
-  return launch_stream_nk_mi<E, EPI, OutT, NK, 4>(A, W, bias, out, M, N, st);
+  return launch_stream_nk_mi<E, EPI, OutT, NK, 4>(A, W, bias, out, M, N, st GS_KARGS);
 }
 
 // K / 64 outside {1, 2, 4, 8, 16}: the k-depths of channels 192 / 320 / 384 / 448 (FAST / FAST16 contexts under D3DP_FAST_IMPL=mfma)
@@ -679,6 +705,19 @@ int launch_stream_widths(const void* A, const void* W, const float* bias, void* 
       case 12: return launch_stream_nk<E, EPI, E, 12>(A, W, bias, out, M, N, st);
       case 14: return launch_stream_nk<E, EPI, E, 14>(A, W, bias, out, M, N, st);
     }
+  }
+  return -1;
+}
+#elif defined(D3DP_STREAM_SCALED_TU)
+// the scaled epilogue exists on fp16 operands with fp16 rows out, at the k-depths of the instantiated widths
+template <int EPI>
+int launch_stream_scaled(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, hipStream_t st GS_KPARAM) {
+  switch (K / SBK) {
+    case 1: return launch_stream_nk<_Float16, EPI, _Float16, 1>(A, W, bias, out, M, N, st GS_KARGS);
+    case 2: return launch_stream_nk<_Float16, EPI, _Float16, 2>(A, W, bias, out, M, N, st GS_KARGS);
+    case 4: return launch_stream_nk<_Float16, EPI, _Float16, 4>(A, W, bias, out, M, N, st GS_KARGS);
+    case 8: return launch_stream_nk<_Float16, EPI, _Float16, 8>(A, W, bias, out, M, N, st GS_KARGS);
+    case 16: return launch_stream_nk<_Float16, EPI, _Float16, 16>(A, W, bias, out, M, N, st GS_KARGS);
   }
   return -1;
 }
@@ -711,6 +750,16 @@ int d3dp_linear_stream_widths(int epi, const void* A, const void* W, const float
                                   : launch_stream_widths<__bf16, EPI_GELU>(A, W, bias, out, M, N, K, st);
   return -1;
 }
+#elif defined(D3DP_STREAM_SCALED_TU)
+// out[M,N] = fp16 of epi(A W^T m_acc + bias m_bias) on fp16 operands, K / 64 in {1, 2, 4, 8, 16}; EPI_GELU: gelu(. m_inv) m_acc with
+// m_acc == m_bias and m_inv = 1 / m_acc.  The three multipliers are powers of two (kernels.h); -1 for any other shape or epilogue
+int d3dp_linear_stream_scaled(int epi, const void* A, const void* W, const float* bias, void* out, int M, int N, int K, hipStream_t st,
+                              float m_acc, float m_bias, float m_inv) {
+  if (K % SBK != 0 || N % 4 != 0 || N > SBIAS_MAX || M <= 0) return -1;
+  if (epi == EPI_BIAS) return launch_stream_scaled<EPI_BIAS>(A, W, bias, out, M, N, K, st GS_KARGS);
+  if (epi == EPI_GELU && m_acc == m_bias) return launch_stream_scaled<EPI_GELU>(A, W, bias, out, M, N, K, st GS_KARGS);
+  return -1;
+}
 #else
 // out[M,N] = epi(A W^T + bias); epi in {EPI_BIAS, EPI_GELU}; operands bf16 (f16 == 0) or IEEE fp16 (f16 == 1); out of the
 // operand type or fp32.
@@ -729,3 +778,10 @@ int d3dp_launch_linear_bf16_stream(int epi, int out_f32, const void* A, const vo
              : linear_stream<__bf16>(epi, out_f32, A, W, bias, out, M, N, K, st);
 }
 #endif
+#undef GS_TPARAM
+#undef GS_KPARAM
+#undef GS_KTYPES
+#undef GS_KARGS
+#undef GS_BIAS
+#undef GS_OUT
+#undef GS_GELU

@@ -47,6 +47,12 @@ int d3dp_launch_linear_bf16_stream(int epi, int out_f32, const void* A, const vo
 //  channels 192 / 320 / 384 / 448 -- through gemm_stream_widths.hip, the same kernel template at those NK; -1 for any other)
 int d3dp_linear_stream_widths(int epi, const void* A, const void* W, const float* bias, void* out, int M, int N, int K,
                               hipStream_t st, int f16);
+// (gemm_stream_scaled.hip: the same kernel template with the scaled epilogue of FAST16 contexts under D3DP_FAST16_RANGE=scale -- fp16
+//  operands and fp16 rows out, K / 64 in {1, 2, 4, 8, 16}, epi EPI_BIAS or EPI_GELU.  out = fp16(fma(acc, m_acc, bias m_bias)); EPI_GELU
+//  (m_acc == m_bias): that value parked as fp16, then fp16(gelu(. m_inv) m_acc) with m_inv = 1 / m_acc.  All three are powers of two;
+//  -1 for any other shape)
+int d3dp_linear_stream_scaled(int epi, const void* A, const void* W, const float* bias, void* out, int M, int N, int K, hipStream_t st,
+                              float m_acc, float m_bias, float m_inv);
 int d3dp_launch_linear_bf16x3(int epi, const void* A3, const void* W3, const float* bias, float* outf, void* out3, int M,
                               int N, int K, hipStream_t st);
 void d3dp_launch_split3(const float* src, void* dst, size_t n, hipStream_t st);
@@ -188,6 +194,9 @@ int d3dp_launch_attn_spatial_bf16(const void* qkv, void* out, int n_seq, SeqMap 
 // (attention_fast_pad.hip: the padded forms behind the two launchers above; axis 0 = the spatial kernel, <= 32 tokens)
 int d3dp_attn_fast_padded(int axis, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st, int f16,
                           int hd_true);
+// (attention_fast_scaled.hip: the same kernels on fp16 rows whose q, k and v hold 2^-s times their value -- FAST16 contexts under
+//  D3DP_FAST16_RANGE=scale; the exponent scale is (C / heads)^-0.5 x emul, emul = 2^(2s); head dim 64, 32 or 16; axis as above)
+int d3dp_attn_fast_scaled(int axis, const void* qkv, void* out, int n_seq, SeqMap map, int C, int heads, hipStream_t st, float emul);
 // ---- attention_x2.hip: EXACT on split-fp16 operands (head dim 64, 32 or 16; -2 for any other) ----
 // split-fp16 attention: `qkv` = PACKED rows of 12 C bytes (q fp32 | k hi | k lo | v hi | v lo), written by the qkv Linear
 // with EPI_QKV_PACK or from fp32 rows by d3dp_launch_qkv_pack_x2
@@ -233,6 +242,17 @@ int d3dp_rows2_ln2(int act, float* x, const void* yadd0, const void* yadd, const
 int d3dp_rows2_head(int act, const float* x, const void* yadd0, const void* yadd, const float* wa, const float* ba, float eps_a,
                     const float* wh, const float* bh, float eps_h, const float* w, const float* b, float* out, int T, int C,
                     hipStream_t st, int FJ, int SP);
+// ---- the ln / ln2 / head launchers around this block for FAST16 contexts under D3DP_FAST16_RANGE=scale: fp16 activations at the
+// instantiated widths (-2 otherwise), every yadd operand there (-1 otherwise) with the power-of-two multiplier m that takes its
+// fp16 rows back to their value -- x + yadd m (ln, never written back), (x + yadd0 m0) + yadd m (ln2, head)
+int d3dp_launch_ln_scaled(const float* x, const void* yadd, float m, const float* w, const float* b, float eps, void* xn, int T, int C,
+                          hipStream_t st);
+int d3dp_launch_ln2_scaled(float* x, const void* yadd0, float m0, const void* yadd, float m, const float* wa, const float* ba,
+                           const float* pos, const float* wb, const float* bb, float eps, void* xn, int T, int C, int F, int J,
+                           hipStream_t st, int SP);
+int d3dp_launch_head_scaled(const float* x, const void* yadd0, float m0, const void* yadd, float m, const float* wa, const float* ba,
+                            float eps_a, const float* wh, const float* bh, float eps_h, const float* w, const float* b, float* out, int T,
+                            int C, hipStream_t st, int FJ, int SP);
 // out[T,3] = Linear(LN_head(LN_a(x)))
 int d3dp_launch_head(int act_bf16, const float* x, const void* yadd0, const void* yadd, const float* wa, const float* ba, float eps_a, const float* wh,
                      const float* bh, float eps_h, const float* w, const float* b, float* out, int T, int C,

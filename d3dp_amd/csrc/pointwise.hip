@@ -429,6 +429,104 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
   }
 }
 
+// ---- FAST16 under D3DP_FAST16_RANGE=scale: fp16 branch outputs at a power-of-two multiple of their value ------------------------
+// The proj / fc2 rows of a block whose proven bound reaches 65504 arrive as y 2^-s (ctx.h BlockDev::r_proj, r_fc2).  The three row
+// kernels that add branch outputs to the fp32 residual stream -- ln_kernel, ln2_kernel and head_kernel above, in their fp16 forms
+// without write_x -- take the multiplier 2^s of each yadd operand by value and add y m in fp32: the product is exact, so fmaf(y, m, v)
+// is the plain kernels' v + y on the value the row stands for.  Everything else is those kernels' arithmetic, statement for
+// statement.  Both operands are always there (the FAST dataflow never folds the adds into the Linears).
+template <int C>
+__global__ __launch_bounds__(256) void ln_scaled_kernel(const float* __restrict__ x, const f16* __restrict__ yadd, float m,
+                                                        const float* __restrict__ w, const float* __restrict__ b, float eps,
+                                                        f16* __restrict__ xn, int T) {
+  using R = Row<C>;
+  const int lane = threadIdx.x & 63;
+  const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (tok >= T) return;
+  float v[R::NV], y[R::NV];
+  if (NT_STREAMS) R::load_nt(x + (size_t)tok * C, lane, v); else R::load(x + (size_t)tok * C, lane, v);
+  if (NT_STREAMS && NT_Y) R::load_nt(yadd + (size_t)tok * C, lane, y); else R::load(yadd + (size_t)tok * C, lane, y);
+#pragma unroll
+  for (int i = 0; i < R::NV; ++i) v[i] = fmaf(y[i], m, v[i]);
+  R::norm(v, w, b, eps, lane, y);
+  ActOut<C, f16>::st(xn, 0, (size_t)tok * C, lane, y);
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void ln2_scaled_kernel(float* __restrict__ x, const f16* __restrict__ yadd0, float m0,
+                                                         const f16* __restrict__ yadd, float m, const float* __restrict__ wa,
+                                                         const float* __restrict__ ba, const float* __restrict__ pos,
+                                                         const float* __restrict__ wb, const float* __restrict__ bb, float eps,
+                                                         f16* __restrict__ xn, int T, int F, int J, int SP) {
+  using R = Row<C>;
+  const int lane = threadIdx.x & 63;
+  const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (tok >= T) return;
+  float v[R::NV], y[R::NV], z[R::NV];
+  if (NT_STREAMS) R::load_nt(x + (size_t)tok * C, lane, v); else R::load(x + (size_t)tok * C, lane, v);
+  if (NT_STREAMS && NT_Y) R::load_nt(yadd0 + (size_t)tok * C, lane, y); else R::load(yadd0 + (size_t)tok * C, lane, y);
+#pragma unroll
+  for (int i = 0; i < R::NV; ++i) v[i] = fmaf(y[i], m0, v[i]);
+  if (NT_STREAMS && NT_Y) R::load_nt(yadd + (size_t)tok * C, lane, y); else R::load(yadd + (size_t)tok * C, lane, y);
+#pragma unroll
+  for (int i = 0; i < R::NV; ++i) v[i] = fmaf(y[i], m, v[i]);
+  R::norm(v, wa, ba, eps, lane, y);
+  if (pos != nullptr) {
+    const int f = min((tok % SP) / J, F - 1);
+    float pv[R::NV];
+    R::load(pos + (size_t)f * C, lane, pv);
+#pragma unroll
+    for (int i = 0; i < R::NV; ++i) y[i] += pv[i];
+  }
+  if (NT_STREAMS) R::store_nt(x + (size_t)tok * C, lane, y); else R::store(x + (size_t)tok * C, lane, y);
+  R::norm(y, wb, bb, eps, lane, z);
+  ActOut<C, f16>::st(xn, 0, (size_t)tok * C, lane, z);
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void head_scaled_kernel(const float* __restrict__ x, const f16* __restrict__ yadd0, float m0,
+                                                          const f16* __restrict__ yadd, float m, const float* __restrict__ wa,
+                                                          const float* __restrict__ ba, float eps_a,
+                                                          const float* __restrict__ wh, const float* __restrict__ bh,
+                                                          float eps_h, const float* __restrict__ w, const float* __restrict__ b,
+                                                          float* __restrict__ out, int T, int FJ, int SP) {
+  using R = Row<C>;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  float wav[R::NV], bav[R::NV], whv[R::NV], bhv[R::NV], wv[3][R::NV];
+  R::load(wa, lane, wav);
+  R::load(ba, lane, bav);
+  R::load(wh, lane, whv);
+  R::load(bh, lane, bhv);
+#pragma unroll
+  for (int o = 0; o < 3; ++o) R::load(w + o * C, lane, wv[o]);
+  const float b0 = b[0], b1 = b[1], b2 = b[2];
+  for (int it = 0; it < kRowTokens; ++it) {
+    const int tok = (blockIdx.x * kRowTokens + it) * 4 + wave;
+    if (tok >= T) break;
+    float v[R::NV], y[R::NV], z[R::NV];
+    if (NT_STREAMS) R::load_nt(x + (size_t)tok * C, lane, v); else R::load(x + (size_t)tok * C, lane, v);
+    if (NT_STREAMS && NT_Y) R::load_nt(yadd0 + (size_t)tok * C, lane, y); else R::load(yadd0 + (size_t)tok * C, lane, y);
+#pragma unroll
+    for (int i = 0; i < R::NV; ++i) v[i] = fmaf(y[i], m0, v[i]);
+    if (NT_STREAMS && NT_Y) R::load_nt(yadd + (size_t)tok * C, lane, y); else R::load(yadd + (size_t)tok * C, lane, y);
+#pragma unroll
+    for (int i = 0; i < R::NV; ++i) v[i] = fmaf(y[i], m, v[i]);
+    R::norm_r(v, wav, bav, eps_a, y);
+    R::norm_r(y, whv, bhv, eps_h, z);
+    float acc[3];
+#pragma unroll
+    for (int o = 0; o < 3; ++o) {
+      float a = 0.f;
+#pragma unroll
+      for (int i = 0; i < R::NV; ++i) a = fmaf(z[i], wv[o][i], a);
+      acc[o] = wave_sum(a) + (o == 0 ? b0 : o == 1 ? b1 : b2);
+    }
+    const int fj = tok % SP;
+    if (lane < 3 && fj < FJ) out[((size_t)(tok / SP) * FJ + fj) * 3 + lane] = lane == 0 ? acc[0] : (lane == 1 ? acc[1] : acc[2]);
+  }
+}
+
 // one workgroup per batch element; sin/cos table `freq` is supplied by the host (computed with the
 // reference's own fp32 expression, mixste.py:135-136) so no device exp() enters the argument.
 __global__ __launch_bounds__(256) void time_mlp_kernel(const int64_t* __restrict__ t, const float* __restrict__ freq,
@@ -935,5 +1033,35 @@ int d3dp_launch_head(int act_bf16, const float* x, const void* yadd0, const void
     if (act_bf16 == 1) hipLaunchKernelGGL((head_kernel<CC, bf16>), gk, blk, 0, st, x, (const bf16*)yadd0, (const bf16*)yadd, wa, ba, eps_a, wh, bh, eps_h, w, b, out, T, FJ, SP);
     else if (act_bf16 == 4) hipLaunchKernelGGL((head_kernel<CC, f16>), gk, blk, 0, st, x, (const f16*)yadd0, (const f16*)yadd, wa, ba, eps_a, wh, bh, eps_h, w, b, out, T, FJ, SP);
     else hipLaunchKernelGGL((head_kernel<CC, float>), gk, blk, 0, st, x, (const float*)yadd0, (const float*)yadd, wa, ba, eps_a, wh, bh, eps_h, w, b, out, T, FJ, SP))
+  return 0;
+}
+
+// ---- the scaled fp16 forms (ln_scaled_kernel ...): yadd rows of IEEE fp16 at the instantiated widths, each with the power-of-two
+// multiplier that takes it back to its value; -2 for any other width
+int d3dp_launch_ln_scaled(const float* x, const void* yadd, float m, const float* w, const float* b, float eps, void* xn, int T, int C,
+                          hipStream_t st) {
+  if (!yadd) return -1;
+  dim3 g((T + 3) / 4), blk(256);
+  DISPATCH_C(C, hipLaunchKernelGGL((ln_scaled_kernel<CC>), g, blk, 0, st, x, (const f16*)yadd, m, w, b, eps, (f16*)xn, T))
+  return 0;
+}
+
+int d3dp_launch_ln2_scaled(float* x, const void* yadd0, float m0, const void* yadd, float m, const float* wa, const float* ba,
+                           const float* pos, const float* wb, const float* bb, float eps, void* xn, int T, int C, int F, int J,
+                           hipStream_t st, int SP) {
+  if (!yadd0 || !yadd) return -1;
+  if (SP <= 0) SP = F * J;
+  dim3 g((T + 3) / 4), blk(256);
+  DISPATCH_C(C, hipLaunchKernelGGL((ln2_scaled_kernel<CC>), g, blk, 0, st, x, (const f16*)yadd0, m0, (const f16*)yadd, m, wa, ba, pos, wb, bb, eps, (f16*)xn, T, F, J, SP))
+  return 0;
+}
+
+int d3dp_launch_head_scaled(const float* x, const void* yadd0, float m0, const void* yadd, float m, const float* wa, const float* ba,
+                            float eps_a, const float* wh, const float* bh, float eps_h, const float* w, const float* b, float* out, int T,
+                            int C, hipStream_t st, int FJ, int SP) {
+  if (!yadd0 || !yadd) return -1;
+  if (FJ <= 0 || SP <= 0) { FJ = SP = 1 << 30; }
+  const dim3 gk((T + 4 * kRowTokens - 1) / (4 * kRowTokens)), blk(256);
+  DISPATCH_C(C, hipLaunchKernelGGL((head_scaled_kernel<CC>), gk, blk, 0, st, x, (const f16*)yadd0, m0, (const f16*)yadd, m, wa, ba, eps_a, wh, bh, eps_h, w, b, out, T, FJ, SP))
   return 0;
 }

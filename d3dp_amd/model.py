@@ -324,7 +324,11 @@ class MixSTE2(nn.Module):
         """FAST / FAST16 numerics: ``(type, bound)`` -- the 2-byte operand type the context's kernels run on ('bf16' or 'fp16')
         and the largest magnitude the current weights PROVE, for any input, for a value the context stores in 2 bytes (0.0 for
         'fast', which proves nothing; inf for non-finite weights).  A 'fast16' model runs 'fp16' while the bound is below
-        ``FP16_MAX`` and falls back to 'bf16' -- bit for bit what 'fast' computes -- otherwise.  None in the other modes.
+        ``FP16_MAX`` and falls back to 'bf16' -- bit for bit what 'fast' computes -- otherwise.  With ``D3DP_FAST16_RANGE=scale`` in
+        the environment when the context is created, 'fp16' beside a bound of ``FP16_MAX`` or more means SCALED: the blocks whose
+        q/k/v, proj, hidden or fc2 bound is out of range store those tensors at a power of two down to 2^-8 of their value; the
+        fallback to 'bf16' (and the model's warning) is left for non-finite weights, a LayerNorm output bound or a weight of
+        ``FP16_MAX`` or more, and bounds of ``FP16_MAX`` x 2^8 or more.  None in the other modes.
         include/d3dp_hip.h: d3dp_fast_operands."""
         t, b = C.c_int32(), C.c_float()
         _lib.check(_lib.load().d3dp_fast_operands(self._state().ctx, C.byref(t), C.byref(b)), "d3dp_fast_operands")

@@ -186,6 +186,18 @@ D3DP_API const char* d3dp_last_error(void);
  *                         other width, head dim or hidden, or D3DP_LONG_ATTN=rows beside it at these widths (the row kernel would take the
  *                         padded head dim for its exponent): D3DP_ENOTSUP, decided before the device is looked for.  EXACT and
  *                         TRAIN contexts do not read the variable.
+ *   channels in {64, 128, 256, 512} with head dim in {16, 32, 64} and hidden in {64, 128, 256, 512, 1024}, D3DP_MODE_FAST16, with
+ *                         D3DP_FAST16_RANGE=scale in the environment of d3dp_create (OPT-IN: without the switch such a context is
+ *                         the FAST16 context of the instantiated widths above, bit for bit as before): where the weights prove a
+ *                         bound of 65504 or more for a block's q / k / v, proj output, MLP hidden or fc2 output, that block stores
+ *                         that class of fp16 tensors at a power of two 2^-s, s <= 8, of its value instead of moving the whole
+ *                         context to bf16 (d3dp_fast_operands below).  Same workspace, same arena, same launches per call; a
+ *                         context whose weights need no scale launches exactly the kernels it launches without the switch.
+ *                         Any other value of the variable in a FAST16 context, head dim 8 (`-cs 64` with 8 heads), any other
+ *                         hidden, D3DP_LONG_ATTN=rows beside it (the row attention kernel has no scaled form) or
+ *                         D3DP_FAST_IMPL=mfma beside it at channels 192 / 320 / 384 / 448 (nor have the padded-head kernels):
+ *                         D3DP_ENOTSUP naming the switch, decided before the device is looked for.  FAST, EXACT and TRAIN contexts
+ *                         do not read the variable.
  * What a D3DP_MODE_TRAIN context takes, by the attention its training step runs:
  *   channels in {128, 256, 512} with head dim in {16, 32, 64} (`-cs 128 / 256 / 512` with 8 heads): Linears on split-fp16 operands and
  *                         the attention of both axes on the split-fp16 matrix-core kernels (train_attn.hip), which pass keys /
@@ -271,7 +283,18 @@ D3DP_API int d3dp_status(d3dp_ctx* ctx, int32_t* nonfinite);
  * d3dp_fast_operands (after d3dp_set_weights): *type = 0 bf16, 1 fp16, -1 not a FAST / FAST16 context; *bound = the proven
  * maximum (inf for non-finite weights; 0 for a plain FAST context, which proves nothing).  The worst-case bound is loose by
  * construction: the seed-initialised 8-block model at C = 512 proves 4762 (13.8x below the limit); where trained checkpoints
- * sit against it has not been measured. */
+ * sit against it has not been measured.
+ * D3DP_FAST16_RANGE=scale (d3dp_create): the four bounds a weight edit can push out of range give each block four exponents --
+ * s_qkv from b_qkv (q, k, v and the attention output, which is at most b_v 2^-s), s_proj from b_proj, s_h from b_h (the hidden
+ * and the fp16 pre-activation parked in front of the GELU), s_fc2 from b_fc2 -- each the smallest s >= 0 with bound x 2^-s < 65504.
+ * The Linear that produces a class multiplies its fp32 accumulator and bias by the power of two before the fp16 rounding, the
+ * attention kernels take 2^(2 s_qkv) into the softmax exponent, proj and fc2 take their input's scale out as they apply their own,
+ * and the row kernels multiply the branch outputs back as they add them to the fp32 residual stream: every multiplication is
+ * exact, so the only change is where fp16's subnormal range begins.  LayerNorm outputs and the weight matrices are never scaled.
+ * The context runs fp16 when every weight is finite, every L1, L2 and max |w| is below 65504 and every s is at most 8 (a CPU
+ * emulation of all four classes at 2^-s in every block stays within 1.2x of the unscaled one's distance to the fp32 oracle up to
+ * s = 12; profiles/fast16_scaled.md) -- otherwise the bf16 kernels, as without the switch.  *bound keeps its meaning, the proven
+ * maximum of the VALUES: *type = 1 beside *bound >= 65504 means scaled. */
 D3DP_API int d3dp_fast_operands(const d3dp_ctx* ctx, int32_t* type, float* bound);
 
 /* Scratch needed by d3dp_denoise for a (B, H) call. */

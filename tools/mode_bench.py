@@ -12,7 +12,13 @@ FAST mode (`fast:mfma`, `fast16:mfma`) creates that model's context with D3DP_FA
 creates that model's library context with D3DP_LONG_ATTN=rows in the environment: the row attention kernel wherever the mode would
 take a chunked-key or, in the FAST modes, a whole-sequence matrix-core kernel beyond 256 frames / 32 joints, and at head dims 32
 and 16 (`--cs 256`, `--cs 128`) for every attention of a FAST mode -- the A/B of those kernels in one process:
-`--cs 256 --numerics fast:rows,fast,fast16:rows,fast16`.  The variable is read when a context is created, so every context is created before anything is timed.
+`--cs 256 --numerics fast:rows,fast,fast16:rows,fast16`.  A `:scale` suffix on `fast16` creates that model's context with
+D3DP_FAST16_RANGE=scale: blocks whose proven bound reaches 65504 store the tensors it covers at a power of two of their value instead
+of moving the context to bf16.  It shows on weights that trip the proof, which `--edit NAME` makes of the seed weights, for every
+model alike -- a tensor of one block multiplied by a factor (EDITS below; `norm1x32`: gain and bias of TTEblocks.1.norm1 x 32) --
+`--edit norm1x32 --numerics fast,fast16:scale --batch 4 --hyps 5 --ksteps 5` is the A/B at BASELINE configs[1] size: without the
+switch `fast16` runs `fast`'s kernels on such weights, so `fast` is the yardstick.  The variables are read when a context is
+created, so every context is created before anything is timed.
 
 Every mode gets its own model (and library context) on the same weights, inputs and generator seed.  After `--warmup` steps of each,
 the timed steps are taken in `--rounds` rounds that visit the modes in turn (a b a b ...), steps / rounds steps per visit, a host
@@ -21,7 +27,7 @@ back-to-back bench.py runs cannot offer.  Clock and power are sampled the way be
 over that mode's timed visits only.  Prints ONE JSON line: per mode hypothesis-clips/s, ms per step, the per-visit spread, mean
 clock / power; the ratio of every mode to the first; the operand type and proven bound of the FAST modes; the library's sha256;
 and, from one more untimed step per mode under d3dp_profile_read, launches and kernel ms of the two attention classes (EXACT
-modes: of every class, with the implementation the context reports).
+modes: of every class, with the implementation the context reports; `--classes`: of every class for every mode).
 """
 import argparse
 import json
@@ -31,6 +37,14 @@ import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+
+
+# --edit: (parameter names under pose_estimator., factor) -- the weight edits of tests/test_hip_fast16_scaled.py
+EDITS = {"norm1x32": (("TTEblocks.1.norm1.weight", "TTEblocks.1.norm1.bias"), 32.0),
+         "norm1x256": (("TTEblocks.1.norm1.weight", "TTEblocks.1.norm1.bias"), 256.0),
+         "fc1x256": (("STEblocks.0.mlp.fc1.weight",), 256.0),
+         "fc2x16": (("TTEblocks.0.mlp.fc2.weight",), 16.0),
+         "projx32": (("STEblocks.1.attn.proj.weight",), 32.0)}
 
 
 def main():
@@ -44,6 +58,8 @@ def main():
     ap.add_argument("--ksteps", type=int, default=10)
     ap.add_argument("--frames", type=int, default=None, help="clip length (default: bench.py's, 243)")
     ap.add_argument("--cs", type=int, default=None, help="channels, 8 heads (default: bench.py's, 512)")
+    ap.add_argument("--classes", action="store_true", help="report launches and kernel ms of EVERY profile class for every mode")
+    ap.add_argument("--edit", choices=sorted(EDITS), default=None, help="multiply one block's tensor(s) in every model (see the docstring)")
     a = ap.parse_args()
     modes = [m.strip() for m in a.numerics.split(",") if m.strip()]
     if not modes or a.steps < a.rounds or a.rounds < 1 or a.warmup < 0:
@@ -54,13 +70,21 @@ def main():
     B, H, K = a.batch, a.hyps, a.ksteps
     frames = bench.F_ if a.frames is None else a.frames
     # the switch a suffix sets in the environment while that mode's context is created
-    suffixes = {"rows": ("D3DP_LONG_ATTN", "rows"), "f16x2": ("D3DP_EXACT_IMPL", "f16x2"), "mfma": ("D3DP_FAST_IMPL", "mfma")}
+    suffixes = {"rows": ("D3DP_LONG_ATTN", "rows"), "f16x2": ("D3DP_EXACT_IMPL", "f16x2"), "mfma": ("D3DP_FAST_IMPL", "mfma"),
+                "scale": ("D3DP_FAST16_RANGE", "scale")}
     if not 1 <= frames <= 1024 or any(m.count(":") > 1 or (":" in m and m.split(":")[1] not in suffixes) for m in modes):
-        ap.error("--frames must be in [1, 1024]; the mode suffixes are ':rows', ':f16x2' and ':mfma'")
+        ap.error("--frames must be in [1, 1024]; the mode suffixes are ':rows', ':f16x2', ':mfma' and ':scale'")
     x2d_np = synthetic_inputs_2d(1234, B, frames)
     x2d, x2f = torch.from_numpy(x2d_np).cuda(), torch.from_numpy(flip_2d(x2d_np)).cuda()
     cs = bench.C_ if a.cs is None else a.cs
     models = {m: bench.build_model(H, K, m.split(":")[0], 0, frames=frames, cs=cs) for m in modes}
+    if a.edit:
+        names, factor = EDITS[a.edit]
+        with torch.no_grad():
+            for model in models.values():
+                params = dict(model.pose_estimator.named_parameters())
+                for n in names:
+                    params[n].mul_(factor)
     for m in modes:                                    # the contexts, now: a suffixed one with its switch set for its creation
         key, val = suffixes[m.split(":")[1]] if ":" in m else (None, None)
         saved = os.environ.get(key) if key else None
@@ -93,7 +117,7 @@ def main():
             teles[m].stop()
             assert bool(torch.isfinite(out).all())
     res = {"workload": f"{'BASELINE configs[2]: ' if (frames, cs) == (bench.F_, bench.C_) else ''}ddim_sample_flip F={frames} J=17 B={B} H={H} K={K} flip-TTA, cs={cs} dep=8",
-           "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "order": modes, "library_sha256": bench.lib_sha256(), "modes": {}}
+           "weight_edit": a.edit, "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "order": modes, "library_sha256": bench.lib_sha256(), "modes": {}}
     for m in modes:
         dt = sum(v * n for v, n in zip(visits[m], per_visit))
         tr = teles[m].report()
@@ -107,6 +131,7 @@ def main():
                                                           if k.startswith("attn")}}
         if m.split(":")[0] == "exact":
             res["modes"][m]["exact_implementation"] = models[m].pose_estimator.exact_scales()[2]
+        if m.split(":")[0] == "exact" or a.classes:
             res["modes"][m]["classes_one_step"] = {k: {"launches": c, "kernel_ms": round(ms, 3)} for k, (c, ms) in prof.items() if c}
     base = res["modes"][modes[0]]["value"]
     res["ratio_to_first"] = {m: res["modes"][m]["value"] / base for m in modes}
