@@ -35,7 +35,18 @@ int d3dp_debug_train_linear(const float* A, const float* W, const float* bias, f
 int d3dp_op_linear(int32_t mode, int32_t epi, const void* A, const void* W, const float* bias, void* out, int32_t M,
                    int32_t N, int32_t K, void* stream) {
   if (!A || !W || !bias || !out) return d3dp_fail(D3DP_EINVAL, "d3dp_op_linear: null argument");
-  if (mode == D3DP_MODE_FAST || mode == 4) {
+  if (mode == 4 && (epi & 32)) {
+    // epi | 32 | (r_in << 8) | (r_out << 12) on fp16 operands: the scaled form of the streaming kernel (gemm_stream_scaled.hip) as a
+    // FAST16 context under D3DP_FAST16_RANGE=scale launches it (capi_denoise.hip linear_f16) -- A holds 2^-r_in times its value, the fp16
+    // rows leave at 2^-r_out; r_in, r_out in 0 .. 8 (the cap of the contexts).  EPI_GELU takes r_in = 0 (its A is a LayerNorm output).
+    const int e = epi & 3, r_in = (epi >> 8) & 15, r_out = (epi >> 12) & 15;
+    if ((e != EPI_BIAS && e != EPI_GELU) || (epi & ~(3 | 32 | 0xff00)) || r_in > 8 || r_out > 8 || (e == EPI_GELU && r_in))
+      return d3dp_fail(D3DP_EINVAL, "d3dp_op_linear: the scaled form takes epi 0 or 1 | 32 | (r_in << 8) | (r_out << 12) with r_in, r_out "
+                                    "<= 8 and r_in = 0 under epi 1; got %d", epi);
+    LAUNCH_TRY(d3dp_linear_stream_scaled(e, A, W, bias, out, M, N, K, (hipStream_t)stream, ldexpf(1.f, r_in - r_out), ldexpf(1.f, -r_out),
+                                         ldexpf(1.f, r_out)));
+  }
+  else if (mode == D3DP_MODE_FAST || mode == 4) {
     // epi 0/1: the persistent streaming kernel the denoiser uses (epi | 16 selects its fp32-output form); mode 4: on fp16 operands
     const int e = epi & 3, f32 = (epi & 16) != 0;
     if (e == EPI_RESID || (epi & ~19)) return d3dp_fail(D3DP_EINVAL, "d3dp_op_linear: FAST mode has epilogues 0, 1 and 0|16");
@@ -95,6 +106,20 @@ int d3dp_op_attention(int32_t act_bf16, int32_t impl, int32_t axis, const void* 
   hipStream_t st = (hipStream_t)stream;
   if (act_bf16 != 0 && act_bf16 != 1 && act_bf16 != 4) return d3dp_fail(D3DP_EINVAL, "act_bf16 must be 0, 1 or 4 (fp16)");
   const int f16 = act_bf16 == 4;
+  // impl = 1 | (s << 16), s = 1 .. 8, on fp16 rows: the scaled forms of the FAST16 attention kernels (attention_fast_scaled.hip) as a
+  // context under D3DP_FAST16_RANGE=scale launches them -- q, k and v hold 2^-s times their value, `out` leaves at v's scale.  (Any
+  // other value with bits above 7 set goes on to the check of the padded forms, as before.)
+  if (f16 && (impl & 0xffff) == 1 && (impl >> 16) >= 1 && (impl >> 16) <= 8) {
+    const int s = impl >> 16;
+    if (heads < 1 || C % heads || !mfma_head_dim(C / heads))
+      return d3dp_fail(D3DP_ENOTSUP, "impl 1 | (s << 16) takes fp16 rows of head dims 64, 32 and 16; C=%d heads=%d is head dim %d", C, heads,
+                       heads > 0 ? C / heads : 0);
+    if (axis == 0 && J > 256) return d3dp_fail(D3DP_ENOTSUP, "MFMA spatial attention takes up to 256 joints; J=%d", J);
+    if (axis == 0) LAUNCH_TRY(d3dp_attn_fast_scaled(J <= 32 ? 0 : 1, qkv, out, n_bh * F, spatial_map(F, J), C, heads, st, ldexpf(1.f, 2 * s)));
+    else LAUNCH_TRY(d3dp_attn_fast_scaled(1, qkv, out, n_bh * J, temporal_map(F, J), C, heads, st, ldexpf(1.f, 2 * s)));
+    HIP_TRY(hipGetLastError());
+    return D3DP_OK;
+  }
   // impl = 1 | (true head dim << 8) on 2-byte rows: the padded forms of the FAST attention kernels (attention_fast_pad.hip) -- C / heads is
   // the padded head dim 32 / 64, whose columns beyond the true head dim are zeros in `qkv` and come back as zeros in `out`
   const int hd_true = (impl & 255) == 1 ? impl >> 8 : 0;

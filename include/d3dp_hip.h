@@ -418,7 +418,12 @@ D3DP_API int d3dp_procrustes(const float* pred, const float* target, float* err,
  * mode EXACT: everything fp32 (fp32 MFMA; the EXACT denoiser itself runs d3dp_op_linear_x2 below).  mode FAST: A, W bf16 (uint16
  * storage), fp32 accumulate, epi 0 or 1 only, out bf16 unless (epi & 16) (fp32): the persistent streaming kernel the
  * denoiser uses.  mode 4: the same kernel on IEEE fp16 A, W and out (what a FAST16 context launches; NOT D3DP_MODE_FAST16's
- * number, which this entry point does not take: 2 and 3 are the split-operand selectors here). */
+ * number, which this entry point does not take: 2 and 3 are the split-operand selectors here).
+ * mode 4 with epi = e | 32 | (r_in << 8) | (r_out << 12), e = 0 or 1, r_in and r_out in 0 .. 8: the SCALED form of that kernel, as a
+ * FAST16 context under D3DP_FAST16_RANGE=scale launches it -- A holds 2^-r_in times its value, the fp16 rows leave at 2^-r_out:
+ * out = fp16((acc 2^(r_in - r_out)) + bias 2^-r_out); e = 1 (r_in = 0 only): that value parked as fp16, then
+ * fp16(gelu(. 2^r_out) 2^-r_out).  K / 64 in {1, 2, 4, 8, 16}.  In mode FAST, and in mode 4 without the 32, any bit of epi other than 0, 1 and 4 is
+ * D3DP_EINVAL as before. */
 D3DP_API int d3dp_op_linear(int32_t mode, int32_t epi, const void* A, const void* W, const float* bias, void* out, int32_t M,
                    int32_t N, int32_t K, void* stream);
 /* Multi-head attention over qkv[T,3C] -> out[T,C]; axis 0 = spatial (sequences of J joints), 1 = temporal
@@ -434,6 +439,10 @@ D3DP_API int d3dp_op_linear(int32_t mode, int32_t epi, const void* A, const void
  * C = heads x hdp is the PADDED width, hdp = 32 with true head dim d = 24 or hdp = 64 with d in {40, 48, 56}; the columns d .. hdp - 1
  * of every head are zeros in qkv and come back as exact zeros in out; the softmax scale is d^-0.5.  Any other (hdp, d):
  * D3DP_ENOTSUP.  Plain impl 1 takes C / heads itself as the head dim, as before.
+ * impl = 1 | (s << 16), s = 1 .. 8, on fp16 rows (act_bf16 4) of head dim 64, 32 or 16: the SCALED forms of the FAST16 kernels
+ * (D3DP_FAST16_RANGE=scale at d3dp_create) -- q, k and v in qkv hold 2^-s times their value, the softmax exponent is scaled by
+ * (C / heads)^-0.5 2^(2s), and out holds 2^-s times the attention output.  Bits 8 .. 15 must be 0 (no padded scaled form exists); s
+ * outside 1 .. 8, or another activation type, is D3DP_ENOTSUP through the check of the padded forms, as before.
  * act_bf16: 0 fp32 rows, 1 bf16 rows, 4 IEEE fp16 rows (impl 0 and 1: the kernels of a FAST16 context).
  * d3dp_op_layernorm out_bf16: the activation code of the row kernels -- 0 fp32, 1 bf16, 2 three split-bf16 planes, 3 two
  * split-fp16 planes (h2i), 4 IEEE fp16.  Codes 1 and 4 take the instantiated widths and any C % 32 == 0, C <= 512 (the run-time-width
