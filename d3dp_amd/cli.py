@@ -15,6 +15,7 @@ Run under `python -m torch.distributed.run --nproc-per-node N main.py ...` to sh
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import sys
 
@@ -61,6 +62,9 @@ def parse_args(argv=None):
     p.add_argument('--synthetic-sequences', type=int, default=2)
     p.add_argument('--synthetic-frames', type=int, default=600)
     p.add_argument('--numerics', default=None, choices=['exact', 'fast', 'fast16'])
+    p.add_argument('--train-passes', type=int, default=None, choices=[1, 3],
+                   help='fp16-MFMA passes per product of the training Linears: 1 = D3DP_TRAIN_PASSES=1 (fp16 operands at their own '
+                        'scale, fp32 accumulation), 3 = the split-fp16 default; set around the creation of the training model only')
     p.add_argument('--seed', type=int, default=1)
     a = p.parse_args(argv)
     a.test_time_augmentation = True          # arguments.py:112 (no flag turns it off in the reference)
@@ -178,6 +182,24 @@ def run_evaluate(args, rank, world, device):
     return 0
 
 
+@contextlib.contextmanager
+def train_passes_env(passes):
+    """D3DP_TRAIN_PASSES=<passes> inside the block (None: the environment as it is), restored on exit.  The library reads the
+    switch when a TRAIN context is created -- the training model's first step -- and for no context of another mode."""
+    if passes is None:
+        yield
+        return
+    saved = os.environ.get("D3DP_TRAIN_PASSES")
+    os.environ["D3DP_TRAIN_PASSES"] = str(passes)
+    try:
+        yield
+    finally:
+        if saved is None:
+            os.environ.pop("D3DP_TRAIN_PASSES", None)
+        else:
+            os.environ["D3DP_TRAIN_PASSES"] = saved
+
+
 def run_train(args, rank, world, device):
     """main.py:305-593 on synthetic sequences: ChunkedBatcher (pools in HBM) -> D3DP(is_train=True) -> HipAdamW."""
     from .data import ChunkedBatcher
@@ -192,6 +214,11 @@ def run_train(args, rank, world, device):
     model_eval = D3DP(args, kl, kr, is_train=False, numerics=args.numerics).to(device)
     if not args.resume:
         model_train.load_state_dict(make_state_dict(7, args.cs, args.dep, args.number_of_frames), strict=False)
+    # --train-passes: the TRAIN context is created HERE, inside the switch's block, instead of at the first step (the eval model's
+    # contexts, created later in the same process, never see the variable)
+    with train_passes_env(args.train_passes):
+        model_train.pose_estimator._context(device)
+        print('INFO: training arithmetic:', model_train.pose_estimator.train_arithmetic())
     n_params = sum(p.numel() for p in model_train.parameters())
     print('INFO: Trainable parameter count:', n_params / 1000000, 'Million')
     batcher = ChunkedBatcher(max(1, args.batch_size // args.stride), [c for c, _, _ in train], [g for _, g, _ in train],

@@ -42,6 +42,33 @@ const char* kClassNames[D3DP_PROFILE_CLASSES] = {"gemm_qkv", "gemm_proj", "gemm_
                                                  "train_attn_bwd_kv_temporal", "train_operand_pass", "train_ln_fwd", "train_ln_bwd",
                                                  "train_other", "event_pair_overhead"};
 
+// D3DP_TRAIN_PASSES (opt-in; read for TRAIN contexts alone, by d3dp_create BEFORE the device is looked for, like the width
+// switches there): =1 runs every product of the split-fp16 training Linears as one fp16-MFMA pass hi(A) x hi(W) (gemm_x2_train.hip,
+// PASSES = 1); =3 names the default.  It exists where X2Train's Linears run in their default launch forms: any other value, the
+// fp32 path (`train_split`: as read_switches below) and the superseded launch forms of the variants build (no one-pass form)
+// are refused -- never ignored.  D3DP_TRAIN_ATTN, D3DP_TRAIN_ATTN_BWD and D3DP_TRAIN_OVERLAP compose with it: they select attention
+// kernels and streams, not Linear products.  D3DP_OK and *passes, or the refusal.
+int read_train_passes(const d3dp_cfg& g, bool train_split, int* passes) {
+  *passes = 3;
+  const char* tp = g.mode == D3DP_MODE_TRAIN ? getenv("D3DP_TRAIN_PASSES") : nullptr;
+  if (!tp) return D3DP_OK;
+  if (strcmp(tp, "1") && strcmp(tp, "3"))
+    return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_PASSES=%.32s: the values a TRAIN context takes are D3DP_TRAIN_PASSES=1 (one fp16-MFMA pass per "
+                              "product of the split-fp16 training Linears) and 3 (the default)", tp);
+  if (tp[0] == '3') return D3DP_OK;
+  const char* ti = getenv("D3DP_TRAIN_IMPL");
+  const bool f32 = ti && !strcmp(ti, "f32");
+  if (f32 || !train_split || g.channels % 32 || g.hidden % 32)      // (TrainPath::use_x2)
+    return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_PASSES=1 exists for the split-fp16 training Linears; channels=%d%s trains on the fp32 path "
+                              "(fp32-MFMA Linears have no one-pass form)", g.channels, f32 ? " under D3DP_TRAIN_IMPL=f32" : "");
+  auto is = [](const char* name, const char* v) { const char* e = getenv(name); return e && !strcmp(e, v); };
+  if (is("D3DP_TRAIN_WGRAD", "each") || is("D3DP_TRAIN_TAIL", "split") || is("D3DP_TRAIN_GELU", "pass") || is("D3DP_TRAIN_LN_OPERAND", "pass"))
+    return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_PASSES=1 beside D3DP_TRAIN_WGRAD=each / D3DP_TRAIN_TAIL=split / D3DP_TRAIN_GELU=pass / "
+                              "D3DP_TRAIN_LN_OPERAND=pass: the superseded launch forms have no one-pass form");
+  *passes = 1;
+  return D3DP_OK;
+}
+
 // The environment switches of a context, read once at d3dp_create: the cross-check implementations, the training step's
 // scheduling switches and the measurement switches of the experiment kernels.  `width_inst`: the width is one the matrix-core
 // kernels are instantiated for, or one the split-fp16 implementation takes with padded heads under D3DP_EXACT_IMPL=f16x2
@@ -271,6 +298,8 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
                                 "backward, which holds a whole sequence in LDS (<= 256 tokens; <= 153 at head dims above 64)",
                   g.channels, g.heads, g.frames, g.joints);
   }
+  int train_passes = 3;
+  if (const int rc = read_train_passes(g, width_inst || hdp != 0 || train_widths, &train_passes); rc != D3DP_OK) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
     return d3dp_fail(D3DP_EHIP, "no HIP device visible: libd3dp_hip has no CPU fallback");
@@ -279,6 +308,7 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   c->fast_f16 = c->fast16() ? 1 : (c->fast() ? D3DP_FAST_F16 : 0);   // (FAST16: until d3dp_set_weights has seen the weights)
   c->hdp = hdp;
   c->fast16_scale = fast16_scale;
+  c->train_passes = train_passes;
   if (const int rc = read_switches(c, width_inst || hdp != 0, width_inst || hdp != 0 || train_widths); rc != D3DP_OK) {
     delete c;
     return rc;

@@ -142,6 +142,8 @@ int lin32(const float* A, const float* W, const float* bias, float* out, int M, 
 // assumed and nothing synchronises.  forward: out = A W^T + b;  dgrad: dX = dY W (W^T split as the "weight" operand);
 // wgrad: dW = dY^T X contracts over the batch's tokens into a handful of output tiles -> split-K over Z chunks of tokens,
 // partial products summed in a fixed order (deterministic; the fp32 path's split-K used atomics).
+// D3DP_TRAIN_PASSES=1 (`passes`): the same launches on the one-pass instantiations of the two product kernels -- hi(A) x hi(W)
+// alone, i.e. every operand rounded to fp16 at its own scale; operand passes, scales, k order, partial sums, streams: unchanged.
 struct X2Train {
   hipStream_t st;
   float* ws;
@@ -150,9 +152,10 @@ struct X2Train {
   d3dp_ctx* pc;                                        // per-kernel profile (d3dp_profile_enable): classes T_LINEAR / T_WGRAD / T_OPERAND
   hipStream_t st_w = nullptr;                          // the weight-gradient products' stream (null: `st`)
   bool tail_blocks;                                    // d3dp_ctx::train_tail_blocks
+  int passes;                                          // d3dp_ctx::train_passes: fp16-MFMA passes per product (3; 1 = D3DP_TRAIN_PASSES=1)
   // the set-up of both passes of a step over T tokens: the same launch forms in forward and backward
   X2Train(d3dp_ctx* c, const TrainLayout& L_, float* ws_, hipStream_t st_, int T)
-      : st(st_), ws(ws_), L(L_), n_cu(c->n_cu), pc(c->prof ? c : nullptr), tail_blocks(c->train_tail_blocks) {
+      : st(st_), ws(ws_), L(L_), n_cu(c->n_cu), pc(c->prof ? c : nullptr), tail_blocks(c->train_tail_blocks), passes(c->train_passes) {
     use_set(0);
     merged_setup(T, c->train_wgrad_merged);
   }
@@ -192,7 +195,7 @@ struct X2Train {
     if (!n_def) return 0;
     hipStream_t sw = st_w ? st_w : st;
     Scope ps(pc, T_WGRAD, sw);
-    int r = d3dp_launch_linear_f16x2_tn_many(def, n_def, mTp, mZ, sw);
+    int r = d3dp_launch_linear_f16x2_tn_many(def, n_def, mTp, mZ, sw, passes);
     if (r) return r;
     D3dpSumTable tb{};
     tb.n = n_def; tb.Z = mZ;
@@ -270,12 +273,12 @@ struct X2Train {
     //  full round, so for 16 k-steps it costs 12 us, what the second launch and the sum cost too: split from 32 k-steps on)
     // the remainder rows as 16 x 64 blocks at the end of the same launch (gemm_f16x2_dyn_kernel): wherever they would cost a round
     if (tail_blocks && rem && q && rounds_all > rounds_full && nk % 16 == 0)
-      return d3dp_launch_linear_f16x2_dyn(A2, W2, bias, ua, uw, out, T, N, K, 1, st, out_amax, amax_pos, 1);
+      return d3dp_launch_linear_f16x2_dyn(A2, W2, bias, ua, uw, out, T, N, K, 1, st, out_amax, amax_pos, 1, passes);
     if (rem == 0 || q == 0 || rounds_all == rounds_full || Z == 1 || nk < 32 || (size_t)Z * rem * N > (size_t)16 * 256 * std::max<size_t>(3 * L.C, L.Hd))
-      return d3dp_launch_linear_f16x2_dyn(A2, W2, bias, ua, uw, out, T, N, K, 1, st, out_amax, amax_pos);
-    int r = d3dp_launch_linear_f16x2_dyn(A2, W2, bias, ua, uw, out, q * 256, N, K, 1, st, out_amax, amax_pos);
+      return d3dp_launch_linear_f16x2_dyn(A2, W2, bias, ua, uw, out, T, N, K, 1, st, out_amax, amax_pos, 0, passes);
+    int r = d3dp_launch_linear_f16x2_dyn(A2, W2, bias, ua, uw, out, q * 256, N, K, 1, st, out_amax, amax_pos, 0, passes);
     if (r) return r;
-    r = d3dp_launch_linear_f16x2_dyn(A2 + (size_t)q * 256 * K, W2, nullptr, ua, uw, ws + L.part_rem, rem, N, K, Z, st);   // (a row = 2 K fp16 = K floats)
+    r = d3dp_launch_linear_f16x2_dyn(A2 + (size_t)q * 256 * K, W2, nullptr, ua, uw, ws + L.part_rem, rem, N, K, Z, st, nullptr, 0, 0, passes);   // (a row = 2 K fp16 = K floats)
     if (r) return r;
     d3dp_launch_sum_partials_bias(ws + L.part_rem, bias, out + (size_t)q * 256 * N, (size_t)rem * N, N, Z, st, out_amax, amax_pos);
     return 0;
@@ -401,11 +404,11 @@ struct X2Train {
     Scope ps(pc, T_WGRAD, sw);
     if (d3dp_tn_applies(N, K)) {                        // both operands in their row forms [Tp][2 .]: nothing was transposed
       if (!dy_ready) return -1;
-      r = d3dp_launch_linear_f16x2_tn(ws + o_a, ws + L.x_cols + xoff(l), uns() + sdy, uns() + sx, ws + o_part, N, K, Tp, Z, sw);
+      r = d3dp_launch_linear_f16x2_tn(ws + o_a, ws + L.x_cols + xoff(l), uns() + sdy, uns() + sx, ws + o_part, N, K, Tp, Z, sw, passes);
     } else {
       if (!dy_ready) return -1;                         // (the transposed form: left by prep_dy)
       r = d3dp_launch_linear_f16x2_dyn(ws + o_at, ws + L.x_cols + xoff(l), nullptr, uns() + sdy, uns() + sx, ws + o_part, N, K,
-                                       Tp, Z, sw);
+                                       Tp, Z, sw, nullptr, 0, 0, passes);
     }
     if (r) return r;
     d3dp_launch_sum_partials(ws + o_part, dW, (size_t)N * K, Z, sw);

@@ -188,6 +188,9 @@ struct d3dp_ctx {
   bool train_wgrad_merged = true;// D3DP_TRAIN_WGRAD=each: a launch (and 32 MB of partial tiles) per weight gradient instead of one per block
   bool train_tail_blocks = true; // D3DP_TRAIN_TAIL=split: the round-4 handling of a batch's last T mod 256 rows (an extra round of tiles,
                                  // or a split-K launch of their own) instead of the 16 x 64 blocks at the end of the product's kernel
+  int train_passes = 3;          // D3DP_TRAIN_PASSES=1 (opt-in; TRAIN contexts with train_x2 alone): every product of X2Train's Linears --
+                                 // forward, dgrad, both wgrad forms -- as ONE fp16-MFMA pass hi(A) x hi(W): the hi plane of a split operand
+                                 // is that tensor rounded to fp16 at its own power-of-two scale, so nothing else in the step changes
   int train_attn_x2 = 2;         // the training step's attention on the split-fp16 kernels of train_attn.hip: 2 = both axes (default),
                                  // 1 = D3DP_TRAIN_ATTN=x2t: the temporal axis only, 0 = D3DP_TRAIN_ATTN=f32: neither (the round-4
                                  // fp32 kernels -- fp32-MFMA temporal forward and backward, VALU spatial forward: the cross-check)

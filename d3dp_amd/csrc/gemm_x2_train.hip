@@ -27,12 +27,19 @@ namespace {
 //   * amax_out (optional; Z = 1 launches): the output's absmax (amax_pos: its largest positive value), one atomicMax per
 //     workgroup -- the operand scale of whatever split-fp16 kernel consumes the output next (the training attention kernels:
 //     q / k / v and dO; the fc2 operand GELU(fc1 output): gelu_rowprep_kernel), without an absmax pass.
+//   * PASSES (template parameter): 3 = the split scheme above; 1 = the one-pass route of
+//     D3DP_TRAIN_PASSES=1 -- the compute waves issue the hi x hi MFMA alone and never read the lo halves (offAl / offWl in LDS, the
+//     second 64 bytes of a line in the remainder blocks).  The hi plane of an operand IS that tensor rounded to fp16 at its own
+//     power-of-two scale, so the product is fp16 operands, fp32 accumulation, same k order, same scales and epilogue.  The loaders
+//     are the same: whole 128-byte h2i lines, of which this form uses the first 64 bytes.
+template <int PASSES>
 __global__ __launch_bounds__(768) void gemm_f16x2_dyn_kernel(const f16* __restrict__ A2, const f16* __restrict__ W2,
                                                              const float* __restrict__ bias, const float* __restrict__ dynA,
                                                              const float* __restrict__ dynW, float* __restrict__ out, int M,
                                                              int N, int Kfull, int NKz, int tiles_n, int tiles_per_z,
                                                              int total_items, unsigned* __restrict__ amax_out, int amax_pos,
                                                              int rem_m0) {
+  static_assert(PASSES == 1 || PASSES == 3, "one pass (hi x hi) or the three-pass split scheme");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int G = gridDim.x;
   const int L = xcd_remap(blockIdx.x, G);
@@ -134,19 +141,21 @@ __global__ __launch_bounds__(768) void gemm_f16x2_dyn_kernel(const f16* __restri
         for (int u = 0; u < 2; ++u) {
           const int o = (ks + u) * (2 * XBK);
           ah[u] = *reinterpret_cast<const f16x8*>(ap + o);
-          al[u] = *reinterpret_cast<const f16x8*>(ap + o + XBK);
+          if constexpr (PASSES == 3) al[u] = *reinterpret_cast<const f16x8*>(ap + o + XBK);
 #pragma unroll
           for (int ni = 0; ni < 4; ++ni) {
             wh[u][ni] = *reinterpret_cast<const f16x8*>(wp[ni] + o);
-            wl[u][ni] = *reinterpret_cast<const f16x8*>(wp[ni] + o + XBK);
+            if constexpr (PASSES == 3) wl[u][ni] = *reinterpret_cast<const f16x8*>(wp[ni] + o + XBK);
           }
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
+          if constexpr (PASSES == 3) {
 #pragma unroll
-          for (int ni = 0; ni < 4; ++ni) pacc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[u], wl[u][ni], pacc[ni], 0, 0, 0);
+            for (int ni = 0; ni < 4; ++ni) pacc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[u], wl[u][ni], pacc[ni], 0, 0, 0);
 #pragma unroll
-          for (int ni = 0; ni < 4; ++ni) pacc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[u], wh[u][ni], pacc[ni], 0, 0, 0);
+            for (int ni = 0; ni < 4; ++ni) pacc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[u], wh[u][ni], pacc[ni], 0, 0, 0);
+          }
 #pragma unroll
           for (int ni = 0; ni < 4; ++ni) pacc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[u], wh[u][ni], pacc[ni], 0, 0, 0);
         }
@@ -200,16 +209,18 @@ __global__ __launch_bounds__(768) void gemm_f16x2_dyn_kernel(const f16* __restri
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
+        for (int pl = 0; pl < (PASSES == 3 ? 2 : 1); ++pl)
           wf[ni][pl] = *reinterpret_cast<const f16x8*>(sb + (pl ? offWl : offW) + ni * 2048);
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
         const f16x8 ah = *reinterpret_cast<const f16x8*>(sb + offA + mi * 2048);
-        const f16x8 al = *reinterpret_cast<const f16x8*>(sb + offAl + mi * 2048);
+        if constexpr (PASSES == 3) {
+          const f16x8 al = *reinterpret_cast<const f16x8*>(sb + offAl + mi * 2048);
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wf[ni][1], acc[mi][ni], 0, 0, 0);
+          for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wf[ni][1], acc[mi][ni], 0, 0, 0);
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, wf[ni][0], acc[mi][ni], 0, 0, 0);
+          for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, wf[ni][0], acc[mi][ni], 0, 0, 0);
+        }
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wf[ni][0], acc[mi][ni], 0, 0, 0);
       }
@@ -283,7 +294,10 @@ __device__ __forceinline__ int tn_find(const D3dpTnTable& tb, int t) {
     if (j < tb.n && t >= tb.p[j].tile0) i = j;
   return i;
 }
+// PASSES: as gemm_f16x2_dyn_kernel -- 1 = hi x hi alone, the lo planes of the slabs (pl = 1) are never read from LDS.
+template <int PASSES>
 __global__ __launch_bounds__(768) void gemm_f16x2_tn_kernel(D3dpTnTable tb, int NKz, int tiles_per_z, int total_items) {
+  static_assert(PASSES == 1 || PASSES == 3, "one pass (hi x hi) or the three-pass split scheme");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int G = gridDim.x;
   const int L = xcd_remap(blockIdx.x, G);
@@ -381,15 +395,17 @@ __global__ __launch_bounds__(768) void gemm_f16x2_tn_kernel(D3dpTnTable tb, int 
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-        for (int pl = 0; pl < 2; ++pl) wf[ni][pl] = tr8(sb + offW[ni][pl], 16 * 512);
+        for (int pl = 0; pl < (PASSES == 3 ? 2 : 1); ++pl) wf[ni][pl] = tr8(sb + offW[ni][pl], 16 * 512);
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
         const f16x8 ah = tr8(sb + offA[mi][0], 16 * 1024);
-        const f16x8 al = tr8(sb + offA[mi][1], 16 * 1024);
+        if constexpr (PASSES == 3) {
+          const f16x8 al = tr8(sb + offA[mi][1], 16 * 1024);
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wf[ni][1], acc[mi][ni], 0, 0, 0);
+          for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wf[ni][1], acc[mi][ni], 0, 0, 0);
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, wf[ni][0], acc[mi][ni], 0, 0, 0);
+          for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, wf[ni][0], acc[mi][ni], 0, 0, 0);
+        }
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wf[ni][0], acc[mi][ni], 0, 0, 0);
       }
@@ -912,19 +928,20 @@ __global__ __launch_bounds__(256) void sum_partials_bias_kernel(const float* __r
 // out_z[M, N] = A2 (chunk z) . W2 (chunk z)^T x dynA x dynW (+ bias): Kfull = Z NKz 32 columns per operand row
 int d3dp_launch_linear_f16x2_dyn(const void* A2, const void* W2, const float* bias, const float* dynA, const float* dynW,
                                  float* out, int M, int N, int Kfull, int Z, hipStream_t st, unsigned* amax_out, int amax_pos,
-                                 int rem_blocks) {
-  if (M <= 0 || N % 4 != 0 || Z < 1 || Kfull % (XBK * Z) != 0 || (amax_out && Z != 1)) return -1;
+                                 int rem_blocks, int passes) {
+  if (M <= 0 || N % 4 != 0 || Z < 1 || Kfull % (XBK * Z) != 0 || (amax_out && Z != 1) || (passes != 1 && passes != 3)) return -1;
   const int NKz = Kfull / XBK / Z;
   // rem_blocks: the rows behind the last whole 256-row tile as 16 x 64 blocks at the end of the kernel (see there)
   const bool rem = rem_blocks && Z == 1 && M > XBM && M % XBM != 0 && NKz % (2 * XNCW) == 0;
   const int tm = rem ? M / XBM : (M + XBM - 1) / XBM, tn = (N + XBN - 1) / XBN;
-  static PerDeviceOnce once;
-  const int cus = once.get([&](int dev) {
-    return d3dp_lds_opt_in(reinterpret_cast<const void*>(gemm_f16x2_dyn_kernel), XNSTAGE * XSTAGE + 64) < 0 ? -3 : d3dp_cu_count(dev);
+  static PerDeviceOnce once, once1;                    // (one opt-in per kernel: the one-pass twin asks when it is first launched)
+  const auto kern = passes == 1 ? gemm_f16x2_dyn_kernel<1> : gemm_f16x2_dyn_kernel<3>;
+  const int cus = (passes == 1 ? once1 : once).get([&](int dev) {
+    return d3dp_lds_opt_in(reinterpret_cast<const void*>(kern), XNSTAGE * XSTAGE + 64) < 0 ? -3 : d3dp_cu_count(dev);
   });
   if (cus < 0) return -3;
   const int items = tm * tn * Z, grid = items < cus ? items : cus;
-  hipLaunchKernelGGL(gemm_f16x2_dyn_kernel, dim3(grid), dim3((XNCW + 4) * 64), XNSTAGE * XSTAGE + 64, st, (const f16*)A2,
+  hipLaunchKernelGGL(kern, dim3(grid), dim3((XNCW + 4) * 64), XNSTAGE * XSTAGE + 64, st, (const f16*)A2,
                      (const f16*)W2, bias, dynA, dynW, out, M, N, Kfull, NKz, tn, tm * tn, items, amax_out, amax_pos,
                      rem ? tm * XBM : 0);
   return 0;
@@ -995,8 +1012,8 @@ int d3dp_launch_gelu_rowprep(const float* src, void* drow, int R, int Rpad, int 
 // beyond the real ones zero), N % 256 == 0, K % 128 == 0 (d3dp_tn_applies)
 bool d3dp_tn_applies(int N, int K) { return N % XBM == 0 && K % XBN == 0; }
 // n products over the same Tp token rows in one launch: out_p,z[N_p, K_p] (z = 0 .. Z - 1, N_p K_p floats apart)
-int d3dp_launch_linear_f16x2_tn_many(const D3dpTnProduct* prods, int n, int Tp, int Z, hipStream_t st) {
-  if (n < 1 || n > D3DP_TN_MAX || Z < 1 || Tp % (XBK * Z) != 0) return -1;
+int d3dp_launch_linear_f16x2_tn_many(const D3dpTnProduct* prods, int n, int Tp, int Z, hipStream_t st, int passes) {
+  if (n < 1 || n > D3DP_TN_MAX || Z < 1 || Tp % (XBK * Z) != 0 || (passes != 1 && passes != 3)) return -1;
   D3dpTnTable tb{};
   tb.n = n;
   int tiles = 0;
@@ -1008,19 +1025,20 @@ int d3dp_launch_linear_f16x2_tn_many(const D3dpTnProduct* prods, int n, int Tp, 
     tiles += (tb.p[i].N / XBM) * tb.p[i].tiles_k;
   }
   const int NKz = Tp / XBK / Z;
-  static PerDeviceOnce once;
-  const int cus = once.get([&](int dev) {
-    return d3dp_lds_opt_in(reinterpret_cast<const void*>(gemm_f16x2_tn_kernel), XNSTAGE * XSTAGE) < 0 ? -3 : d3dp_cu_count(dev);
+  static PerDeviceOnce once, once1;
+  const auto kern = passes == 1 ? gemm_f16x2_tn_kernel<1> : gemm_f16x2_tn_kernel<3>;
+  const int cus = (passes == 1 ? once1 : once).get([&](int dev) {
+    return d3dp_lds_opt_in(reinterpret_cast<const void*>(kern), XNSTAGE * XSTAGE) < 0 ? -3 : d3dp_cu_count(dev);
   });
   if (cus < 0) return -3;
   const int items = tiles * Z, grid = items < cus ? items : cus;
-  hipLaunchKernelGGL(gemm_f16x2_tn_kernel, dim3(grid), dim3((XNCW + 4) * 64), XNSTAGE * XSTAGE, st, tb, NKz, tiles, items);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3((XNCW + 4) * 64), XNSTAGE * XSTAGE, st, tb, NKz, tiles, items);
   return 0;
 }
 int d3dp_launch_linear_f16x2_tn(const void* A2, const void* W2, const float* dynA, const float* dynW, float* out, int N, int K,
-                                int Tp, int Z, hipStream_t st) {
+                                int Tp, int Z, hipStream_t st, int passes) {
   const D3dpTnProduct one{A2, W2, dynA, dynW, out, N, K, 0, 0};
-  return d3dp_launch_linear_f16x2_tn_many(&one, 1, Tp, Z, st);
+  return d3dp_launch_linear_f16x2_tn_many(&one, 1, Tp, Z, st, passes);
 }
 
 int d3dp_launch_wprep(const D3dpWPrepTable& tb, void* rows_base, void* cols_base, unsigned* amax, float* unscale, hipStream_t st) {

@@ -106,9 +106,11 @@ void d3dp_launch_nonfinite_flag(const float* x, size_t n, unsigned* flag, hipStr
 // (amax_pos: the largest POSITIVE output value instead of the largest magnitude)
 // (rem_blocks: Z == 1, M > 256, Kfull % 512 == 0 -- the M mod 256 rows behind the last whole tile go to 16 x 64 blocks spread over
 //  all workgroups instead of a last row of mostly empty 256 x 128 tiles; ignored where the conditions do not hold)
+// (passes: 3 = the split scheme; 1 = the hi x hi pass alone -- D3DP_TRAIN_PASSES=1: fp16 operands at their own scale, fp32
+//  accumulation; the same operand rows, of which the lo halves are not read.  Also of the two TN launchers below.)
 int d3dp_launch_linear_f16x2_dyn(const void* A2, const void* W2, const float* bias, const float* dynA, const float* dynW,
                                  float* out, int M, int N, int Kfull, int Z, hipStream_t st, unsigned* amax_out = nullptr,
-                                 int amax_pos = 0, int rem_blocks = 0);
+                                 int amax_pos = 0, int rem_blocks = 0, int passes = 3);
 // drow [Rpad][2 C] = split(GELU(src [R][C])) (rows R .. Rpad - 1 zero) at the scale max(GELU(pmax), 0.17) asks for (pmax: the
 // largest positive value of src, left by the Linear that produced it); writes that bound to amax_out[0] and 1 / scale to unscale[0]
 int d3dp_launch_gelu_rowprep(const float* src, void* drow, int R, int Rpad, int C, const unsigned* pmax, unsigned* amax_out,
@@ -141,7 +143,7 @@ int d3dp_launch_rowprep_ln(const float* src, const float* w, const float* b, flo
 // Tp = Z NKz 32 rows per operand (rows beyond the real ones zero).  d3dp_tn_applies: N % 256 == 0 and K % 128 == 0.
 bool d3dp_tn_applies(int N, int K);
 int d3dp_launch_linear_f16x2_tn(const void* A2, const void* W2, const float* dynA, const float* dynW, float* out, int N, int K,
-                                int Tp, int Z, hipStream_t st);
+                                int Tp, int Z, hipStream_t st, int passes = 3);
 // ... several such products over the same Tp rows in one launch (the weight gradients of a block): one merged tile list, one Z
 constexpr int D3DP_TN_MAX = 4;
 struct D3dpTnProduct {
@@ -152,7 +154,7 @@ struct D3dpTnProduct {
   int tiles_k, tile0;                                  // (filled by the launcher)
 };
 struct D3dpTnTable { D3dpTnProduct p[D3DP_TN_MAX]; int n; };
-int d3dp_launch_linear_f16x2_tn_many(const D3dpTnProduct* prods, int n, int Tp, int Z, hipStream_t st);
+int d3dp_launch_linear_f16x2_tn_many(const D3dpTnProduct* prods, int n, int Tp, int Z, hipStream_t st, int passes = 3);
 struct D3dpSumTable { const float* part[D3DP_TN_MAX]; float* out[D3DP_TN_MAX]; size_t n4[D3DP_TN_MAX]; int Z; int n; };
 void d3dp_launch_sum_partials_many(const D3dpSumTable& tb, hipStream_t st);   // out_p[i] = sum_z part_p[z n_p + i], z ascending
 // the training step's weight operands in three launches: absmax -> slot, rows form [N][2 K] at rows_base + 2 off

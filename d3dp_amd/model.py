@@ -546,10 +546,15 @@ class MixSTE2(nn.Module):
                     "power-of-two scale for dS)")
         if os.environ.get("D3DP_TRAIN_ATTN_BWD", "")[:1] == "v":
             attn += "; D3DP_TRAIN_ATTN_BWD=valu: every fp32 attention backward on the VALU kernels instead"
+        # D3DP_TRAIN_PASSES=1 (capi.hip read_train_passes): every product of the split-fp16 Linears as one pass on the hi planes
+        one = os.environ.get("D3DP_TRAIN_PASSES") == "1"
+        lin = ("one-pass fp16 Linears of D3DP_TRAIN_PASSES=1 (one fp16-MFMA pass hi(A) x hi(W) per product -- forward, dgrad, "
+               "weight gradients: every operand rounded to fp16 at the power-of-two scale of its own absmax, fp32 accumulate, "
+               "device-side operand scales, no loss scaling" if one else
+               "split-fp16 Linears (three fp16-MFMA passes, fp32 accumulate, device-side operand scales")
         if widths:
             pad = f"; head dim {hd} padded to {32 if hd <= 32 else 64} inside the attention kernels' LDS images" if hd in (56, 48, 40, 24) else ""
-            return (f"split-fp16 route of D3DP_TRAIN_IMPL=f16x2 (cs = {self.embed_dim}): split-fp16 Linears (three fp16-MFMA passes, fp32 "
-                    "accumulate, device-side operand scales; an operand pass in front of every Linear, weight gradients as TN products "
+            return (f"split-fp16 route of D3DP_TRAIN_IMPL=f16x2 (cs = {self.embed_dim}): " + lin + "; an operand pass in front of every Linear, weight gradients as TN products "
                     "where N % 256 == 0 and K % 128 == 0 and on transposed operands elsewhere, partial tiles summed in a fixed order; "
                     "run-time-width row kernels that leave the operand absmax), " + attn + pad)
         if not inst:       # (include/d3dp_hip.h d3dp_create: a width outside the instantiated set trains on the fp32 path)
@@ -560,7 +565,7 @@ class MixSTE2(nn.Module):
             return "fp32 MFMA Linears (D3DP_TRAIN_IMPL=f32), fp32 attention"
         wg = ("a launch per weight gradient (D3DP_TRAIN_WGRAD=each)" if os.environ.get("D3DP_TRAIN_WGRAD") == "each"
               else "the four weight gradients of a block as one TN launch")
-        return ("split-fp16 Linears (three fp16-MFMA passes, fp32 accumulate, device-side operand scales; forward and dgrad on "
+        return (lin + "; forward and dgrad on "
                 "256 x 128 tiles with the batch's last T mod 256 rows as 16 x 64 blocks, " + wg + ", partial tiles summed in a "
                 "fixed order; LayerNorm and attention outputs written by their producers as the next Linear's operand rows), " + attn)
 

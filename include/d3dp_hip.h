@@ -225,6 +225,19 @@ D3DP_API const char* d3dp_last_error(void);
  *                         before the device is looked for.  Contexts of the other modes do not read D3DP_TRAIN_IMPL, and
  *                         D3DP_EXACT_IMPL=f16x2 keeps refusing a TRAIN context at these widths: a process that keeps a train
  *                         and an eval context sets each switch around the creation of its own context.
+ *   D3DP_TRAIN_PASSES=1 in the environment of d3dp_create (OPT-IN; read for D3DP_MODE_TRAIN contexts alone; unset or =3: the step
+ *                         above, bit for bit): a TRAIN context whose step runs the split-fp16 Linears -- the instantiated widths, and
+ *                         channels in {192, 320, 384, 448} under D3DP_TRAIN_IMPL=f16x2 -- runs every product of those Linears
+ *                         (forward, dgrad, both weight-gradient forms) as ONE fp16-MFMA pass hi(A) x hi(W): each operand rounded
+ *                         to IEEE fp16 at the power of two its own absmax asks for (so neither a range proof nor loss scaling is
+ *                         needed), fp32 accumulation, the same device-side scales, k order, partial sums, launches, streams and
+ *                         workspace.  Attention, LayerNorm, GELU, the residual stream, the embedding, time-MLP and head Linears
+ *                         and AdamW are untouched.  It is a mixed-precision route: gradients lie about 2^-11 from fp32's, not
+ *                         2^-21.  D3DP_ENOTSUP, decided before the device is looked for and naming the switch: any other value;
+ *                         =1 for a context on the fp32 path (D3DP_TRAIN_IMPL=f32, a width outside the sets above); =1 beside
+ *                         D3DP_TRAIN_WGRAD=each, D3DP_TRAIN_TAIL=split, D3DP_TRAIN_GELU=pass or D3DP_TRAIN_LN_OPERAND=pass (launch
+ *                         forms of the variants build, which have no one-pass form).  D3DP_TRAIN_ATTN, D3DP_TRAIN_ATTN_BWD and
+ *                         D3DP_TRAIN_OVERLAP compose with it.  Contexts of the other modes do not read it.
  * A D3DP_MODE_TRAIN context whose backward pass overlaps (split-fp16 Linears, D3DP_TRAIN_OVERLAP not 0) gets its second stream
  * and three events here, so that d3dp_train_backward never creates anything. */
 D3DP_API int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out);
@@ -365,6 +378,8 @@ D3DP_API int d3dp_jpma_ex(const float* pred, const float* traj, const float* cam
  * from and joined back to `stream` with events before it returns (the host is never synchronised; env D3DP_TRAIN_OVERLAP=0: one
  * stream) -- see Conventions: the caller orders against `stream` alone.
  * No gradient is accumulated with float atomics: the same inputs give the same bits.
+ * Arithmetic of the Linears: three fp16-MFMA passes on split operands (fp32-class), or one pass on their hi planes under
+ * D3DP_TRAIN_PASSES=1 (fp16 operands at their own scale, fp32 accumulation: d3dp_create) -- same launches, same workspace.
  * Clip length: any F <= 1024 like inference (reference common/arguments.py:58); beyond 256 frames the step needs its split-fp16
  * attention kernels (head dims 64, 32 and 16, and 24 / 40 / 48 / 56 under D3DP_TRAIN_IMPL=f16x2; keys / queries through LDS in
  * chunks) -- head dim 8, the fp32 path of the other widths and the fp32 cross-check implementations (D3DP_TRAIN_IMPL=f32,
@@ -508,7 +523,8 @@ D3DP_API const char* d3dp_profile_class_name(int32_t cls);
  *   (`make variants`: lib/variants/libd3dp_variants.so), 0 for the product library.
  * d3dp_debug_train_linear: the training step's split-fp16 Linear alone, out[M, N] = A[M, K] W[N, K]^T + bias on fp32 device
  *   operands -- absmax, operand split and gemm_f16x2_dyn_kernel exactly as d3dp_train_forward launches them.  tail: 0 = the rows
- *   behind the last whole 256-row tile as one more row of tiles, 1 = as 16 x 64 blocks inside the same launch; amax_out:
+ *   behind the last whole 256-row tile as one more row of tiles, 1 = as 16 x 64 blocks inside the same launch; tail | 16: the one-pass instantiation
+ *   of the kernel (what D3DP_TRAIN_PASSES=1 launches); any other bit: D3DP_EINVAL; amax_out:
  *   optional pre-zeroed device word receiving the output's absmax (amax_pos = 1: its largest positive value).  Allocates its
  *   operand buffers and synchronises `stream`. */
 D3DP_API int d3dp_debug_x2_variants(void);

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Compare the GPU code of two builds kernel by kernel: the proof that a source refactor left the device code alone.
 
-    python tools/kernel_isa_diff.py --old OLD.s [OLD2.s ...] --new NEW.s [NEW2.s ...]
+    python tools/kernel_isa_diff.py --old OLD.s [OLD2.s ...] --new NEW.s [NEW2.s ...] [--rename OLDSYM=NEWSYM ...]
 
 Each side is one or more outputs of `hipcc -S --cuda-device-only` (the Makefile's flags for that translation unit); a side's
 files are pooled, so one old file can be compared against the files it was split into.  Per kernel symbol two things are
 compared: the instruction lines from the symbol's label to the end of the function (comments dropped; the function index n
 of `.LBB<n>_<m>` / `.Lfunc_end<n>` labels, which only counts the functions in front of it in the file, normalised away) and
 the `.amdhsa_*` kernel descriptor (registers, LDS, scratch, every enable bit).  One line per kernel: identical, or the first
-line that differs.  Exit status 1 if any kernel differs or exists on one side only.  Profiles built this way: profiles/*_isa.md.
+line that differs.  --rename: a kernel whose symbol changed without its code (one that became a template instantiation) is compared under
+its old name.  Exit status 1 if any kernel differs or exists on one side only.  Profiles built this way: profiles/*_isa.md.
 """
 import argparse
 import re
@@ -57,8 +58,16 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--old", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
+    ap.add_argument("--rename", nargs="*", default=[], metavar="OLD=NEW",
+                    help="a kernel that became a template instantiation: compare old symbol OLD with new symbol NEW (every "
+                         "occurrence of either name inside the code is normalised to OLD)")
     args = ap.parse_args()
     old, new = kernels(args.old), kernels(args.new)
+    for pair in args.rename:
+        o, n = pair.split("=")
+        if n not in new:
+            sys.exit(f"--rename: {n} is not a kernel of the new side")
+        new[o] = tuple([l.replace(n, o) for l in part] for part in new.pop(n))
     bad = 0
     for name in sorted(set(old) | set(new)):
         if name not in old or name not in new:
