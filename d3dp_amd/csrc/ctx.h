@@ -1,6 +1,7 @@
 // Host-side types shared by the C-ABI translation units (capi.hip, capi_weights.hip, capi_denoise.hip, capi_ops.hip,
-// capi_train.hip): the context with its environment switches and derived predicates, a block's device weights, the profile
-// scope, the error function and the token maps of the two attention axes.  Internal: nothing here is exported.
+// capi_train.hip): the context -- the plan of its creation (ctx_plan.h), what d3dp_set_weights and the calls change later and the
+// predicates derived from both --, a block's device weights, the profile scope and the token maps of the two attention axes.
+// Internal: nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,12 +9,9 @@
 #include <cstdlib>
 #include <vector>
 
-#include "../../include/d3dp_hip.h"
 #include "common.h"
+#include "ctx_plan.h"
 #include "kernels.h"
-
-// The one error function: formats the message d3dp_last_error() returns for this thread and returns `code` (capi.hip)
-int d3dp_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 #define HIP_TRY(expr)                                                                      \
   do {                                                                                     \
@@ -63,13 +61,15 @@ inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
 // Which attention kernel family a context launches on an axis (0 = spatial, 1 = temporal): attn_route(), capi_denoise.hip
 enum class AttnRoute { X2, FAST_SPATIAL, FAST_WHOLE_SEQ, F32_TEMPORAL, ROWS };
-inline bool mfma_head_dim(int hd) { return hd == 64 || hd == 32 || hd == 16; }   // head dims the matrix-core attention kernels take
-// ... and the training step's (train_attn.hip): those, and 24 / 40 / 48 / 56 padded to 32 / 64 inside its kernels -- the head dims of
-// channels in {192, 320, 384, 448} with the model's 8 heads, reached under D3DP_TRAIN_IMPL=f16x2 only (d3dp_create)
+// The head dims the training step's attention kernels take (train_attn.hip): mfma_head_dim's, and 24 / 40 / 48 / 56 padded to 32 / 64
+// inside its kernels -- the head dims of channels in {192, 320, 384, 448} with the model's 8 heads, reached under
+// D3DP_TRAIN_IMPL=f16x2 only (plan_context)
 inline bool train_attn_head_dim(int hd) { return mfma_head_dim(hd) || hd == 24 || hd == 40 || hd == 48 || hd == 56; }
 AttnRoute attn_route(int mode, int exact_impl, int hd, int frames, int joints, bool long_rows, int axis);
 
-struct d3dp_ctx {
+// The members d3dp_create decides are the base (CtxPlan); the ones below it change later: d3dp_set_weights (exact_impl, impl_fallback,
+// fast_f16, fast_bound, the weights), the profile calls and the pass plan.
+struct d3dp_ctx : CtxPlan {
   d3dp_cfg cfg{};
   int device = 0;
   bool weights_set = false;
@@ -98,35 +98,18 @@ struct d3dp_ctx {
   bool fast() const { return cfg.mode == D3DP_MODE_FAST || fast16(); }
   int fast_f16 = 0;
   float fast_bound = 0.f;
-  // D3DP_FAST16_RANGE=scale (opt-in, read at d3dp_create for FAST16 contexts alone): a per-block bound that reaches 65504 lowers that
-  // block's power-of-two scale for the tensor class it bounds (BlockDev::r_*) instead of moving the whole context to bf16 -- what
-  // EXACT does with s_kv / s_h.  The context still falls back when a weight is non-finite, when a LayerNorm output bound or a
-  // max |w| reaches 65504 (neither is scaled), or when a class would need more than 2^-kFast16MaxShift.
-  bool fast16_scale = false;
   // EXACT mode runs its Linears on split-fp16 operands (2 planes, 3 fp16-MFMA passes, gemm_x2.hip); activations that
   // feed a Linear are then two fp16 planes.  env D3DP_EXACT_IMPL=bf16x3 selects the round-1 six-pass split-bf16 kernels
   // and =f32 the plain fp32-MFMA kernels (bitwise an fp32 fmaf chain) -- both kept as cross-checks.
-  int exact_impl = 0;   // 0 = f16x2, 1 = bf16x3, 2 = f32
-  int exact_impl_req = 0;        // what D3DP_EXACT_IMPL asked for; d3dp_set_weights moves an f16x2 context to bf16x3 when a
-  bool impl_fallback = false;    // LayerNorm's own output bound leaves the split-fp16 range (see there; with padded heads: to f32)
+  int exact_impl = 0;            // 0 = f16x2, 1 = bf16x3, 2 = f32.  Starts as exact_impl_req; d3dp_set_weights moves an f16x2 context to
+  bool impl_fallback = false;    // bf16x3 when LayerNorm's own output bound leaves the split-fp16 range (see there; with padded heads: to f32)
   bool train() const { return cfg.mode == D3DP_MODE_TRAIN; }
   bool exact() const { return !fast() && !train(); }
   bool x2() const { return exact() && exact_impl == 0; }
   // The split-fp16 attention kernels run (attn_route(): the same answer on both axes).  Everything that follows from the packed
   // qkv rows follows x2_attn(): EPI_QKV_PACK in linear(), the scale of the attention output planes in run_block, seq_pitch(), and
   // the range fallback of d3dp_set_weights, which lowers s_kv instead of leaving the split-fp16 implementation wherever these
-  // kernels run.  long_rows: D3DP_LONG_ATTN=rows, the row-kernel cross-check (read in d3dp_create).
-  bool long_rows = false;
-  // D3DP_EXACT_IMPL=f16x2 at channels in {192, 320, 384, 448} (d3dp_create): the split-fp16 implementation at a width outside the
-  // instantiated set.  The head dim is PADDED inside the packed weights to hdp = 32 or 64 (capi_weights.hip): the qkv Linear writes
-  // packed rows of cp() = heads x hdp columns whose pad columns are exact zeros, the attention kernels run their head dim 32 / 64
-  // instantiations on them (the softmax exponent takes the true head dim) and proj contracts over cp() columns against zero weight
-  // columns.  The residual stream, the LayerNorms and the MLP keep the true width.  0: no padding (every other context).
-  // D3DP_FAST_IMPL=mfma at the same widths (d3dp_create; FAST / FAST16 contexts): the same padding inside 2-byte weights -- the streaming
-  // Linear at the k-depths of these widths (gemm_stream_widths.hip), the FAST attention kernels' head dim 32 / 64 forms with the true head
-  // dim in the exponent (attention_fast_pad.hip) and run-time-width row kernels with 2-byte rows (pointwise_rows2.hip).  Such a context
-  // has no fallback implementation: FAST16's range fallback is the same route on bf16.
-  int hdp = 0;
+  // kernels run.  cp(): the columns of a qkv third, padded heads (CtxPlan::hdp) included.
   int cp() const { return hdp ? cfg.heads * hdp : cfg.channels; }
   // (the columns of a packed qkv third / of the attention output while the split-fp16 implementation runs; the range fallback of
   //  a padded context is the fp32 implementation, which knows no padding)
@@ -137,7 +120,6 @@ struct d3dp_ctx {
   bool x2_attn() const { return route(0) == AttnRoute::X2; }
   // proj / fc2 add into the residual stream in their epilogue (x += ...), so the row kernels read x alone
   bool fold_resid() const { return x2() && fold; }
-  bool fold = true;
   // norm2 (mixste.py:115) has no kernel of its own: proj's epilogue leaves x + proj(...) a second time as fc1's split-fp16
   // operand, UN-normalised, with (mean, M2) of each 64-column slice of each row; fc1 runs on W diag(gamma) and applies
   // rstd (. - mean c1) + c2 in its epilogue (gemm_x2.hip EPI_RESID_LN / EPI_GELU_LN).  OFF by default (D3DP_FOLD_LN=1 turns it
@@ -145,7 +127,6 @@ struct d3dp_ctx {
   // row kernel: the 284 ms/step of the LayerNorm kernel come back as +160 ms in proj (its tile epilogue now also splits, stores
   // the operand and reduces the statistics with the matrix pipes idle) and +90 ms in fc1 (profiles/r03_fold_ln_ab.md).
   bool fold_ln() const { return fold_resid() && fold_ln_on && 2 * cfg.hidden <= 2048; }
-  bool fold_ln_on = false;
   // The shared norm at a block boundary (Spatial_norm in front of the TTE blocks, Temporal_norm in front of the STE blocks d >= 1)
   // is DEFERRED into the next block's proj: the norm pair stores the next qkv operand and 8 bytes of (mean, rstd) per row but does
   // not rewrite x (2 KB per row at C = 512, a third of its traffic); proj, the first kernel to touch x again and one that reads
@@ -156,24 +137,16 @@ struct d3dp_ctx {
     // (ln2_defer_kernel is width-templated: a padded-head context keeps the in-place norm pair, as width 64 does)
     return fold_resid() && defer && !fold_ln() && skew_d == 0 && pingpong == 0 && cfg.channels >= 96 && 3 * cfg.channels <= 2048 && !hdp;
   }
-  bool defer = true;
   // The EXACT qkv / fc1 Linears run the SKEWED schedule of gemm_x2.hip (a tile's epilogue spread under the k-loop of the
   // next): the order in which a token row sums its k-steps then depends on (row within its pass) / 16 mod 4.  Every sequence
   // therefore starts at a multiple of 64 rows -- seq_pitch() rows per sequence, F J rounded up, the rest finite filler -- so
   // that order is a function of the token's index within its sequence alone and results stay bit-identical whatever the batch
   // composition, pass split or rank count (the H-sharding contract, tests/test_hip_parity.py::test_full_size_properties).
   bool skew() const { return x2_attn() && skew_d > 0 && cfg.channels >= 128 * skew_d; }   // (K = C >= 4 D k-steps of 32)
-  int skew_d = 0;                // D3DP_X2_SKEW=1|2|4: k-steps a parked row class takes to leave.  OFF by default: measured
-                                 // 3 % slower on the whole step (gemm_x2.hip, DESIGN.md 7: the Linear is bound by its vector-memory
-                                 // instruction rate, and an epilogue's stores cost the same wherever they issue)
   int seq_pitch() const {
     const int fj = cfg.frames * cfg.joints;
     return (pad_override < 0 ? skew() : (pad_override > 0 && x2_attn())) ? (fj + 63) / 64 * 64 : fj;
   }
-  int pad_override = -1;         // D3DP_SEQ_PAD=0|1: measurement switch (pad without the skewed schedule, or the reverse)
-  bool train_x2 = true;          // D3DP_TRAIN_IMPL=f32: the training Linears on the fp32 matrix cores (round-1 path, cross-check).  Also
-                                 // false at a width outside {64, 128, 256, 512} -- unless D3DP_TRAIN_IMPL=f16x2 opted a TRAIN context
-                                 // at channels in {192, 320, 384, 448} into the split-fp16 step (d3dp_create)
   // The backward pass runs the weight-gradient products (one merged TN launch per block, or one launch per Linear, and the sum of
   // their partial tiles) on a second stream beside the rest of the backward pass: a block's launch goes on while the next block's
   // dgrad products, attention and row kernels run (two operand / partial-tile sets, X2Train::use_set).  Forked and joined with events
@@ -181,22 +154,6 @@ struct d3dp_ctx {
   // since the weight gradients are one launch per block: kept because it costs nothing.
   hipStream_t aux = nullptr;
   hipEvent_t ev_fork = nullptr, ev_done[2] = {nullptr, nullptr};
-  bool train_overlap = true;
-  int train_overlap_sets = 2;    // D3DP_TRAIN_OVERLAP=1: one operand set (every operand pass waits for the product before it)
-  bool train_gelu_in_prep = true;// D3DP_TRAIN_GELU=pass: d h_pre by a pass of its own (gelu_bwd_kernel) instead of inside the fc1 gradients' operand pass
-  bool train_ln_direct = true;  // D3DP_TRAIN_LN_OPERAND=pass: the qkv / fc1 operands by an operand pass behind the LayerNorm (round 5) instead of by its producer
-  bool train_wgrad_merged = true;// D3DP_TRAIN_WGRAD=each: a launch (and 32 MB of partial tiles) per weight gradient instead of one per block
-  bool train_tail_blocks = true; // D3DP_TRAIN_TAIL=split: the round-4 handling of a batch's last T mod 256 rows (an extra round of tiles,
-                                 // or a split-K launch of their own) instead of the 16 x 64 blocks at the end of the product's kernel
-  int train_passes = 3;          // D3DP_TRAIN_PASSES=1 (opt-in; TRAIN contexts with train_x2 alone): every product of X2Train's Linears --
-                                 // forward, dgrad, both wgrad forms -- as ONE fp16-MFMA pass hi(A) x hi(W): the hi plane of a split operand
-                                 // is that tensor rounded to fp16 at its own power-of-two scale, so nothing else in the step changes
-  int train_attn_x2 = 2;         // the training step's attention on the split-fp16 kernels of train_attn.hip: 2 = both axes (default),
-                                 // 1 = D3DP_TRAIN_ATTN=x2t: the temporal axis only, 0 = D3DP_TRAIN_ATTN=f32: neither (the round-4
-                                 // fp32 kernels -- fp32-MFMA temporal forward and backward, VALU spatial forward: the cross-check)
-  int pingpong = 0;              // D3DP_X2_PP=1: the ping-pong form of the EXACT Linear (gemm_x2.hip; bit-identical results;
-                                 // measured 1.5-2 % SLOWER on the whole step, gpurun c8); 2 = D3DP_X2_WIDE=1: the 256 x 256
-                                 // tile form (bit-identical; ties with the default, profiles/r04_gemm_probes.md section 4)
   bool x3() const { return exact() && exact_impl == 1; }
   int act() const { return fast() ? (fast_f16 ? 4 : 1) : (x3() ? 2 : (x2() ? 3 : 0)); }   // code understood by the row-wise launchers
   size_t act_size() const { return fast() ? 2 : (x3() ? 6 : 4); }    // bytes per element of a Linear-input activation
@@ -292,7 +249,7 @@ inline SeqMap spatial_map(int F, int J, int sp = 0) { return sp > F * J ? SeqMap
 inline SeqMap temporal_map(int F, int J, int sp = 0) { return SeqMap{F, J, sp > F * J ? sp : F * J, 1, J}; }
 
 // Which path a TRAIN context's step takes, computed once per call from the switches read at d3dp_create.
-//   use_x2     the Linears on split-fp16 operands (X2Train, capi_train.hip); else the fp32 matrix cores.  d3dp_ctx::train_x2: the
+//   use_x2     the Linears on split-fp16 operands (train_linears_split); else the fp32 matrix cores.  CtxPlan::train_x2: the
 //              instantiated widths unless D3DP_TRAIN_IMPL=f32, and channels in {192, 320, 384, 448} under D3DP_TRAIN_IMPL=f16x2
 //   attn_x2(a) axis a's attention on the split-fp16 kernels of train_attn.hip: they need the split Linears' device-side scales
 //              and a head dim those kernels take (train_attn_head_dim: 64, 32, 16 -- `-cs` 512 / 256 / 128 with the model's 8 heads --
@@ -305,7 +262,7 @@ struct TrainPath {
   bool attn_x2(int axis) const { return axis == 1 ? attn_x2_t : attn_x2_s; }
   explicit TrainPath(const d3dp_ctx& c) {
     const d3dp_cfg& g = c.cfg;
-    use_x2 = c.train_x2 && g.channels % 32 == 0 && g.hidden % 32 == 0;
+    use_x2 = train_linears_split(c, g);
     attn_x2_t = use_x2 && c.train_attn_x2 > 0 && train_attn_head_dim(g.channels / g.heads) && g.frames <= 1024;
     attn_x2_s = attn_x2_t && c.train_attn_x2 > 1;      // the spatial axis too
     needs_aux = c.train() && use_x2 && c.train_overlap;

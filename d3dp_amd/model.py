@@ -546,7 +546,7 @@ class MixSTE2(nn.Module):
                     "power-of-two scale for dS)")
         if os.environ.get("D3DP_TRAIN_ATTN_BWD", "")[:1] == "v":
             attn += "; D3DP_TRAIN_ATTN_BWD=valu: every fp32 attention backward on the VALU kernels instead"
-        # D3DP_TRAIN_PASSES=1 (capi.hip read_train_passes): every product of the split-fp16 Linears as one pass on the hi planes
+        # D3DP_TRAIN_PASSES=1 (ctx_plan.h plan_context, step 7): every product of the split-fp16 Linears as one pass on the hi planes
         one = os.environ.get("D3DP_TRAIN_PASSES") == "1"
         lin = ("one-pass fp16 Linears of D3DP_TRAIN_PASSES=1 (one fp16-MFMA pass hi(A) x hi(W) per product -- forward, dgrad, "
                "weight gradients: every operand rounded to fp16 at the power-of-two scale of its own absmax, fp32 accumulate, "

@@ -492,8 +492,9 @@ D3DP_API int d3dp_op_split3(const float* src, void* dst, size_t n, void* stream)
  * (lib/variants/libd3dp_variants.so; tests marked `variants`): here those flags, and the environment switches D3DP_X2_SKEW,
  * D3DP_X2_PP, D3DP_X2_WIDE, D3DP_SEQ_PAD, D3DP_FOLD_LN read by d3dp_create, fail with D3DP_ENOTSUP -- they are never ignored.
  * Cross-check switches the product library does honour (read in d3dp_create): D3DP_EXACT_IMPL=bf16x3|f32, D3DP_NO_FOLD=1
- * (other implementations of EXACT mode's Linears / residual adds, same tolerance; D3DP_EXACT_IMPL=f16x2 is the opt-in route of
- * channels 192 / 320 / 384 / 448 described at d3dp_create), D3DP_DEFER_NORM=0 (the shared norm of every
+ * (other implementations of EXACT mode's Linears / residual adds, same tolerance; D3DP_EXACT_IMPL=bf16x3 exists for channels in
+ * {64, 128, 256, 512}: at any other width D3DP_ENOTSUP, decided before the device is looked for; D3DP_EXACT_IMPL=f16x2 is the opt-in
+ * route of channels 192 / 320 / 384 / 448 described at d3dp_create), D3DP_DEFER_NORM=0 (the shared norm of every
  * block boundary applied in place by the norm pair instead of inside the next proj Linear: bit-identical), D3DP_TRAIN_IMPL=f32. */
 D3DP_API int d3dp_op_split2(const float* src, void* dst, size_t n, float scale, void* stream);
 D3DP_API int d3dp_op_linear_x2(int32_t epi, const void* A2, const void* W2, const float* bias, float w_scale, void* out, int32_t M,

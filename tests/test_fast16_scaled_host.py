@@ -2,31 +2,13 @@
 operand scales where the proven bound reaches 65504, instead of moving the context to bf16) is decided before the device is looked
 for, so a machine without one sees every refusal -- the switch is never ignored -- and sees the shapes the switch takes get as far
 as the device check.  The form of test_fast_widths_host.py."""
-import ctypes as C
-
 import pytest
 
+from create_host import D3DP_ENOTSUP, create, reached_the_device_check
 from d3dp_amd import _lib
 
-D3DP_OK, D3DP_ENOTSUP, D3DP_EHIP = 0, -2, -3
 SWITCH = "D3DP_FAST16_RANGE=scale"
 OTHER_MODES = [_lib.MODE_FAST, _lib.MODE_EXACT, _lib.MODE_TRAIN]
-
-
-def create(cs, mode, frames=9, joints=5, heads=8, hidden=None):
-    """-> (return code, message); a context that was created is destroyed again."""
-    lib = _lib.load()
-    cfg = _lib.Cfg(frames, joints, cs, 1, heads, 2 * cs if hidden is None else hidden, 1e-6, 1e-5, mode, 0)
-    h = C.c_void_p()
-    rc = lib.d3dp_create(C.byref(cfg), C.byref(h))
-    msg = lib.d3dp_last_error().decode() if rc != D3DP_OK else ""
-    if rc == D3DP_OK:
-        lib.d3dp_destroy(h)
-    return rc, msg
-
-
-def reached_the_device_check(rc, msg):
-    return rc == D3DP_OK or (rc == D3DP_EHIP and "no HIP device" in msg)
 
 
 @pytest.mark.parametrize("cs", [128, 256, 512])

@@ -1,13 +1,11 @@
 """No GPU needed: what d3dp_create answers to D3DP_FAST_IMPL=mfma (the opt-in FAST / FAST16 route with padded heads at channels
 192 / 320 / 384 / 448) is decided before the device is looked for, so a machine without one sees every refusal -- the switch is
 never ignored -- and sees the shapes the switch takes get as far as the device check.  The form of test_exact_widths_host.py."""
-import ctypes as C
-
 import pytest
 
+from create_host import D3DP_ENOTSUP, create, reached_the_device_check
 from d3dp_amd import _lib
 
-D3DP_OK, D3DP_ENOTSUP, D3DP_EHIP = 0, -2, -3
 SWITCH = "D3DP_FAST_IMPL=mfma"
 FAST_MODES = [_lib.MODE_FAST, _lib.MODE_FAST16]
 # the two refusals of a library without the switch (capi.hip), verbatim for channels = 384, heads = 8, hidden = 768
@@ -18,22 +16,6 @@ TODAY = {
                       "{64,128,256,512} with head dim in {8,16,32,64} and hidden a multiple of 64; other widths run in D3DP_MODE_EXACT / "
                       "D3DP_MODE_TRAIN (fp32 implementation)",
 }
-
-
-def create(cs, mode, frames=9, joints=5, heads=8, hidden=None):
-    """-> (return code, message); a context that was created is destroyed again."""
-    lib = _lib.load()
-    cfg = _lib.Cfg(frames, joints, cs, 1, heads, 2 * cs if hidden is None else hidden, 1e-6, 1e-5, mode, 0)
-    h = C.c_void_p()
-    rc = lib.d3dp_create(C.byref(cfg), C.byref(h))
-    msg = lib.d3dp_last_error().decode() if rc != D3DP_OK else ""
-    if rc == D3DP_OK:
-        lib.d3dp_destroy(h)
-    return rc, msg
-
-
-def reached_the_device_check(rc, msg):
-    return rc == D3DP_OK or (rc == D3DP_EHIP and "no HIP device" in msg)
 
 
 @pytest.mark.parametrize("mode", FAST_MODES)

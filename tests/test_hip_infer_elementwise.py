@@ -33,7 +33,7 @@ from oracle import infer_check as ic
 from test_hip_train_grads import EDITS as TRAIN_EDITS
 
 pytestmark = pytest.mark.gpu
-# every environment switch d3dp_create reads for an EXACT context (csrc/capi.hip: read_switches)
+# every environment switch d3dp_create reads for an EXACT context (csrc/ctx_plan.h: CtxEnv)
 _SWITCHES = ("D3DP_EXACT_IMPL", "D3DP_LONG_ATTN", "D3DP_NO_FOLD", "D3DP_DEFER_NORM", "D3DP_X2_SKEW", "D3DP_X2_PP", "D3DP_X2_WIDE",
              "D3DP_SEQ_PAD", "D3DP_FOLD_LN")
 SD_SEED, X2D_SEED, X3D_SEED = 11, 911, 912

@@ -11,11 +11,12 @@ import torch
 import torch.nn.functional as F
 
 import train_passes_emu as emu
+from create_host import D3DP_ENOTSUP, create, reached_the_device_check
 from d3dp_amd import _lib, cli
 from oracle import grad_check as gc
 from oracle import lowp_check as lc
 from test_hip_train_grads import DROPPED_PARAMS, problem
-from test_train_widths_host import D3DP_ENOTSUP, arithmetic, create, reached_the_device_check
+from test_train_widths_host import arithmetic
 
 SWITCH = emu.SWITCH
 _ALL = ("D3DP_TRAIN_PASSES", "D3DP_TRAIN_IMPL", "D3DP_TRAIN_ATTN", "D3DP_TRAIN_ATTN_BWD", "D3DP_TRAIN_OVERLAP", "D3DP_TRAIN_WGRAD",

@@ -2,36 +2,19 @@
 384 / 448) is decided before the device is looked for, so a machine without one sees every refusal -- a switch is never ignored --
 and sees the shapes the switch takes get as far as the device check; what MixSTE2.train_arithmetic() says about the route; and
 that every case of tests/test_hip_train_widths.py is well-conditioned by the reference's own measure (oracle/grad_check.py)."""
-import ctypes as C
 from types import SimpleNamespace
 
 import pytest
 
+from create_host import D3DP_ENOTSUP, create, reached_the_device_check
 from d3dp_amd import D3DP, _lib
 from d3dp_amd.weights import H36M_JOINTS_LEFT, H36M_JOINTS_RIGHT
 from oracle import grad_check as gc
 from test_hip_train_grads import DROPPED_PARAMS, reference
 from test_hip_train_widths import ALL_CASES, DROPPED
 
-D3DP_OK, D3DP_ENOTSUP, D3DP_EHIP = 0, -2, -3
 SWITCH = "D3DP_TRAIN_IMPL=f16x2"
 LDS_REFUSAL = "holds a whole sequence in LDS"
-
-
-def create(cs, mode, frames=9, joints=5, heads=8):
-    """-> (return code, message); a context that was created is destroyed again."""
-    lib = _lib.load()
-    cfg = _lib.Cfg(frames, joints, cs, 1, heads, 2 * cs, 1e-6, 1e-5, mode, 0)
-    h = C.c_void_p()
-    rc = lib.d3dp_create(C.byref(cfg), C.byref(h))
-    msg = lib.d3dp_last_error().decode() if rc != D3DP_OK else ""
-    if rc == D3DP_OK:
-        lib.d3dp_destroy(h)
-    return rc, msg
-
-
-def reached_the_device_check(rc, msg):
-    return rc == D3DP_OK or (rc == D3DP_EHIP and "no HIP device" in msg)
 
 
 def switches(monkeypatch, train_impl=None):
