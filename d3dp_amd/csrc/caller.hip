@@ -74,11 +74,15 @@ __global__ __launch_bounds__(256) void jpma_combine_kernel(const float* __restri
                                                            float* __restrict__ agg, int* __restrict__ sel) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
+  // torch.min over the gathered hypothesis axis, like jpma_kernel's own selection: the running best starts at rank 0; a
+  // later rank replaces it when its error is smaller, or is the first NaN; a NaN, once held, stays
   float best = INFINITY, x = 0.f, y = 0.f, z = 0.f;
   int h = 0;
   for (int r = 0; r < R; ++r) {
     const float* w = win + ((size_t)r * n + i) * 5;
-    if (w[0] < best) { best = w[0]; x = w[1]; y = w[2]; z = w[3]; h = __float_as_int(w[4]); }
+    if (r == 0 || w[0] < best || (w[0] != w[0] && best == best)) {
+      best = w[0]; x = w[1]; y = w[2]; z = w[3]; h = __float_as_int(w[4]);
+    }
   }
   agg[i * 3] = x; agg[i * 3 + 1] = y; agg[i * 3 + 2] = z;
   if (sel != nullptr) sel[i] = h;

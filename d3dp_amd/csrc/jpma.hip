@@ -12,7 +12,12 @@
 
 namespace {
 
-__device__ __forceinline__ float clamp1(float v) { return fminf(fmaxf(v, -1.f), 1.f); }
+// torch.clamp semantics (camera.py:44): NaN stays NaN (0 / 0 at a zero depth) -- fminf / fmaxf alone would make it -1
+__device__ __forceinline__ float clamp1(float v) { return v != v ? v : fminf(fmaxf(v, -1.f), 1.f); }
+
+// torch.min semantics (loss.py:39,67) for a running minimum that STARTS at hypothesis 0: a later value replaces it when
+// it is smaller, or when it is the first NaN; a NaN, once held, stays.  Ties and an all-+inf row keep the first index.
+__device__ __forceinline__ bool min_takes(float e, float best) { return e < best || (e != e && best == best); }
 
 // The selection below is INDEX work: it must pick the hypothesis the reference picks, so every float operation is
 // written out in the reference's order with explicit single roundings (__fmul_rn / __fadd_rn are never contracted into
@@ -78,9 +83,9 @@ __global__ __launch_bounds__(256) void jpma_kernel(const float* __restrict__ pre
     }
     const float e2 = norm2(u - g2u, v - g2v);                             // loss.py:66 torch.norm
     const float e3 = norm3(x[0] - g3[0], x[1] - g3[1], x[2] - g3[2]);     // loss.py:65
-    if (e3 < min3) { min3 = e3; mx = x[0]; my = x[1]; mz = x[2]; }
+    if (h == 0 || min_takes(e3, min3)) { min3 = e3; mx = x[0]; my = x[1]; mz = x[2]; }
     sx += x[0]; sy += x[1]; sz += x[2];
-    if (e2 < best2) { best2 = e2; bh = h; bx = x[0]; by = x[1]; bz = x[2]; best3 = e3; }
+    if (h == 0 || min_takes(e2, best2)) { best2 = e2; bh = h; bx = x[0]; by = x[1]; bz = x[2]; best3 = e3; }
   }
   if (agg != nullptr) { agg[i * 3] = bx; agg[i * 3 + 1] = by; agg[i * 3 + 2] = bz; }
   if (sel != nullptr) sel[i] = bh;

@@ -3,6 +3,8 @@
 // :244-254 DDIM update, :260-267 q_sample).  HBM-trivial (one (B,H,F,J,3) tensor per step); what matters is
 // matching the reference's arithmetic: fp32 multiplies/adds WITHOUT fma contraction, and fp64 for
 // predict_noise_from_start (its coefficients differ by 1e-9 relative at t=999: catastrophic in fp32).
+// The __f*_rn spellings below mark the single roundings but do not enforce them (the headers define them as plain
+// operators): this file is compiled with -ffp-contract=off (Makefile), which does, for the fp64 lines as well.
 #include "common.h"
 #include "kernels.h"
 
@@ -11,6 +13,11 @@ namespace {
 // torch.clamp semantics (diffusionpose.py:148,164): NaN stays NaN -- fminf / fmaxf alone would turn it into a bound and
 // hide a broken denoiser output behind a plausible pose
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return x != x ? x : fminf(fmaxf(x, lo), hi); }
+__device__ __forceinline__ double clampd(double x, double lo, double hi) { return x != x ? x : fmin(fmax(x, lo), hi); }
+
+// the reference clamps an fp32 tensor with the Python double 1.1 * scale: the bound is that double rounded ONCE.  The fp32
+// product 1.1f * scale is one ulp away at scale 0.75, 1.5, 3, 6, 7, ..., and every saturated element takes the bound's value
+__device__ __forceinline__ float clamp_bound(float scale) { return (float)(1.1 * (double)scale); }
 
 // xt2[0:B]  = clamp(img, +-1.1 s) / s
 // xt2[B:2B] = the same with x negated and left/right joints swapped (perm[j] = source joint of j)
@@ -19,7 +26,7 @@ __global__ __launch_bounds__(256) void ddim_pre_kernel(const float* __restrict__
                                                        int J) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;   // index over (b, h, f, j) rows of 3
   if (i >= total) return;
-  const float lim = 1.1f * scale;
+  const float lim = clamp_bound(scale);
   const int j = (int)(i % J);
   const size_t src = i - j + perm[j];
   float a[3], f[3];
@@ -45,7 +52,7 @@ __global__ __launch_bounds__(256) void ddim_post_kernel(const float* __restrict_
                                                         int J) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
-  const float lim = 1.1f * scale;
+  const float lim = clamp_bound(scale);
   const int j = (int)(i % J);
   const size_t src = total + (i - j + perm[j]);
   const size_t b = i / per_b_rows, r = i % per_b_rows;
@@ -76,7 +83,7 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
   const size_t b = i / per_b;
   const double lim = 1.1 * (double)scale;
   double v = a[b] * (double)__fmul_rn(x0[i], scale) + bb[b] * (double)noise[i];
-  v = fmin(fmax(v, -lim), lim) / (double)scale;
+  v = clampd(v, -lim, lim) / (double)scale;
   out[i] = (float)v;
 }
 

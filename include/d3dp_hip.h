@@ -345,7 +345,8 @@ D3DP_API int d3dp_q_sample(const float* x0, const float* noise, const double* sq
  * Replaces main.py:700 (root zeroing, if zero_root), :706-712 (trajectory add + project_to_2d, camera.py:30-60) and
  * the per-joint argmin + gather of loss.py:54-76 / main_3dhp.py:797-835 in ONE pass, without (B,K,H,F,J,*) temporaries.
  *   pred (B,K,H,F,J,3), traj (B,F,1,3), cam (9) = f(2) c(2) k(3) p(2), gt2d (B,F,J,2), gt3d (B,F,J,3) or NULL
- *   agg (B,K,F,J,3)  <- the hypothesis whose reprojection is closest to gt2d (first minimum, like torch.min)
+ *   agg (B,K,F,J,3)  <- the hypothesis whose reprojection is closest to gt2d (first minimum, like torch.min: a NaN error
+ *                       counts as the smallest and the first one wins; hypothesis 0 where every error is +inf)
  *   sel (B,K,F,J) int32 or NULL; err_sel / err_min (B,K,F,J) or NULL: |selected - gt3d| and min_h |pred_h - gt3d|
  *   (their means over (B,F,J) are the reference's J_Agg and J_Best errors per step). */
 D3DP_API int d3dp_jpma(const float* pred, const float* traj, const float* cam, const float* gt2d, const float* gt3d, float* agg,
