@@ -75,7 +75,7 @@ int d3dp_create(const d3dp_cfg* cfg, d3dp_ctx** out) {
   // The second stream of d3dp_train_backward and its events are made HERE, not on the first step: d3dp_train_backward then creates
   // nothing, and even a context's first step keeps the header's "does not allocate" (tests/test_hip_streams.py).
   // (exactly the contexts whose backward pass forks: split-fp16 Linears and D3DP_TRAIN_OVERLAP not 0)
-  if (TrainPath(*c).needs_aux) {
+  if (plan_train_path(*c, c->cfg).needs_aux) {
     bool ok = hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess;
     for (hipEvent_t& e : c->ev_done) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;

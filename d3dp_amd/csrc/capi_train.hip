@@ -3,94 +3,18 @@
 // Every Linear -- forward, dgrad, wgrad -- runs on split-fp16 operands scaled on the device by their own absmax (X2Train), the
 // weight gradients as TN products of two row-form operands (nothing is transposed), one merged launch per block on a second
 // stream; attention on the split-fp16 kernels of train_attn.hip; the rest are row-wise fp32 kernels (train.hip) that leave the
-// next Linear's operand or its absmax behind.  TrainPath (ctx.h) says which of these a context takes: the fp32 matrix-core
-// path (D3DP_TRAIN_IMPL=f32, every width outside {64, 128, 256, 512} that D3DP_TRAIN_IMPL=f16x2 has not opted in) stays as the
-// cross-check.  No float atomics (Reducer).
+// next Linear's operand or its absmax behind.  train_plan.h says which of these a step takes and where its tensors lie: both
+// passes begin with its TrainLayout and TrainPlan and carry them out, neither decides a route here.  The fp32 matrix-core path
+// (TrainPath::use_x2 false: D3DP_TRAIN_IMPL=f32, every width outside {64, 128, 256, 512} that D3DP_TRAIN_IMPL=f16x2 has not opted
+// in) stays as the cross-check.  No float atomics (Reducer).
+#include <optional>
+
 #include "ctx.h"
 
 namespace {
 
 // one launch inside a profile scope of its class (pc: the context under d3dp_profile_enable, else null; st: the caller's stream)
 #define TP(cls, call) { Scope ps_(pc, cls, st); LAUNCH_TRY(call); }
-
-struct TrainLayout {
-  size_t T, Tpad, C, Hd, unit;      // unit = T*C floats
-  // offsets in floats
-  size_t temb, x_final, zero_bias, saved0, saved_stride, tmp0;
-  // per-block saved tensors (offsets inside a block's slab)
-  size_t o_xin, o_qkv, o_att, o_xmid, o_hpre, o_xout;
-  // temporaries
-  size_t xn, y, hid, dA, dB, dC, dqkv, dh, z, At, Xt, Wt, dtemb, stats;
-  // split-fp16 operands of the training Linears (X2Train below): row form [rows][2 K] and transposed form [features][2 Tp]
-  size_t op_a, op_w, op_at, op_xt, part, part_rem, slots;
-  size_t part_floats;               // capacity of `part` and of `part2`: split-K partial products, at most ~ (CUs + tiles) output tiles
-  size_t op_a2, op_at2, part2;      // a second set of the dY operand and partial-tile regions: two weight-gradient products in flight
-  size_t x_cols, x_block;           // every Linear's activation operand kept from the forward pass for its wgrad: the ROW form [Tp][2 K]
-                                    // where the TN kernel applies (it is then also the forward product's operand), else the transposed [K][2 Tp]
-  size_t w_rows, w_cols, w_block;   // every weight's split operands (row form / transposed form), prepared once per step: w_block floats per block
-  size_t Tp_max;                    // columns (tokens, padded) of a transposed operand row
-  size_t stats_x2, stats_x2_stride; // per block: (log-sum-exp, dO . O) of every query of the split-fp16 temporal attention
-  size_t red, red_floats;           // partial sums of the backward pass (LayerNorm gammas / betas, biases, embedding side),
-                                    // summed in a fixed order by d3dp_train_reduce_many at its end
-  size_t total_floats;
-};
-
-constexpr int kGroupSlices = 32;     // slices of the grouped row sums (position / time embedding gradients)
-
-TrainLayout train_layout(const d3dp_cfg& g, int B) {
-  TrainLayout L{};
-  L.T = (size_t)B * g.frames * g.joints;
-  L.Tpad = (L.T + 15) / 16 * 16;
-  L.C = g.channels; L.Hd = g.hidden; L.unit = L.T * L.C;
-  size_t off = 0;
-  auto take = [&](size_t n) { size_t o = off; off += (n + 63) / 64 * 64; return o; };
-  L.temb = take((size_t)B * L.C);
-  L.x_final = take(L.unit);
-  L.zero_bias = take(4 * L.C);
-  L.o_xin = 0; L.o_qkv = L.unit; L.o_att = 4 * L.unit; L.o_xmid = 5 * L.unit; L.o_hpre = 6 * L.unit;
-  L.o_xout = 6 * L.unit + L.T * L.Hd;
-  L.saved_stride = (7 * L.unit + L.T * L.Hd + 63) / 64 * 64;
-  L.saved0 = take(L.saved_stride * 2 * g.depth);
-  L.xn = take(L.unit); L.y = take(L.unit); L.hid = take(L.T * L.Hd);
-  L.dA = take(L.unit); L.dB = take(L.unit); L.dC = take(L.unit);
-  L.dqkv = take(3 * L.unit); L.dh = take(L.T * L.Hd); L.z = take(L.unit);
-  const size_t wide = std::max<size_t>(3 * L.C, L.Hd);
-  L.At = take(wide * L.Tpad); L.Xt = take(wide * L.Tpad); L.Wt = take(wide * wide);
-  L.dtemb = take((size_t)B * 2 * L.C);              // (the training forward's time-MLP hidden layer borrows it: B x 2 C)
-  L.stats = take(d3dp_train_attn_stats_bytes(B * std::max(g.frames, g.joints), std::max(g.frames, g.joints), g.heads) / 4 + 64);
-  {
-    const size_t fmax = std::max<size_t>(3 * L.C, L.Hd), kmax = std::max<size_t>(L.C, L.Hd);
-    L.Tp_max = ((L.T + 31) / 32 + 64) * 32;          // (room for rounding the k-steps up to a multiple of the split count)
-    const size_t dy_all = 5 * L.C + L.Hd;            // the four dY of a block side by side (their weight gradients go out as ONE launch)
-    L.op_a = take(L.Tp_max * dy_all);                // [Tp][2 N] fp16 = Tp N floats per dY (rows T .. Tp - 1: the TN wgrad's zero rows)
-    L.op_w = take(fmax * kmax);                      // [N][2 K] or [K][2 N] fp16
-    L.op_at = take(fmax * L.Tp_max);                 // dY^T: [N][2 Tp] fp16
-    L.op_xt = take(kmax * L.Tp_max);                 // X^T:  [K][2 Tp] fp16
-    L.part_floats = (size_t)(1024 + 64) * 256 * 128;
-    L.part = take(L.part_floats);
-    L.op_a2 = take(L.Tp_max * dy_all); L.op_at2 = take(fmax * L.Tp_max); L.part2 = take(L.part_floats);
-    L.part_rem = take((size_t)16 * 256 * fmax);      // ... of a forward / dgrad product's remainder rows (its own region: the
-                                                     // weight-gradient product of the same dY runs concurrently on the second stream)
-    L.slots = take(2 * 8192);                        // absmax words | 1 / scale per operand
-    L.w_block = 4 * L.C * L.C + 2 * L.Hd * L.C;      // qkv | proj | fc1 | fc2 of one block ([N][2 K] fp16 = N K floats each)
-    L.x_block = (3 * L.C + L.Hd) * L.Tp_max;         // qkv | proj | fc1 | fc2 inputs of one block
-    L.x_cols = take(L.x_block * 2 * g.depth);
-    L.w_rows = take(L.w_block * 2 * g.depth);
-    L.w_cols = take(L.w_block * 2 * g.depth);
-  }
-  L.stats_x2_stride = (d3dp_train_attn_x2_stats_bytes(B * g.joints, g.frames, g.heads) / 4 + 63) / 64 * 64;   // (temporal axis: B J sequences of F tokens)
-  L.stats_x2 = take(L.stats_x2_stride * 2 * g.depth);
-  {
-    const size_t lnb = (size_t)D3DP_LN_BWD_BLOCKS * 2 * L.C;         // one LayerNorm call's [dgamma | dbeta] rows
-    L.red_floats = (size_t)(6 * g.depth + 2) * lnb                   // 3 LayerNorm backward calls per block + the head's
-                   + (size_t)2 * g.depth * std::max(D3DP_DYPREP_ROWS, D3DP_ROWPREP_ROWS) * (5 * L.C + L.Hd + 256)   // bias gradients: the column sums of every dY
-                   + (size_t)512 * (3 * L.C + 4) + (size_t)D3DP_EMBED_BWD_ROWS * 5 * L.C + (size_t)512 * L.C   // head, embedding
-                   + (size_t)kGroupSlices * (g.joints + (size_t)B) * L.C + 4096;                                // spos, time embedding
-    L.red = take(L.red_floats);
-  }
-  L.total_floats = off;
-  return L;
-}
 
 const float* mask_ptr(const float* masks, const d3dp_cfg& g, int B, int blk, int branch) {
   if (!masks) return nullptr;
@@ -136,28 +60,30 @@ int lin32(const float* A, const float* W, const float* bias, float* out, int M, 
   return d3dp_launch_linear_f32(EPI_BIAS, A, W, bias, out, M, N, K, st);
 }
 
+// weight / bias of one of a block's four Linears (j: TrainLinearId)
+const float* lin_w(const BlockDev& w, int j) { return (const float*)(j == kQkv ? w.qkv_w : j == kProj ? w.proj_w : j == kFc1 ? w.fc1_w : w.fc2_w); }
+const float* lin_b(const BlockDev& w, int j) { return j == kQkv ? w.qkv_b : j == kProj ? w.proj_b : j == kFc1 ? w.fc1_b : w.fc2_b; }
+
 // The training step's Linears on the split-fp16 scheme of EXACT inference (three fp16-MFMA passes, fp32-class; gemm_x2.hip
 // gemm_f16x2_dyn_kernel) instead of the fp32 matrix cores (1/16 of the fp16 rate).  Every operand -- activations, weights,
 // GRADIENTS -- is split at the power of two its own absmax asks for, computed and consumed on the device: no range is
 // assumed and nothing synchronises.  forward: out = A W^T + b;  dgrad: dX = dY W (W^T split as the "weight" operand);
 // wgrad: dW = dY^T X contracts over the batch's tokens into a handful of output tiles -> split-K over Z chunks of tokens,
 // partial products summed in a fixed order (deterministic; the fp32 path's split-K used atomics).
-// D3DP_TRAIN_PASSES=1 (`passes`): the same launches on the one-pass instantiations of the two product kernels -- hi(A) x hi(W)
+// D3DP_TRAIN_PASSES=1 (TrainPlan::passes): the same launches on the one-pass instantiations of the two product kernels -- hi(A) x hi(W)
 // alone, i.e. every operand rounded to fp16 at its own scale; operand passes, scales, k order, partial sums, streams: unchanged.
+// What a pass DECIDES is in the plan P (train_plan.h); this holds what a pass is in the middle of: the current operand set, the
+// deferred TN products, the slot counter, the streams.
 struct X2Train {
   hipStream_t st;
   float* ws;
   const TrainLayout& L;
-  int n_cu;
+  const TrainPlan& P;
   d3dp_ctx* pc;                                        // per-kernel profile (d3dp_profile_enable): classes T_LINEAR / T_WGRAD / T_OPERAND
   hipStream_t st_w = nullptr;                          // the weight-gradient products' stream (null: `st`)
-  bool tail_blocks;                                    // d3dp_ctx::train_tail_blocks
-  int passes;                                          // d3dp_ctx::train_passes: fp16-MFMA passes per product (3; 1 = D3DP_TRAIN_PASSES=1)
-  // the set-up of both passes of a step over T tokens: the same launch forms in forward and backward
-  X2Train(d3dp_ctx* c, const TrainLayout& L_, float* ws_, hipStream_t st_, int T)
-      : st(st_), ws(ws_), L(L_), n_cu(c->n_cu), pc(c->prof ? c : nullptr), tail_blocks(c->train_tail_blocks), passes(c->train_passes) {
+  X2Train(d3dp_ctx* c, const TrainLayout& L_, const TrainPlan& P_, float* ws_, hipStream_t st_)
+      : st(st_), ws(ws_), L(L_), P(P_), pc(c->prof ? c : nullptr) {
     use_set(0);
-    merged_setup(T, c->train_wgrad_merged);
   }
   // the dY operand (row form / transposed form) and the weight-gradient product's partial tiles live in one of two sets of
   // regions: the backward pass alternates, so that the operand pass of the next dY need not wait for the product of this one
@@ -168,37 +94,18 @@ struct X2Train {
   }
   // The four weight gradients of a block as ONE launch (gemm_f16x2_tn_kernel's product table): each dY's operand pass takes the
   // next region of the set, wgrad() only records its product, flush_wgrads() launches them and the sum of their partial tiles.
-  // On where every Linear of the block has a TN shape (merged_setup); mZ / mTp: split count and padded token count of the merged list.
-  bool merged = false;
-  int mZ = 1, mTp = 0, n_def = 0;
+  // On where every Linear of the block has a TN shape (TrainPlan::merged; mZ / mTp: split count and padded token count of the merged list).
+  int n_def = 0;
   D3dpTnProduct def[D3DP_TN_MAX];
   float* def_dw[D3DP_TN_MAX];
-  void merged_setup(int T, bool on) {
-    const int C = (int)L.C, Hd = (int)L.Hd;
-    const int shapes[4][2] = {{C, Hd}, {Hd, C}, {C, C}, {3 * C, C}};     // fc2, fc1, proj, qkv: [N, K] of dW
-    int tiles = 0;
-    bool ok = on;
-    size_t nk_sum = 0;
-    for (auto& sh : shapes) { ok = ok && d3dp_tn_applies(sh[0], sh[1]); tiles += ((sh[0] + 255) / 256) * ((sh[1] + 127) / 128); nk_sum += (size_t)sh[0] * sh[1]; }
-    const int nk = (T + 31) / 32;
-    mZ = std::max(1, std::min(std::min(n_cu / std::max(tiles, 1), 64), nk / 4));
-    mTp = mZ * ((nk + mZ - 1) / mZ) * 32;
-    merged = ok && (size_t)mTp <= L.Tp_max && (size_t)mZ * nk_sum <= L.part_floats;
-  }
-  // rows the operands of the weight gradient dW[N, K] must have (zero behind T)
-  int pad_rows(int T, int N, int K) const {
-    int Z, Tp;
-    wgrad_split(T, N, K, Z, Tp);
-    return merged ? std::max(Tp, mTp) : Tp;
-  }
   int flush_wgrads() {
     if (!n_def) return 0;
     hipStream_t sw = st_w ? st_w : st;
     Scope ps(pc, T_WGRAD, sw);
-    int r = d3dp_launch_linear_f16x2_tn_many(def, n_def, mTp, mZ, sw, passes);
+    int r = d3dp_launch_linear_f16x2_tn_many(def, n_def, P.mTp, P.mZ, sw, P.passes);
     if (r) return r;
     D3dpSumTable tb{};
-    tb.n = n_def; tb.Z = mZ;
+    tb.n = n_def; tb.Z = P.mZ;
     for (int i = 0; i < n_def; ++i) { tb.part[i] = def[i].out; tb.out[i] = def_dw[i]; tb.n4[i] = (size_t)def[i].N * def[i].K / 4; }
     d3dp_launch_sum_partials_many(tb, sw);
     n_def = 0;
@@ -208,18 +115,21 @@ struct X2Train {
   // + {qkv, proj, fc1, fc2} and leaves them -- with the operands themselves: the weights' two forms and every activation's
   // transposed form -- for the backward pass of the same step, whose wgrad / dgrad read the same tensors: 128 of the step's
   // 320 absmax launches are not repeated.  The backward pass allocates its own (the gradients) from kBwdSlot0.
-  static constexpr int kBwdSlot0 = 4096;
-  static constexpr int kQkvSlot0 = 2048;               // forward range: slot kQkvSlot0 + block = absmax of that block's qkv OUTPUT
+  static constexpr int kBwdSlot0 = kTrainBwdSlot0;
+  static constexpr int kQkvSlot0 = kTrainQkvSlot0;     // forward range: slot kQkvSlot0 + block = absmax of that block's qkv OUTPUT
+  static constexpr int kPmaxSlot0 = kTrainPmaxSlot0;   // forward range: slot kPmaxSlot0 + block = largest positive fc1 output
   int next = 0;
   unsigned* amax() const { return reinterpret_cast<unsigned*>(ws + L.slots); }
-  float* uns() const { return ws + L.slots + 8192; }
+  float* uns() const { return ws + L.slots + kTrainSlots; }
+  // (null where the attention of that block's axis does not run on split-fp16 operands: nobody reads the slot)
+  unsigned* qkv_amax(int blk) const { return P.path.attn_x2(blk & 1) ? amax() + kQkvSlot0 + blk : nullptr; }
   int begin(bool forward_pass) {
     next = forward_pass ? 0 : kBwdSlot0;
     return hipMemsetAsync(ws + L.slots + next, 0, (size_t)kBwdSlot0 * 4, st) == hipSuccess ? 0 : -3;
   }
-  int take() { return (next < kBwdSlot0 || next >= 8192) ? -1 : next++; }   // a fresh slot of the backward range for a producer kernel to fill
+  int take() { return (next < kBwdSlot0 || next >= kTrainSlots) ? -1 : next++; }   // a fresh slot of the backward range for a producer kernel to fill
   int slot_for(const float* src, size_t n) {           // absmax of a tensor into a fresh slot of the backward range
-    if (next < kBwdSlot0 || next >= 8192) return -1;
+    if (next < kBwdSlot0 || next >= kTrainSlots) return -1;
     d3dp_launch_absmax(src, n, amax() + next, st);
     return next++;
   }
@@ -229,27 +139,24 @@ struct X2Train {
   void cols(const float* src, int R, int C, int Rpad, void* dst, int slot) {   // [R][C] -> [C][2 Rpad]
     d3dp_launch_split2_t_dyn(src, dst, R, C, Rpad, amax() + slot, uns() + slot, st);
   }
-  // Every weight's absmax, row form and transposed form in three launches at the start of the forward pass (up to 64
-  // Linears: depth <= 8; deeper models prepare each weight where it is used).  woff(l): float offset of Linear l's operands
-  // inside the w_rows / w_cols regions.
-  bool batched = false;
+  // Every weight's absmax, row form and transposed form in three launches at the start of the forward pass (TrainPlan::batched: up
+  // to 64 Linears, depth <= 8; deeper models prepare each weight where it is used).  woff(l): float offset of Linear l's operands
+  // inside the w_rows / w_cols regions; xoff(l): of its activation operand inside x_cols.
   size_t xoff(int l) const { return (size_t)(l >> 2) * L.x_block + (size_t)(l & 3) * L.C * L.Tp_max; }
   size_t woff(int l) const {
     const size_t CC = L.C * L.C, j = (size_t)(l & 3);
     return (size_t)(l >> 2) * L.w_block + (j == 0 ? 0 : j == 1 ? 3 * CC : j == 2 ? 4 * CC : 4 * CC + L.Hd * L.C);
   }
+  float* x_op(int l) const { return ws + L.x_cols + xoff(l); }   // Linear l's activation operand, kept for the backward pass of the step
   int prepare_weights(const d3dp_ctx* c) {
+    if (!P.batched) return 0;
     const int nl = 8 * c->cfg.depth;
-    batched = nl <= D3DP_WPREP_MAX;
-    if (!batched) return 0;
     D3dpWPrepTable tb{};
     tb.n = nl;
-    const int C = (int)L.C, Hd = (int)L.Hd;
     for (int l = 0; l < nl; ++l) {
       const int blk = l >> 2, j = l & 3;
       const BlockDev& w = (blk & 1) ? c->tte[blk >> 1] : c->ste[blk >> 1];
-      const void* p = j == 0 ? w.qkv_w : j == 1 ? w.proj_w : j == 2 ? w.fc1_w : w.fc2_w;
-      tb.it[l] = D3dpWPrepItem{(const float*)p, j == 0 ? 3 * C : j == 2 ? Hd : C, j == 3 ? Hd : C, 2 * l + 1, 0, woff(l)};
+      tb.it[l] = D3dpWPrepItem{lin_w(w, j), P.lin[j].N, P.lin[j].K, 2 * l + 1, 0, woff(l)};
     }
     return d3dp_launch_wprep(tb, ws + L.w_rows, ws + L.w_cols, amax(), uns(), st);
   }
@@ -259,159 +166,129 @@ struct X2Train {
   // a round of their own the kernel takes them as 16 x 64 blocks spread over all workgroups (round 5; gemm_f16x2_dyn_kernel).
   // D3DP_TRAIN_TAIL=split, and contractions that are not a multiple of 16 k-steps, keep round 4's form: from 32 k-steps on a
   // second launch as a split-K product (Z chunks of the contraction: tn Z short work items instead of tn long ones) whose
-  // partial sums are added in a fixed order, else the extra round.
-  int gemm(const float* A2, const float* W2, const float* bias, const float* ua, const float* uw, float* out, int T, int N,
+  // partial sums are added in a fixed order, else the extra round.  (Which of the three: train_plan.h train_tail.)
+  int gemm(TrainTail tail, const float* A2, const float* W2, const float* bias, const float* ua, const float* uw, float* out, int N,
            int K, unsigned* out_amax = nullptr, int amax_pos = 0) {
     Scope ps(pc, T_LINEAR, st);
-    const int tn = (N + 127) / 128, q = T / 256, rem = T - q * 256;
-    const int rounds_all = ((q + (rem ? 1 : 0)) * tn + n_cu - 1) / n_cu, rounds_full = (q * tn + n_cu - 1) / n_cu;
-    const int nk = K / 32;
-    int Z = 1;
-    for (int z = 2; z <= 16; ++z)
-      if (nk % z == 0) Z = z;
-    // (measured: a last round of a few tiles runs its k-steps at 0.75 us -- few CUs active, full clock -- against 1.4 us in a
-    //  full round, so for 16 k-steps it costs 12 us, what the second launch and the sum cost too: split from 32 k-steps on)
-    // the remainder rows as 16 x 64 blocks at the end of the same launch (gemm_f16x2_dyn_kernel): wherever they would cost a round
-    if (tail_blocks && rem && q && rounds_all > rounds_full && nk % 16 == 0)
-      return d3dp_launch_linear_f16x2_dyn(A2, W2, bias, ua, uw, out, T, N, K, 1, st, out_amax, amax_pos, 1, passes);
-    if (rem == 0 || q == 0 || rounds_all == rounds_full || Z == 1 || nk < 32 || (size_t)Z * rem * N > (size_t)16 * 256 * std::max<size_t>(3 * L.C, L.Hd))
-      return d3dp_launch_linear_f16x2_dyn(A2, W2, bias, ua, uw, out, T, N, K, 1, st, out_amax, amax_pos, 0, passes);
+    const int T = P.T, passes = P.passes;
+    if (tail.form != TrainTailForm::SPLIT_REM)
+      return d3dp_launch_linear_f16x2_dyn(A2, W2, bias, ua, uw, out, T, N, K, 1, st, out_amax, amax_pos,
+                                          tail.form == TrainTailForm::REM_BLOCKS ? 1 : 0, passes);
+    const int q = T / 256, rem = T - q * 256;
     int r = d3dp_launch_linear_f16x2_dyn(A2, W2, bias, ua, uw, out, q * 256, N, K, 1, st, out_amax, amax_pos, 0, passes);
     if (r) return r;
-    r = d3dp_launch_linear_f16x2_dyn(A2 + (size_t)q * 256 * K, W2, nullptr, ua, uw, ws + L.part_rem, rem, N, K, Z, st, nullptr, 0, 0, passes);   // (a row = 2 K fp16 = K floats)
+    r = d3dp_launch_linear_f16x2_dyn(A2 + (size_t)q * 256 * K, W2, nullptr, ua, uw, ws + L.part_rem, rem, N, K, tail.Z, st, nullptr, 0, 0, passes);   // (a row = 2 K fp16 = K floats)
     if (r) return r;
-    d3dp_launch_sum_partials_bias(ws + L.part_rem, bias, out + (size_t)q * 256 * N, (size_t)rem * N, N, Z, st, out_amax, amax_pos);
+    d3dp_launch_sum_partials_bias(ws + L.part_rem, bias, out + (size_t)q * 256 * N, (size_t)rem * N, N, tail.Z, st, out_amax, amax_pos);
     return 0;
   }
-  // out[T, N] = A[T, K] W[N, K]^T + bias     (l: the Linear's index, see the slots above)
-  // (a_amax_ready: the kernel that produced A already left its absmax in slot 2 l)
-  // (out_amax: optional slot for the OUTPUT's absmax, left by the product's epilogue)
-  // (a_prepared: the activation operand of Linear l -- planes at x_cols + xoff(l), zero rows behind T, unscale slot 2 l -- was
-  //  written by its producer: gelu_operand below)
-  // (ln_w / ln_b / ln_eps: A is the INPUT of the LayerNorm whose output is this Linear's operand, slot 2 l holds that output's
-  //  absmax: the operand pass normalises on the fly, d3dp_launch_rowprep_ln -- TN shapes with K <= 512 only, see ln_operand_applies)
-  bool ln_operand_applies(int N, int K) const { return d3dp_tn_applies(N, K) && K <= 512; }
-  int forward(int l, const float* A, const float* W, const float* bias, float* out, int T, int N, int K, bool a_amax_ready = false,
-              unsigned* out_amax = nullptr, int amax_pos = 0, bool a_prepared = false, const float* ln_w = nullptr,
-              const float* ln_b = nullptr, float ln_eps = 0.f) {
-    const int sa = 2 * l, sw = 2 * l + 1;
-    if (l < 0 || sw >= kBwdSlot0) return -1;
-    const float* a2 = ws + o_a;
-    if (a_prepared) a2 = ws + L.x_cols + xoff(l);
-    else {
+  // out[T, N] = A[T, K] W[N, K]^T + bias of Linear l = 4 blk + j (see the slots above).  Where its activation operand comes from
+  // is the plan's TrainOperand:
+  //   ROWS / ROWS_T  an operand pass over the fp32 rows A; the kernel that produced A already left its absmax in slot 2 l
+  //                  (but the fp32-MFMA temporal attention in front of proj: TrainPlan::attn_t_f32_mfma)
+  //   LN_INPUT       A is the INPUT of the LayerNorm whose output is this Linear's operand (norm1 in front of qkv, norm2 in front of
+  //                  fc1), slot 2 l holds that output's absmax: the operand pass normalises on the fly, d3dp_launch_rowprep_ln
+  //   PRODUCER       the operand -- planes at x_op(l), zero rows behind T, unscale slot 2 l -- was written by its producer; A is not read
+  // The product's epilogue leaves the OUTPUT's absmax where a kernel behind it asks for one: qkv's in qkv_amax(blk), the largest
+  // positive fc1 output in kPmaxSlot0 + blk where gelu_operand() follows.
+  int forward(int blk, TrainLinearId j, const float* A, const BlockDev& w, float ln_eps, float* out) {
+    const TrainLinear& p = P.lin[j];
+    const int l = 4 * blk + j, sa = 2 * l, sw = 2 * l + 1, T = P.T, N = p.N, K = p.K;
+    if (sw >= kBwdSlot0) return -1;
+    const float* W = lin_w(w, j);
+    const bool pmax = j == kFc1 && P.gelu_operand;
+    unsigned* out_amax = j == kQkv ? qkv_amax(blk) : pmax ? amax() + kPmaxSlot0 + blk : nullptr;
+    const TrainOperand src = P.source(blk, j);
+    const float* a2 = x_op(l);
+    if (src != TrainOperand::PRODUCER) {
       Scope ps(pc, T_OPERAND, st);
-      if (!a_amax_ready) d3dp_launch_absmax(A, (size_t)T * K, amax() + sa, st);
+      if (j == kProj && (blk & 1) && P.attn_t_f32_mfma) d3dp_launch_absmax(A, (size_t)T * K, amax() + sa, st);
       // the operand of this product and, in the same pass, what the wgrad of this Linear will want of it: the backward pass
       // then neither recomputes this activation (LayerNorm / GELU outputs) nor reads it again.  Where the TN wgrad kernel applies
       // that is the SAME row form (kept, zero rows behind T), else a second, transposed form.
-      const int Tp = pad_rows(T, N, K);
-      if ((size_t)Tp > L.Tp_max) return -1;
+      const int Tp = p.pad_rows;
       int r;
-      if (ln_w) {
-        if (!ln_operand_applies(N, K) || !a_amax_ready) return -1;
-        a2 = ws + L.x_cols + xoff(l);
-        r = d3dp_launch_rowprep_ln(A, ln_w, ln_b, ln_eps, ws + L.x_cols + xoff(l), T, Tp, K, amax() + sa, uns() + sa, st);
-      } else if (d3dp_tn_applies(N, K)) {
-        a2 = ws + L.x_cols + xoff(l);
-        r = d3dp_launch_rowprep(A, ws + L.x_cols + xoff(l), nullptr, nullptr, T, Tp, K, amax() + sa, uns() + sa, st);
-      } else r = d3dp_launch_dyprep(A, ws + o_a, ws + L.x_cols + xoff(l), nullptr, T, K, Tp, amax() + sa, uns() + sa, st);
+      if (src == TrainOperand::LN_INPUT)
+        r = d3dp_launch_rowprep_ln(A, j == kQkv ? w.n1w : w.n2w, j == kQkv ? w.n1b : w.n2b, ln_eps, x_op(l), T, Tp, K, amax() + sa, uns() + sa, st);
+      else if (src == TrainOperand::ROWS)
+        r = d3dp_launch_rowprep(A, x_op(l), nullptr, nullptr, T, Tp, K, amax() + sa, uns() + sa, st);
+      else {
+        a2 = ws + o_a;
+        r = d3dp_launch_dyprep(A, ws + o_a, x_op(l), nullptr, T, K, Tp, amax() + sa, uns() + sa, st);
+      }
       if (r) return r;
     }
     const float* w2 = ws + L.op_w;
-    if (batched) w2 = ws + L.w_rows + woff(l);
+    if (P.batched) w2 = ws + L.w_rows + woff(l);
     else {
       Scope ps(pc, T_OPERAND, st);
       d3dp_launch_absmax(W, (size_t)N * K, amax() + sw, st);
       rows(W, N, K, ws + L.op_w, sw);
     }
-    return gemm(a2, w2, bias, uns() + sa, uns() + sw, out, T, N, K, out_amax, amax_pos);
+    return gemm(p.fwd_tail, a2, w2, lin_b(w, j), uns() + sa, uns() + sw, out, N, K, out_amax, pmax ? 1 : 0);
   }
-  // whether Linear l (N out features, K in) takes its GELU'd input straight from its producer's output: TN shapes only (the
-  // row form is then also the wgrad operand)
-  bool gelu_operand_applies(int N, int K) const { return d3dp_tn_applies(N, K); }
-  static constexpr int kPmaxSlot0 = 3072;              // forward range: slot kPmaxSlot0 + block = largest positive fc1 output
-  int gelu_operand(int l, const float* hpre, int blk, int T, int N, int K) {
-    const int Tp = pad_rows(T, N, K);
-    if ((size_t)Tp > L.Tp_max) return -1;
+  // the fc2 operand of block blk from the fc1 output hpre (TrainPlan::gelu_operand)
+  int gelu_operand(int blk, const float* hpre) {
+    const int l = 4 * blk + kFc2;
     Scope ps(pc, T_OPERAND, st);
-    return d3dp_launch_gelu_rowprep(hpre, ws + L.x_cols + xoff(l), T, Tp, K, amax() + kPmaxSlot0 + blk, amax() + 2 * l, uns() + 2 * l, st);
+    return d3dp_launch_gelu_rowprep(hpre, x_op(l), P.T, P.lin[kFc2].pad_rows, P.lin[kFc2].K, amax() + kPmaxSlot0 + blk, amax() + 2 * l, uns() + 2 * l, st);
   }
-  // dX[T, K] = dY[T, N] W[N, K]   (sdy: the absmax slot of dY, shared with wgrad; l: the forward Linear whose W this is)
-  int dgrad(int l, const float* dY, int sdy, const float* W, float* dX, int T, int N, int K, unsigned* out_amax = nullptr) {
-    const int sw = 2 * l + 1;
+  // dX[T, K] = dY[T, N] W[N, K] of Linear l = 4 blk + j   (sdy: the absmax slot of dY, shared with wgrad; always right behind the
+  // wgrad of the same dY, whose prep_dy left the row form of dY in the current set)
+  int dgrad(int blk, TrainLinearId j, int sdy, const float* W, float* dX, unsigned* out_amax = nullptr) {
+    const TrainLinear& p = P.lin[j];
+    const int l = 4 * blk + j, sw = 2 * l + 1;
     {
-      Scope ps(pc, T_OPERAND, st);
-      if (!dy_ready) rows(dY, T, N, ws + o_a, sdy);
-      if (!batched) cols(W, N, K, N, ws + L.op_w, sw);   // W^T: [K][2 N]  (N % 32 == 0: the model's widths)
+      Scope ps(pc, T_OPERAND, st);                     // (the profile counts this scope per dgrad, with or without a launch in it)
+      if (!P.batched) cols(W, p.N, p.K, p.N, ws + L.op_w, sw);   // W^T: [K][2 N]  (N % 32 == 0: the model's widths)
     }
     const float* wt = ws + L.op_w;
-    if (batched) wt = ws + L.w_cols + woff(l);         // (prepared by the forward pass of this step)
-    return gemm(ws + o_a, wt, nullptr, uns() + sdy, uns() + sw, dX, T, K, N, out_amax);
+    if (P.batched) wt = ws + L.w_cols + woff(l);       // (prepared by the forward pass of this step)
+    return gemm(p.dgrad_tail, ws + o_a, wt, nullptr, uns() + sdy, uns() + sw, dX, p.K, p.N, out_amax);
   }
-  // split count / padded token count of the wgrad product dW[N, K] = dY^T X
-  void wgrad_split(int T, int N, int K, int& Z, int& Tp) const {
-    const int tiles = ((N + 255) / 256) * ((K + 127) / 128);
-    const int nk = (T + 31) / 32;
-    Z = std::max(1, std::min(std::min(n_cu / tiles, 64), nk / 4));
-    const int nkz = (nk + Z - 1) / Z;
-    Tp = Z * nkz * 32;
-  }
-  // everything the backward pass of Linear [N, K] needs from its dY in one pass: row form -> op_a (dgrad), transposed form
-  // -> op_at (wgrad), the bias gradient's partial column sums -> bias_part (D3DP_DYPREP_ROWS rows of N floats).  `dy_ready`
-  // then tells dgrad / wgrad not to build them again.
-  bool dy_ready = false;
-  static constexpr int kBiasRows = D3DP_DYPREP_ROWS > D3DP_ROWPREP_ROWS ? D3DP_DYPREP_ROWS : D3DP_ROWPREP_ROWS;   // capacity of bias_part
-  // (mask: the DropPath scales still to be applied to dY's rows -- TN shapes only, see mask_in_prep_applies)
+  // everything the backward pass of Linear j needs from its dY in one pass: row form -> op_a (dgrad), transposed form
+  // -> op_at (wgrad, where the TN kernel does not apply), the bias gradient's partial column sums -> bias_part (*bias_rows rows of
+  // N floats, at most TrainLayout::bias_rows).
+  // (mask: the DropPath scales still to be applied to dY's rows -- TrainPlan::mip1 / mip2)
   // (gelu_pre: dY is d hidden and the Linear's dY is dY x gelu'(gelu_pre), formed by the operand pass; slot sdy then holds the
-  //  absmax of d hidden -- TN shapes the row pass takes only, see gelu_in_prep_applies)
-  bool mask_in_prep_applies(int N, int K) const { return d3dp_tn_applies(N, K); }
-  bool gelu_in_prep_applies(int N, int K) const { return d3dp_tn_applies(N, K) && N <= 1536; }
-  int prep_dy(const float* dY, int sdy, float* bias_part, int* bias_rows, int T, int N, int K, const float* mask = nullptr,
-              int axis = 0, int F = 1, int J = 1, const float* gelu_pre = nullptr) {
-    const int Tp = pad_rows(T, N, K);
-    if ((size_t)Tp > L.Tp_max) return -1;
-    if (merged) {                    // the next region of the set: the block's four dY stay until flush_wgrads()
-      if (set_used + L.Tp_max * (size_t)N > L.Tp_max * (5 * L.C + L.Hd)) return -1;
+  //  absmax of d hidden -- TrainPlan::gip)
+  int prep_dy(TrainLinearId j, const float* dY, int sdy, float* bias_part, int* bias_rows, const float* mask = nullptr, int axis = 0,
+              int F = 1, int J = 1, const float* gelu_pre = nullptr) {
+    const TrainLinear& p = P.lin[j];
+    if (P.merged) {                  // the next region of the set: the block's four dY stay until flush_wgrads()
+      if (set_used + L.Tp_max * (size_t)p.N > L.dy_set_floats) return -1;
       o_a = set_base + set_used;
-      set_used += L.Tp_max * (size_t)N;
+      set_used += L.Tp_max * (size_t)p.N;
     }
-    dy_ready = true;
     Scope ps(pc, T_OPERAND, st);
-    if (d3dp_tn_applies(N, K))       // the row form alone (zero rows behind T): dgrad's operand AND the TN wgrad's
-      return d3dp_launch_rowprep(dY, ws + o_a, bias_part, bias_rows, T, Tp, N, amax() + sdy, uns() + sdy, st, mask, axis, F, J,
+    if (p.tn)                        // the row form alone (zero rows behind T): dgrad's operand AND the TN wgrad's
+      return d3dp_launch_rowprep(dY, ws + o_a, bias_part, bias_rows, P.T, p.pad_rows, p.N, amax() + sdy, uns() + sdy, st, mask, axis, F, J,
                                  gelu_pre);
-    if (mask || gelu_pre) return -1;
     *bias_rows = D3DP_DYPREP_ROWS;
-    return d3dp_launch_dyprep(dY, ws + o_a, ws + o_at, bias_part, T, N, Tp, amax() + sdy, uns() + sdy, st);
+    return d3dp_launch_dyprep(dY, ws + o_a, ws + o_at, bias_part, P.T, p.N, p.pad_rows, amax() + sdy, uns() + sdy, st);
   }
-  // dW[N, K] = dY[T, N]^T X[T, K]   (X: the activation operand of forward Linear l)
-  int wgrad(int l, const float* dY, int sdy, const float* X, float* dW, int T, int N, int K) {
-    const int sx = 2 * l;
-    int Z, Tp;
-    wgrad_split(T, N, K, Z, Tp);
-    if ((size_t)Tp > L.Tp_max || (size_t)Z * N * K > L.part_floats) return -1;
-    (void)X;                                           // X's operand form: left by the forward pass of this step
-    if (merged) {                                      // recorded; launched with the block's other three by flush_wgrads()
-      if (!dy_ready || n_def >= D3DP_TN_MAX || !d3dp_tn_applies(N, K)) return -1;
+  // dW[N, K] = dY[T, N]^T X[T, K] of Linear l = 4 blk + j   (dY: as prep_dy left it; X: the activation operand of forward Linear l,
+  // left by the forward pass of this step)
+  int wgrad(int blk, TrainLinearId j, int sdy, float* dW) {
+    const TrainLinear& p = P.lin[j];
+    const int l = 4 * blk + j, sx = 2 * l, N = p.N, K = p.K;
+    if (P.merged) {                                    // recorded; launched with the block's other three by flush_wgrads()
+      if (n_def >= D3DP_TN_MAX) return -1;
       size_t po = 0;
-      for (int i = 0; i < n_def; ++i) po += (size_t)mZ * def[i].N * def[i].K;
-      def[n_def] = D3dpTnProduct{ws + o_a, ws + L.x_cols + xoff(l), uns() + sdy, uns() + sx, ws + o_part + po, N, K, 0, 0};
+      for (int i = 0; i < n_def; ++i) po += (size_t)P.mZ * def[i].N * def[i].K;
+      def[n_def] = D3dpTnProduct{ws + o_a, x_op(l), uns() + sdy, uns() + sx, ws + o_part + po, N, K, 0, 0};
       def_dw[n_def++] = dW;
       return 0;
     }
     int r;
     hipStream_t sw = st_w ? st_w : st;
     Scope ps(pc, T_WGRAD, sw);
-    if (d3dp_tn_applies(N, K)) {                        // both operands in their row forms [Tp][2 .]: nothing was transposed
-      if (!dy_ready) return -1;
-      r = d3dp_launch_linear_f16x2_tn(ws + o_a, ws + L.x_cols + xoff(l), uns() + sdy, uns() + sx, ws + o_part, N, K, Tp, Z, sw, passes);
-    } else {
-      if (!dy_ready) return -1;                         // (the transposed form: left by prep_dy)
-      r = d3dp_launch_linear_f16x2_dyn(ws + o_at, ws + L.x_cols + xoff(l), nullptr, uns() + sdy, uns() + sx, ws + o_part, N, K,
-                                       Tp, Z, sw, nullptr, 0, 0, passes);
-    }
+    if (p.tn)                                          // both operands in their row forms [Tp][2 .]: nothing was transposed
+      r = d3dp_launch_linear_f16x2_tn(ws + o_a, x_op(l), uns() + sdy, uns() + sx, ws + o_part, N, K, p.Tp, p.Z, sw, P.passes);
+    else                                               // (the transposed form: left by prep_dy)
+      r = d3dp_launch_linear_f16x2_dyn(ws + o_at, x_op(l), nullptr, uns() + sdy, uns() + sx, ws + o_part, N, K, p.Tp, p.Z, sw, nullptr, 0, 0, P.passes);
     if (r) return r;
-    d3dp_launch_sum_partials(ws + o_part, dW, (size_t)N * K, Z, sw);
+    d3dp_launch_sum_partials(ws + o_part, dW, (size_t)N * K, p.Z, sw);
     return 0;
   }
 };
@@ -432,43 +309,41 @@ int d3dp_train_forward(d3dp_ctx* c, const float* x2d, const float* x3d, const in
   if (!c->train()) return d3dp_fail(D3DP_ESTATE, "d3dp_train_forward needs a D3DP_MODE_TRAIN context");
   if (!c->weights_set) return d3dp_fail(D3DP_ESTATE, "weights not set");
   const d3dp_cfg& g = c->cfg;
-  const TrainPath path(*c);
-  const bool use_x2 = path.use_x2;
+  const TrainLayout L = train_layout(g, B);
+  const TrainPlan P = plan_train_step(*c, g, B, c->n_cu);
   // clips longer than 256 frames (reference common/arguments.py:58, main.py:325 train at any `-f`): the split-fp16 attention kernels
   // pass their keys / queries through LDS in chunks (train_attn.hip: head dims 64, 32 and 16, and 24 / 40 / 48 / 56 at the widths
   // D3DP_TRAIN_IMPL=f16x2 opts in); the fp32 kernels hold whole sequences, and they are what head dim 8, a width on the fp32 path
   // and the cross-check switches run
-  if (g.frames > 256 && !(path.attn_x2(0) && path.attn_x2(1)))
+  if (g.frames > 256 && !(P.path.attn_x2(0) && P.path.attn_x2(1)))
     return d3dp_fail(D3DP_ENOTSUP, "frames=%d > 256: the training step runs such clips on its split-fp16 attention kernels only, which take "
                               "head dims 64, 32 and 16 -- 24, 40, 48 and 56 under D3DP_TRAIN_IMPL=f16x2 -- (channels=%d heads=%d is head dim %d) and are switched off by the cross-check "
                               "switches D3DP_TRAIN_IMPL=f32 and D3DP_TRAIN_ATTN=f32|x2t; the fp32 attention holds a whole sequence "
                               "in LDS (<= 256 frames)", g.frames, g.channels, g.heads, g.channels / g.heads);
-  const TrainLayout L = train_layout(g, B);
   if (workspace_bytes < L.total_floats * 4) return d3dp_fail(D3DP_ESTATE, "train workspace too small");
+  if (P.use_x2 && !P.rows_fit) return d3dp_fail(D3DP_EINVAL, "d3dp_train_forward: an operand's padded rows exceed the workspace's");
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
-  const int T = (int)L.T, C = g.channels, F = g.frames, J = g.joints, Hd = g.hidden;
+  const int T = P.T, C = g.channels, F = g.frames, J = g.joints, Hd = g.hidden;
   float *xn = ws + L.xn, *y = ws + L.y, *hid = ws + L.hid;
-  X2Train x2(c, L, ws, st, T);
-  d3dp_ctx* const pc = x2.pc;
-  if (use_x2) {
+  d3dp_ctx* const pc = c->prof ? c : nullptr;
+  std::optional<X2Train> x2s;
+  if (P.use_x2) x2s.emplace(c, L, P, ws, st);
+  X2Train* const x2 = P.use_x2 ? &*x2s : nullptr;
+  if (x2) {
     Scope ps_(pc, T_OTHER, st);
-    LAUNCH_TRY(x2.begin(true));
-    LAUNCH_TRY(x2.prepare_weights(c));
+    LAUNCH_TRY(x2->begin(true));
+    LAUNCH_TRY(x2->prepare_weights(c));
   }
-  auto lin = [&](int l, const float* A, const float* W, const float* bias, float* out, int M, int N, int K, bool a_amax_ready = false,
-                 unsigned* out_amax = nullptr, int amax_pos = 0, bool a_prepared = false, const float* ln_w = nullptr,
-                 const float* ln_b = nullptr, float ln_eps = 0.f) {
-    if (use_x2) return x2.forward(l, A, W, bias, out, M, N, K, a_amax_ready, out_amax, amax_pos, a_prepared, ln_w, ln_b, ln_eps);
+  // one of block blk's four Linears: src = the fp32 rows its operand pass reads -- its input, or where the plan says LN_INPUT the
+  // input of the LayerNorm in front of it; not read where its producer wrote the operand -- and, on the fp32 path, its input
+  auto lin = [&](int blk, TrainLinearId j, const float* src, float* out) -> int {
+    const BlockDev& w = (blk & 1) ? c->tte[blk >> 1] : c->ste[blk >> 1];
+    if (x2) return x2->forward(blk, j, src, w, g.eps_block, out);
     Scope ps_(pc, T_LINEAR, st);
-    return lin32(A, W, bias, out, M, N, K, st);
+    return lin32(src, lin_w(w, j), lin_b(w, j), out, T, P.lin[j].N, P.lin[j].K, st);
   };
-  // the qkv / fc1 operands straight from the INPUT of the LayerNorm in front of them (no fp32 normalised activation is written)
-  const bool ln_fused = use_x2 && x2.ln_operand_applies(3 * C, C) && x2.ln_operand_applies(Hd, C);
-  // ... and (round 6) written BY the kernel that produces that input, at the scale the LayerNorm's own weights bound (train.hip
-  // ln_operand_scale): the operand pass in front of qkv / fc1 disappears (block 0's qkv operand: the embedding kernel is shared
-  // with inference and keeps the pass)
-  const bool ln_direct = ln_fused && c->train_ln_direct && C % 256 == 0;
+  const bool ln_fused = P.ln_fused, ln_direct = P.ln_direct;
   TP(T_OTHER, d3dp_train_time_mlp(t, c->freq, c->t1w, c->t1b, c->t3w, c->t3b, ws + L.dtemb, ws + L.temb, B, C, st));   // (dtemb: free until the backward pass; needs B x 2 C)
   float* slab0 = ws + L.saved0;
   TP(T_LN_FWD, d3dp_launch_embed_ln(0, x2d, x3d, ws + L.temb, c->ew, c->eb, c->spos, c->ste[0].n1w, c->ste[0].n1b,
@@ -476,61 +351,46 @@ int d3dp_train_forward(d3dp_ctx* c, const float* x2d, const float* x3d, const in
   // Every Linear's activation operand arrives with its absmax already in slot 2 l, left there by the kernel that produced it
   // (round 4 ran 64 absmax launches per step); the two exceptions are the first block's input, which the inference embedding
   // kernel writes, and the temporal attention's output (the fp32-MFMA kernel is shared with inference).
-  auto slot = [&](int l) -> unsigned* { return use_x2 ? x2.amax() + 2 * l : nullptr; };
-  if (use_x2) { Scope ps_(pc, T_OTHER, st); d3dp_launch_absmax(xn, (size_t)T * C, slot(0), st); }
+  auto slot = [&](int l) -> unsigned* { return x2 ? x2->amax() + 2 * l : nullptr; };
+  if (x2) { Scope ps_(pc, T_OTHER, st); d3dp_launch_absmax(xn, (size_t)T * C, slot(0), st); }
   for (int blk = 0; blk < 2 * g.depth; ++blk) {
     const int kind = blk & 1, d = blk >> 1;
     const BlockDev& w = kind ? c->tte[d] : c->ste[d];
     float* S = ws + L.saved0 + (size_t)blk * L.saved_stride;
-    const bool ax2 = path.attn_x2(kind);                 // attention on split-fp16 operands (train_attn.hip)
-    unsigned* qkv_amax = ax2 ? x2.amax() + X2Train::kQkvSlot0 + blk : nullptr;
-    if (ln_direct && blk > 0) LAUNCH_TRY(lin(4 * blk, nullptr, (const float*)w.qkv_w, w.qkv_b, S + L.o_qkv, T, 3 * C, C, true, qkv_amax, 0, true));
-    else if (ln_fused) LAUNCH_TRY(lin(4 * blk, S + L.o_xin, (const float*)w.qkv_w, w.qkv_b, S + L.o_qkv, T, 3 * C, C, true, qkv_amax, 0, false,
-                                      w.n1w, w.n1b, g.eps_block));
-    else LAUNCH_TRY(lin(4 * blk, xn, (const float*)w.qkv_w, w.qkv_b, S + L.o_qkv, T, 3 * C, C, true, qkv_amax));
-    bool att_ready = true;
-    // the split-fp16 attention also writes the proj Linear's operand rows (scale: the qkv absmax bounds every output), round 6
-    const bool att_direct = ax2 && ln_direct && d3dp_tn_applies(C, C);
-    void* att_op = att_direct ? ws + L.x_cols + x2.xoff(4 * blk + 1) : nullptr;
-    const int att_tp = att_direct ? x2.pad_rows(T, C, C) : 0;
-    float* att_un = att_direct ? x2.uns() + 2 * (4 * blk + 1) : nullptr;
+    const bool ax2 = P.path.attn_x2(kind);               // attention on split-fp16 operands (train_attn.hip)
+    LAUNCH_TRY(lin(blk, kQkv, ln_fused ? S + L.o_xin : xn, S + L.o_qkv));
+    const bool att_direct = P.att_direct(kind);
+    void* att_op = att_direct ? x2->x_op(4 * blk + 1) : nullptr;
+    const int att_tp = att_direct ? P.lin[kProj].pad_rows : 0;
+    float* att_un = att_direct ? x2->uns() + 2 * (4 * blk + 1) : nullptr;
     const int n_seq = kind ? B * J : B * F;
     const SeqMap map = kind ? temporal_map(F, J) : spatial_map(F, J);
     auto attention = [&]() -> int {                      // (the launcher's own return code)
       if (ax2)
         return d3dp_train_attn_x2_fwd(S + L.o_qkv, S + L.o_att, ws + L.stats_x2 + (size_t)blk * L.stats_x2_stride, n_seq, map, C,
-                                      g.heads, qkv_amax, slot(4 * blk + 1), st, att_op, T, att_tp, att_un);
-      if (kind == 1 && use_x2 && C / g.heads == 64 && F <= 256) {   // temporal axis on the fp32 matrix cores (bitwise an fp32 fmaf chain per product)
-        att_ready = false;
+                                      g.heads, x2->qkv_amax(blk), slot(4 * blk + 1), st, att_op, T, att_tp, att_un);
+      if (kind == 1 && P.attn_t_f32_mfma)                // temporal axis on the fp32 matrix cores (bitwise an fp32 fmaf chain per product)
         return d3dp_launch_attn_temporal_f32(0, S + L.o_qkv, S + L.o_att, n_seq, map, C, g.heads, st);
-      }
       return d3dp_launch_attn_rows(0, S + L.o_qkv, S + L.o_att, n_seq, map, C, g.heads, st, slot(4 * blk + 1));
     };
     TP(kind ? T_ATTN_FWD_T : T_ATTN_FWD_S, attention());
-    LAUNCH_TRY(lin(4 * blk + 1, S + L.o_att, (const float*)w.proj_w, w.proj_b, y, T, C, C, att_ready, nullptr, 0, att_direct));
+    LAUNCH_TRY(lin(blk, kProj, S + L.o_att, y));
     if (ln_direct)
       TP(T_LN_FWD, d3dp_train_add_mask_ln(S + L.o_xin, y, mask_ptr(masks, g, B, blk, 0), kind, F, J, w.n2w, w.n2b, g.eps_block,
-                                          S + L.o_xmid, nullptr, slot(4 * blk + 2), T, C, st, ws + L.x_cols + x2.xoff(4 * blk + 2),
-                                          x2.pad_rows(T, Hd, C), x2.uns() + 2 * (4 * blk + 2)))
+                                          S + L.o_xmid, nullptr, slot(4 * blk + 2), T, C, st, x2->x_op(4 * blk + 2),
+                                          P.lin[kFc1].pad_rows, x2->uns() + 2 * (4 * blk + 2)))
     else
       TP(T_LN_FWD, d3dp_train_add_mask_ln(S + L.o_xin, y, mask_ptr(masks, g, B, blk, 0), kind, F, J, w.n2w, w.n2b, g.eps_block,
                                           S + L.o_xmid, ln_fused ? nullptr : xn, slot(4 * blk + 2), T, C, st));
-    const float* fc1_in = ln_fused ? S + L.o_xmid : xn;
-    const float *f1w = ln_fused ? w.n2w : nullptr, *f1b = ln_fused ? w.n2b : nullptr;
-    if (use_x2 && x2.gelu_operand_applies(C, Hd)) {
+    LAUNCH_TRY(lin(blk, kFc1, ln_fused ? S + L.o_xmid : xn, S + L.o_hpre));
+    if (P.gelu_operand) {
       // the fc2 operand = split(GELU(fc1 output)) in one pass, its scale from the largest positive fc1 output (the fc1
       // epilogue leaves it): no fp32 hidden tensor, no separate operand pass
-      if (ln_direct) LAUNCH_TRY(lin(4 * blk + 2, nullptr, (const float*)w.fc1_w, w.fc1_b, S + L.o_hpre, T, Hd, C, true,
-                                    x2.amax() + X2Train::kPmaxSlot0 + blk, 1, true));
-      else LAUNCH_TRY(lin(4 * blk + 2, fc1_in, (const float*)w.fc1_w, w.fc1_b, S + L.o_hpre, T, Hd, C, true,
-                          x2.amax() + X2Train::kPmaxSlot0 + blk, 1, false, f1w, f1b, g.eps_block));
-      LAUNCH_TRY(x2.gelu_operand(4 * blk + 3, S + L.o_hpre, blk, T, C, Hd));
-      LAUNCH_TRY(lin(4 * blk + 3, nullptr, (const float*)w.fc2_w, w.fc2_b, y, T, C, Hd, true, nullptr, 0, true));
+      LAUNCH_TRY(x2->gelu_operand(blk, S + L.o_hpre));
+      LAUNCH_TRY(lin(blk, kFc2, nullptr, y));
     } else {
-      LAUNCH_TRY(lin(4 * blk + 2, fc1_in, (const float*)w.fc1_w, w.fc1_b, S + L.o_hpre, T, Hd, C, true, nullptr, 0, ln_direct, f1w, f1b,
-                     g.eps_block));
       TP(T_OPERAND, d3dp_train_gelu_fwd(S + L.o_hpre, hid, (size_t)T * Hd, slot(4 * blk + 3), st));
-      LAUNCH_TRY(lin(4 * blk + 3, hid, (const float*)w.fc2_w, w.fc2_b, y, T, C, Hd, true));
+      LAUNCH_TRY(lin(blk, kFc2, hid, y));
     }
     // the block's end in one pass: residual add, the shared norm (+ Temporal_pos_embed after the first spatial block,
     // mixste.py:250) -> the next block's input, that block's norm1 -> its qkv operand (after the last block: the head's
@@ -543,9 +403,9 @@ int d3dp_train_forward(d3dp_ctx* c, const float* x2d, const float* x3d, const in
                                          kind ? c->tnb : c->snb, g.eps_block, (kind == 0 && d == 0) ? c->tpos : nullptr, nw, nb,
                                          last ? g.eps_head : g.eps_block, S + L.o_xout, x_next,
                                          last ? ws + L.z : (ln_fused ? nullptr : xn), last ? nullptr : slot(4 * (blk + 1)), T, C, st,
-                                         (ln_direct && !last) ? ws + L.x_cols + x2.xoff(4 * (blk + 1)) : nullptr,
-                                         (ln_direct && !last) ? x2.pad_rows(T, 3 * C, C) : 0,
-                                         (ln_direct && !last) ? x2.uns() + 2 * 4 * (blk + 1) : nullptr));
+                                         (ln_direct && !last) ? x2->x_op(4 * (blk + 1)) : nullptr,
+                                         (ln_direct && !last) ? P.lin[kQkv].pad_rows : 0,
+                                         (ln_direct && !last) ? x2->uns() + 2 * 4 * (blk + 1) : nullptr));
   }
   TP(T_OTHER, d3dp_train_head_linear(ws + L.z, c->hw, c->hb, out, T, C, st));
   HIP_TRY(hipGetLastError());
@@ -562,10 +422,13 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
   if (!c->train()) return d3dp_fail(D3DP_ESTATE, "d3dp_train_backward needs a D3DP_MODE_TRAIN context");
   const d3dp_cfg& g = c->cfg;
   const TrainLayout L = train_layout(g, B);
+  const TrainPlan P = plan_train_step(*c, g, B, c->n_cu);   // (as the forward pass of this step: the operands it left are the plan's)
   if (workspace_bytes < L.total_floats * 4) return d3dp_fail(D3DP_ESTATE, "train workspace too small");
+  if (P.use_x2 && !(P.rows_fit && P.parts_fit))
+    return d3dp_fail(D3DP_EINVAL, "d3dp_train_backward: an operand's padded rows or a weight gradient's partial products exceed the workspace's");
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
-  const int T = (int)L.T, Tp = (int)L.Tpad, C = g.channels, F = g.frames, J = g.joints, Hd = g.hidden;
+  const int T = P.T, Tp = (int)L.Tpad, C = g.channels, F = g.frames, J = g.joints, Hd = g.hidden;
   auto G = [](const float* p) { return const_cast<float*>(p); };
   // (one launch for the few gradient buffers that are still ACCUMULATED into -- the time MLP's; everything else is written:
   //  weight matrices by their wgrad product, every other gradient by the fixed-order reduction at the end of this function)
@@ -580,24 +443,19 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
   const size_t CC = (size_t)C * C;
   HIP_TRY(zero(grads->time1_w, 2 * CC)); HIP_TRY(zero(grads->time1_b, 2 * C));
   HIP_TRY(zero(grads->time3_w, 2 * CC)); HIP_TRY(zero(grads->time3_b, C));
-  HIP_TRY(zero(ws + L.zero_bias, 4 * (size_t)C));
   d3dp_ctx* const pc = c->prof ? c : nullptr;
   if (ztab.count) TP(T_OTHER, d3dp_train_zero_many(ztab, st));
-  const float* zb = ws + L.zero_bias;
   float *xn = ws + L.xn, *hid = ws + L.hid, *dA = ws + L.dA, *dB = ws + L.dB, *dC = ws + L.dC, *dqkv = ws + L.dqkv,
         *dh = ws + L.dh, *At = ws + L.At, *Xt = ws + L.Xt, *Wt = ws + L.Wt;
 
-  X2Train x2(c, L, ws, st, T);
-  const TrainPath path(*c);                              // (as the forward pass of this step)
-  const bool use_x2 = path.use_x2;
-  if (use_x2) {
-    TP(T_OTHER, x2.begin(false));
-    x2.batched = 8 * g.depth <= D3DP_WPREP_MAX;          // (the forward pass of this step left the weight operands in place)
-  }
+  std::optional<X2Train> x2s;
+  if (P.use_x2) x2s.emplace(c, L, P, ws, st);
+  X2Train* const x2 = P.use_x2 ? &*x2s : nullptr;
+  if (x2) TP(T_OTHER, x2->begin(false));
   // second stream for the weight-gradient products (see d3dp_ctx::aux)
   // (under the per-kernel profile everything runs on the caller's stream: a class's time must not contain a wait for CUs that a
   //  product on the second stream holds -- same arithmetic, test_training_step_stream_switches_change_no_bit)
-  const bool overlap = path.needs_aux && !c->prof;
+  const bool overlap = P.path.needs_aux && !c->prof;
   if (overlap && !c->aux) return d3dp_fail(D3DP_ESTATE, "d3dp_train_backward: the second stream was not created (d3dp_create makes it)");
   // Up to two weight-gradient products are in flight on c->aux, each with its own operand / partial-tile set (X2Train::use_set):
   // product k takes set k & 1 and the caller's stream waits for product k - 2 before the operand pass overwrites that set -- not
@@ -605,7 +463,7 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
   // every operand pass waits for the product before it (the first form of this overlap).
   bool pending[2] = {false, false};
   int n_wgrad = 0, cur_set = 0;
-  const int n_sets = c->train_overlap_sets;
+  const int n_sets = P.overlap_sets;
   auto wait_set = [&](int s) -> int {                    // the caller's stream waits for the product that last used set s
     if (!pending[s]) return 0;
     pending[s] = false;
@@ -614,7 +472,7 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
   auto join = [&]() -> int { int r = wait_set(0); return r ? r : wait_set(1); };
   Reducer red{ws + L.red, L.red_floats, 0, st};
   red.items.reserve(24 * (size_t)g.depth + 32);
-  const int lnrows = d3dp_train_ln_bwd_blocks(T);        // partial rows one LayerNorm-backward call leaves
+  const int lnrows = L.ln_rows;                          // partial rows one LayerNorm-backward call leaves
   // [dgamma | dbeta] partial rows of a LayerNorm with `calls` backward calls per step (the shared norms: one per depth), and
   // their two destinations; call i writes rows [i lnrows, (i + 1) lnrows)
   auto ln_part = [&](const float* dgamma, const float* dbeta, int calls) -> float* {
@@ -630,36 +488,38 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
   float* part_hn = ln_part(grads->head_norm_w, grads->head_norm_b, 1);
   if (red.rc) return d3dp_fail(D3DP_ESTATE, "d3dp_train_backward: partial-sum region too small");
   int sdy = -1;                                          // absmax slot of the dY the next wgrad / dgrad pair shares
-  // wgrad: dW[N, K] = dY[T, N]^T X[T, K]  (fp32 path: both operands transposed to [*, Tpad], zero padded)
+  // wgrad of Linear l = 4 blk + j: dW[N, K] = dY[T, N]^T X[T, K]  (fp32 path: both operands transposed to [*, Tpad], zero padded;
+  //  split-fp16 path: X's operand form was left by the forward pass of this step and X is not read)
   // (dbias: the Linear's bias gradient = column sums of dY, left as partial rows and summed at the end)
   // (pre_slot >= 0: the kernel that produced dY left its absmax there)
   // (mk / mk_axis: DropPath scales the operand pass still has to apply to dY's rows -- then dY is the UNSCALED gradient)
   // (gelu_pre: dY is d hidden, the Linear's dY is dY x gelu'(gelu_pre) and pre_slot holds the absmax of d hidden: split-fp16 path)
-  auto wgrad = [&](int l, const float* dY, int N, const float* X, int K, float* dW, float* dbias, int pre_slot = -1,
+  auto wgrad = [&](int blk, TrainLinearId j, const float* dY, const float* X, float* dW, float* dbias, int pre_slot = -1,
                    const float* mk = nullptr, int mk_axis = 0, const float* gelu_pre = nullptr) -> int {
+    const int N = P.lin[j].N, K = P.lin[j].K;
     int r;
-    if (use_x2) {
-      sdy = pre_slot >= 0 ? pre_slot : x2.slot_for(dY, (size_t)T * N);
+    if (x2) {
+      sdy = pre_slot >= 0 ? pre_slot : x2->slot_for(dY, (size_t)T * N);
       if (sdy < 0) return -1;
-      float* bp = red.take((size_t)X2Train::kBiasRows * N);
+      float* bp = red.take((size_t)L.bias_rows * N);
       int brows = 0;
       if (!bp) return -1;
-      // merged (one launch per block): l = 4 block + {3, 2, 1, 0} arrive in this order, the set changes with the block and the
+      // merged (one launch per block): fc2, fc1, proj, qkv arrive in this order, the set changes with the block and the
       // products are launched behind the last dY; else every weight gradient is a product, and takes a set, of its own
-      const bool first = !x2.merged || (l & 3) == 3, last = !x2.merged || (l & 3) == 0;
+      const bool first = !P.merged || j == kFc2, last = !P.merged || j == kQkv;
       if (first) {
         cur_set = overlap ? (n_wgrad++ % n_sets) : 0;
         if ((r = wait_set(cur_set))) return r;           // the product that last used this set is done with its operands and partial tiles
-        x2.use_set(cur_set);
+        x2->use_set(cur_set);
       }
-      if ((r = x2.prep_dy(dY, sdy, bp, &brows, T, N, K, mk, mk_axis, F, J, gelu_pre))) return r;
+      if ((r = x2->prep_dy(j, dY, sdy, bp, &brows, mk, mk_axis, F, J, gelu_pre))) return r;
       red.add(bp, dbias, N, brows, N);
       if (last && overlap) {
         if (hipEventRecord(c->ev_fork, st) != hipSuccess || hipStreamWaitEvent(c->aux, c->ev_fork, 0) != hipSuccess) return -3;
-        x2.st_w = c->aux;
+        x2->st_w = c->aux;
       }
-      if ((r = x2.wgrad(l, dY, sdy, X, dW, T, N, K))) return r;        // (merged: recorded)
-      if (last && x2.merged && (r = x2.flush_wgrads())) return r;
+      if ((r = x2->wgrad(blk, j, sdy, dW))) return r;        // (merged: recorded)
+      if (last && P.merged && (r = x2->flush_wgrads())) return r;
       if (last && overlap) {
         if (hipEventRecord(c->ev_done[cur_set], c->aux) != hipSuccess) return -3;
         pending[cur_set] = true;
@@ -681,28 +541,30 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
     // are bit-reproducible too)
     return d3dp_launch_linear_f32_splitk(At, Xt, dW, N, K, Tp, st, ws + L.part, L.part_floats);
   };
-  // dgrad: dX[T, K] = dY[T, N] W[N, K]   (W transposed to [K, N])
-  auto dgrad = [&](int l, const float* dY, int N, const float* W, int K, float* dX, unsigned* out_amax = nullptr) -> int {
-    if (use_x2) return sdy < 0 ? -1 : x2.dgrad(l, dY, sdy, W, dX, T, N, K, out_amax);  // (always right behind the wgrad of the same dY)
+  // dgrad of Linear l = 4 blk + j: dX[T, K] = dY[T, N] W[N, K]   (fp32 path: W transposed to [K, N]; no bias: a null one is zeros)
+  auto dgrad = [&](int blk, TrainLinearId j, const float* dY, float* dX, unsigned* out_amax = nullptr) -> int {
+    const BlockDev& w = (blk & 1) ? c->tte[blk >> 1] : c->ste[blk >> 1];
+    const int N = P.lin[j].N, K = P.lin[j].K;
+    if (x2) return sdy < 0 ? -1 : x2->dgrad(blk, j, sdy, lin_w(w, j), dX, out_amax);  // (always right behind the wgrad of the same dY)
     int r;
-    { Scope ps_(pc, T_OPERAND, st); if ((r = d3dp_train_transpose_pad(W, Wt, N, K, N, st))) return r; }
+    { Scope ps_(pc, T_OPERAND, st); if ((r = d3dp_train_transpose_pad(lin_w(w, j), Wt, N, K, N, st))) return r; }
     Scope ps_(pc, T_LINEAR, st);
-    return lin32(dY, Wt, zb, dX, T, K, N, st);
+    return lin32(dY, Wt, nullptr, dX, T, K, N, st);
   };
   // a slot for the absmax the producer of the next dY leaves (split-fp16 path only)
   auto fresh = [&](int& slot) -> unsigned* {
-    slot = use_x2 ? x2.take() : -1;
-    return slot >= 0 ? x2.amax() + slot : nullptr;
+    slot = x2 ? x2->take() : -1;
+    return slot >= 0 ? x2->amax() + slot : nullptr;
   };
 #define D3DP_FRESH(ps, pa)                                                                              \
   int ps = -1;                                                                                          \
   unsigned* pa = fresh(ps);                                                                             \
-  if (use_x2 && ps < 0) return d3dp_fail(D3DP_ESTATE, "d3dp_train_backward: out of operand slots");
+  if (x2 && ps < 0) return d3dp_fail(D3DP_ESTATE, "d3dp_train_backward: out of operand slots");
 
   // ---- head: Linear(C, 3) backward, then its LayerNorm and the last block's shared norm in one pass --------------
   const int nblk = 2 * g.depth;
   {
-    float* hp = red.take((size_t)512 * (3 * C + 4));
+    float* hp = red.take((size_t)L.head_rows * (3 * C + 4));
     int rows = 0;
     if (!hp) return d3dp_fail(D3DP_ESTATE, "d3dp_train_backward: partial-sum region too small");
     TP(T_OTHER, d3dp_train_head_bwd(grad_out, ws + L.z, c->hw, dC, hp, &rows, T, C, st));   // (z: left by the forward pass)
@@ -714,7 +576,7 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
   const float* dy_mask = nullptr;                        // ... and the DropPath scales its operand pass still has to apply
   int ps_next = -1;
   // (the DropPath-scaled gradient is not stored where the operand pass can apply the scales itself: only its absmax is)
-  const bool mip2 = use_x2 && x2.mask_in_prep_applies(C, Hd), mip1 = use_x2 && x2.mask_in_prep_applies(C, C);
+  const bool mip2 = P.mip2, mip1 = P.mip1, gip = P.gip;
   {
     const int lb = nblk - 1, lk = lb & 1;
     const float* S = ws + L.saved0 + (size_t)lb * L.saved_stride;
@@ -734,18 +596,17 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
     float* S = ws + L.saved0 + (size_t)blk * L.saved_stride;
     // here: dB = d x_out(blk), dy = its DropPath-scaled form, absmax in slot ps_next
     // ---- MLP branch ----
-    if (!use_x2) TP(T_OPERAND, d3dp_train_gelu_fwd(S + L.o_hpre, hid, (size_t)T * Hd, nullptr, st));   // (x2: wgrad reads the forward pass' operand)
-    LAUNCH_TRY(wgrad(4 * blk + 3, dy, C, hid, Hd, G(gw.fc2_w), G(gw.fc2_b), ps_next, dy_mask, kind));
+    if (!x2) TP(T_OPERAND, d3dp_train_gelu_fwd(S + L.o_hpre, hid, (size_t)T * Hd, nullptr, st));   // (x2: wgrad reads the forward pass' operand)
+    LAUNCH_TRY(wgrad(blk, kFc2, dy, hid, G(gw.fc2_w), G(gw.fc2_b), ps_next, dy_mask, kind));
     {
-      // d hidden = dy W_fc2; d h_pre = d hidden x gelu'(h_pre).  Split-fp16 path: the product is formed by the operand pass of
-      // the fc1 gradients (the only reader of d h_pre), from the absmax of d hidden the fc2 dgrad's epilogue leaves
-      const bool gip = use_x2 && c->train_gelu_in_prep && x2.gelu_in_prep_applies(Hd, C);
+      // d hidden = dy W_fc2; d h_pre = d hidden x gelu'(h_pre).  Split-fp16 path (TrainPlan::gip): the product is formed by the operand
+      // pass of the fc1 gradients (the only reader of d h_pre), from the absmax of d hidden the fc2 dgrad's epilogue leaves
       D3DP_FRESH(ps, pa)
-      LAUNCH_TRY(dgrad(4 * blk + 3, dy, C, (const float*)w.fc2_w, Hd, dh, gip ? pa : nullptr));                         // d hidden
+      LAUNCH_TRY(dgrad(blk, kFc2, dy, dh, gip ? pa : nullptr));                                                         // d hidden
       if (!gip) TP(T_OPERAND, d3dp_train_gelu_bwd(dh, S + L.o_hpre, dh, (size_t)T * Hd, pa, st));             // d h_pre
-      if (!use_x2) TP(T_LN_FWD, d3dp_train_ln_pos(S + L.o_xmid, w.n2w, w.n2b, g.eps_block, nullptr, F, J, xn, T, C, st));   // xn2
-      LAUNCH_TRY(wgrad(4 * blk + 2, dh, Hd, xn, C, G(gw.fc1_w), G(gw.fc1_b), ps, nullptr, 0, gip ? S + L.o_hpre : nullptr));
-      LAUNCH_TRY(dgrad(4 * blk + 2, dh, Hd, (const float*)w.fc1_w, C, dC));                                             // d xn2
+      if (!x2) TP(T_LN_FWD, d3dp_train_ln_pos(S + L.o_xmid, w.n2w, w.n2b, g.eps_block, nullptr, F, J, xn, T, C, st));   // xn2
+      LAUNCH_TRY(wgrad(blk, kFc1, dh, xn, G(gw.fc1_w), G(gw.fc1_b), ps, nullptr, 0, gip ? S + L.o_hpre : nullptr));
+      LAUNCH_TRY(dgrad(blk, kFc1, dh, dC));                                                                             // d xn2
     }
     // norm2 backward + the residual: dA = d x_mid; its DropPath-scaled form (the proj dY) over dC
     {
@@ -757,30 +618,30 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
                                    (mk && !mip1) ? dC : nullptr, pa, pn, nullptr, T, C, st));
       dy = (mk && !mip1) ? dC : dA;
       // ---- attention branch ----
-      LAUNCH_TRY(wgrad(4 * blk + 1, dy, C, S + L.o_att, C, G(gw.proj_w), G(gw.proj_b), ps, mip1 ? mk : nullptr, kind));
+      LAUNCH_TRY(wgrad(blk, kProj, dy, S + L.o_att, G(gw.proj_w), G(gw.proj_b), ps, mip1 ? mk : nullptr, kind));
     }
     int ps_dqkv = -1;
-    if (path.attn_x2(kind)) {
+    if (P.path.attn_x2(kind)) {
       // split-fp16 operands: the proj dgrad leaves d att's absmax, the attention backward that of dqkv
       D3DP_FRESH(pdo, pado)
       D3DP_FRESH(pq, paq)
-      LAUNCH_TRY(dgrad(4 * blk + 1, dy, C, (const float*)w.proj_w, C, dB, pado));                                       // d att
+      LAUNCH_TRY(dgrad(blk, kProj, dy, dB, pado));                                                                      // d att
       // (the per-kernel profile times the two passes apart; otherwise one call launches both)
       for (int part = pc ? 1 : 0; part <= (pc ? 2 : 0); ++part)
         TP(part == 2 ? (kind ? T_ATTN_BKV_T : T_ATTN_BKV_S) : (kind ? T_ATTN_BQ_T : T_ATTN_BQ_S),
            d3dp_train_attn_x2_bwd(S + L.o_qkv, S + L.o_att, dB, dqkv, ws + L.stats_x2 + (size_t)blk * L.stats_x2_stride,
                                   kind ? B * J : B * F, kind ? temporal_map(F, J) : spatial_map(F, J), C, g.heads,
-                                  x2.amax() + X2Train::kQkvSlot0 + blk, pado, paq, st, part));
+                                  x2->qkv_amax(blk), pado, paq, st, part));
       ps_dqkv = pq;
     } else {
-      LAUNCH_TRY(dgrad(4 * blk + 1, dy, C, (const float*)w.proj_w, C, dB));                                             // d att
+      LAUNCH_TRY(dgrad(blk, kProj, dy, dB));                                                                            // d att
       // (fp32 kernels: both passes behind one launcher -- timed together under the pass-Q class)
       TP(kind ? T_ATTN_BQ_T : T_ATTN_BQ_S, d3dp_train_attn_bwd(S + L.o_qkv, S + L.o_att, dB, dqkv, ws + L.stats, kind ? B * J : B * F,
                                                              kind ? temporal_map(F, J) : spatial_map(F, J), C, g.heads, st));
     }
-    if (!use_x2) TP(T_LN_FWD, d3dp_train_ln_pos(S + L.o_xin, w.n1w, w.n1b, g.eps_block, nullptr, F, J, xn, T, C, st));    // xn1
-    LAUNCH_TRY(wgrad(4 * blk, dqkv, 3 * C, xn, C, G(gw.qkv_w), G(gw.qkv_b), ps_dqkv));
-    LAUNCH_TRY(dgrad(4 * blk, dqkv, 3 * C, (const float*)w.qkv_w, C, dC));                                          // d xn1
+    if (!x2) TP(T_LN_FWD, d3dp_train_ln_pos(S + L.o_xin, w.n1w, w.n1b, g.eps_block, nullptr, F, J, xn, T, C, st));    // xn1
+    LAUNCH_TRY(wgrad(blk, kQkv, dqkv, xn, G(gw.qkv_w), G(gw.qkv_b), ps_dqkv));
+    LAUNCH_TRY(dgrad(blk, kQkv, dqkv, dC));                                                                         // d xn1
     float* pn1 = ln_part(gw.norm1_w, gw.norm1_b, 1);
     if (!pn1) return d3dp_fail(D3DP_ESTATE, "d3dp_train_backward: partial-sum region too small");
     if (blk > 0) {
@@ -810,19 +671,19 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
   {
     Scope ps_(pc, T_OTHER, st);
     float* ep = red.take((size_t)D3DP_EMBED_BWD_ROWS * 5 * C);
-    float* bp = red.take((size_t)512 * C);
-    float* sp = red.take((size_t)kGroupSlices * J * C);
-    float* tp = red.take((size_t)kGroupSlices * B * C);
+    float* bp = red.take((size_t)L.embed_bias_rows * C);
+    float* sp = red.take((size_t)L.group_slices * J * C);
+    float* tp = red.take((size_t)L.group_slices * B * C);
     int rows = 0;
     if (!ep || !bp || !sp || !tp) return d3dp_fail(D3DP_ESTATE, "d3dp_train_backward: partial-sum region too small");
     LAUNCH_TRY(d3dp_train_embed_bwd(dB, x2d, x3d, ep, T, C, st));
     red.add(ep, G(grads->embed_w), 5 * (size_t)C, D3DP_EMBED_BWD_ROWS, 5 * (size_t)C);
-    LAUNCH_TRY(d3dp_train_colsum(dB, bp, &rows, 512, T, C, st));
+    LAUNCH_TRY(d3dp_train_colsum(dB, bp, &rows, L.embed_bias_rows, T, C, st));
     red.add(bp, G(grads->embed_b), C, rows, C);
-    LAUNCH_TRY(d3dp_train_groupsum(dB, sp, T, C, 0, F, J, kGroupSlices, st));
-    red.add(sp, G(grads->spatial_pos), (size_t)J * C, kGroupSlices, (size_t)J * C);
-    LAUNCH_TRY(d3dp_train_groupsum(dB, tp, T, C, 2, F, J, kGroupSlices, st));
-    red.add(tp, ws + L.dtemb, (size_t)B * C, kGroupSlices, (size_t)B * C);
+    LAUNCH_TRY(d3dp_train_groupsum(dB, sp, T, C, 0, F, J, L.group_slices, st));
+    red.add(sp, G(grads->spatial_pos), (size_t)J * C, L.group_slices, (size_t)J * C);
+    LAUNCH_TRY(d3dp_train_groupsum(dB, tp, T, C, 2, F, J, L.group_slices, st));
+    red.add(tp, ws + L.dtemb, (size_t)B * C, L.group_slices, (size_t)B * C);
     red.flush();                                          // (dtemb feeds the time MLP's backward below)
   }
   if (red.rc) return d3dp_fail(D3DP_EHIP, "d3dp_train_backward: the gradient reduction failed");

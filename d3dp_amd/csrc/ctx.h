@@ -1,6 +1,7 @@
 // Host-side types shared by the C-ABI translation units (capi.hip, capi_weights.hip, capi_denoise.hip, capi_ops.hip,
 // capi_train.hip): the context -- the plan of its creation (ctx_plan.h), what d3dp_set_weights and the calls change later and the
 // predicates derived from both --, a block's device weights, the profile scope and the token maps of the two attention axes.
+// (The route and the workspace layout of a training step: train_plan.h, which kernels.h brings in.)
 // Internal: nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -61,10 +62,6 @@ inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
 // Which attention kernel family a context launches on an axis (0 = spatial, 1 = temporal): attn_route(), capi_denoise.hip
 enum class AttnRoute { X2, FAST_SPATIAL, FAST_WHOLE_SEQ, F32_TEMPORAL, ROWS };
-// The head dims the training step's attention kernels take (train_attn.hip): mfma_head_dim's, and 24 / 40 / 48 / 56 padded to 32 / 64
-// inside its kernels -- the head dims of channels in {192, 320, 384, 448} with the model's 8 heads, reached under
-// D3DP_TRAIN_IMPL=f16x2 only (plan_context)
-inline bool train_attn_head_dim(int hd) { return mfma_head_dim(hd) || hd == 24 || hd == 40 || hd == 48 || hd == 56; }
 AttnRoute attn_route(int mode, int exact_impl, int hd, int frames, int joints, bool long_rows, int axis);
 
 // The members d3dp_create decides are the base (CtxPlan); the ones below it change later: d3dp_set_weights (exact_impl, impl_fallback,
@@ -247,24 +244,3 @@ struct Scope {
 // (sp: rows per (clip, hypothesis) sequence in the token buffers, >= F J; d3dp_ctx::seq_pitch)
 inline SeqMap spatial_map(int F, int J, int sp = 0) { return sp > F * J ? SeqMap{J, F, sp, J, 1} : SeqMap{J, 1, J, 0, 1}; }
 inline SeqMap temporal_map(int F, int J, int sp = 0) { return SeqMap{F, J, sp > F * J ? sp : F * J, 1, J}; }
-
-// Which path a TRAIN context's step takes, computed once per call from the switches read at d3dp_create.
-//   use_x2     the Linears on split-fp16 operands (train_linears_split); else the fp32 matrix cores.  CtxPlan::train_x2: the
-//              instantiated widths unless D3DP_TRAIN_IMPL=f32, and channels in {192, 320, 384, 448} under D3DP_TRAIN_IMPL=f16x2
-//   attn_x2(a) axis a's attention on the split-fp16 kernels of train_attn.hip: they need the split Linears' device-side scales
-//              and a head dim those kernels take (train_attn_head_dim: 64, 32, 16 -- `-cs` 512 / 256 / 128 with the model's 8 heads --
-//              and 56, 48, 40, 24 -- `-cs` 448 / 384 / 320 / 192 -- padded to 64 / 32 inside the kernels); clips of up to 1024 frames
-//              (beyond 256 their keys / queries pass through LDS in chunks).  Head dim 8, the cross-check switches and every
-//              context on the fp32 path stay on the fp32 kernels of train.hip (<= 256 frames)
-//   needs_aux  the backward pass forks its weight-gradient products onto the context's second stream (made by d3dp_create)
-struct TrainPath {
-  bool use_x2, attn_x2_t, attn_x2_s, needs_aux;
-  bool attn_x2(int axis) const { return axis == 1 ? attn_x2_t : attn_x2_s; }
-  explicit TrainPath(const d3dp_ctx& c) {
-    const d3dp_cfg& g = c.cfg;
-    use_x2 = train_linears_split(c, g);
-    attn_x2_t = use_x2 && c.train_attn_x2 > 0 && train_attn_head_dim(g.channels / g.heads) && g.frames <= 1024;
-    attn_x2_s = attn_x2_t && c.train_attn_x2 > 1;      // the spatial axis too
-    needs_aux = c.train() && use_x2 && c.train_overlap;
-  }
-};

@@ -135,7 +135,7 @@ inline bool fast_optin_shape(const d3dp_cfg& g) {
   const int hd = g.channels / g.heads;
   return optin_width(g.channels) && (hd == 24 || hd == 32 || hd == 40 || hd == 48 || hd == 56 || hd == 64) && g.hidden == 2 * g.channels;
 }
-// The training Linears run on split-fp16 operands (X2Train, capi_train.hip); else on the fp32 matrix cores: TrainPath::use_x2
+// The training Linears run on split-fp16 operands (X2Train, capi_train.hip); else on the fp32 matrix cores: TrainPath::use_x2 (train_plan.h)
 inline bool train_linears_split(const CtxPlan& p, const d3dp_cfg& g) { return p.train_x2 && g.channels % 32 == 0 && g.hidden % 32 == 0; }
 
 // The route of a context of shape g under the switches e, in a library with (variants_built) or without the experiment kernels of

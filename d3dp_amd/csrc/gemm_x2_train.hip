@@ -1010,7 +1010,7 @@ int d3dp_launch_gelu_rowprep(const float* src, void* drow, int R, int Rpad, int 
 
 // out_z[N, K] = sum over the token rows of chunk z of A2[t][n] W2[t][k], x dynA x dynW: Tp = Z NKz 32 rows per operand (rows
 // beyond the real ones zero), N % 256 == 0, K % 128 == 0 (d3dp_tn_applies)
-bool d3dp_tn_applies(int N, int K) { return N % XBM == 0 && K % XBN == 0; }
+static_assert(XBM == D3DP_TN_TILE_N && XBN == D3DP_TN_TILE_K, "train_plan.h: the tile d3dp_tn_applies asks whole multiples of");
 // n products over the same Tp token rows in one launch: out_p,z[N_p, K_p] (z = 0 .. Z - 1, N_p K_p floats apart)
 int d3dp_launch_linear_f16x2_tn_many(const D3dpTnProduct* prods, int n, int Tp, int Z, hipStream_t st, int passes) {
   if (n < 1 || n > D3DP_TN_MAX || Z < 1 || Tp % (XBK * Z) != 0 || (passes != 1 && passes != 3)) return -1;

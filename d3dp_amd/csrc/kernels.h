@@ -5,6 +5,8 @@
 
 #include <mutex>
 
+#include "train_plan.h"   // the training kernels' capacities (D3DP_DYPREP_ROWS ... D3DP_TN_MAX), d3dp_tn_applies, the statistics sizes
+
 // "Once per DEVICE" cache of a launcher's set-up (the > 64 KiB dynamic-LDS opt-in of a kernel, which HIP records per device,
 // or a number derived from the device's CU count): one process may drive several devices -- nn.DataParallel callers,
 // one thread per device (reference main.py:242-248) -- so neither a process-wide `static bool` nor an unlocked one is right.
@@ -124,12 +126,10 @@ void d3dp_launch_split2_t_dyn(const float* src, void* dst, int R, int C, int Rpa
                               hipStream_t st);
 // src [R][C] -> row form [R][2 C], transposed form [C][2 Rpad] and (colpart != null) its column sums as D3DP_DYPREP_ROWS
 // partial rows of C floats (every row written; summed by d3dp_train_reduce_many) in one pass
-constexpr int D3DP_DYPREP_ROWS = 96;
 int d3dp_launch_dyprep(const float* src, void* drow, void* dcol, float* colpart, int R, int C, int Rpad, const unsigned* amax,
                        float* unscale, hipStream_t st);
 // the row form alone as a streaming pass: src [R][C] -> drow [Rpad][2 C] (rows R .. Rpad - 1 zero) + optional column sums as *rows
 // (<= D3DP_ROWPREP_ROWS) partial rows of C floats; C % 32 == 0, C <= 1536
-constexpr int D3DP_ROWPREP_ROWS = 512;
 // (mask: optional per-sample scales applied to the rows first -- sample = r / J (axis 0) or (r / (F J)) J + r % J (axis 1))
 // (gelu_pre: optional [R][C]; the operand is src x gelu'(gelu_pre) and amax[0] holds the absmax of SRC, see rowprep_kernel)
 int d3dp_launch_rowprep(const float* src, void* drow, float* colpart, int* rows, int R, int Rpad, int C, const unsigned* amax,
@@ -141,11 +141,9 @@ int d3dp_launch_rowprep_ln(const float* src, const float* w, const float* b, flo
                            const unsigned* amax, float* unscale, hipStream_t st);
 // wgrad straight from the ROW forms (gemm_f16x2_tn_kernel): out_z[N, K] = sum_{t in chunk z} A2[t][n] W2[t][k] x dynA x dynW,
 // Tp = Z NKz 32 rows per operand (rows beyond the real ones zero).  d3dp_tn_applies: N % 256 == 0 and K % 128 == 0.
-bool d3dp_tn_applies(int N, int K);
 int d3dp_launch_linear_f16x2_tn(const void* A2, const void* W2, const float* dynA, const float* dynW, float* out, int N, int K,
                                 int Tp, int Z, hipStream_t st, int passes = 3);
 // ... several such products over the same Tp rows in one launch (the weight gradients of a block): one merged tile list, one Z
-constexpr int D3DP_TN_MAX = 4;
 struct D3dpTnProduct {
   const void* A2; const void* W2;                      // [Tp][2 N] and [Tp][2 K] row forms
   const float* dynA; const float* dynW;
@@ -159,7 +157,6 @@ struct D3dpSumTable { const float* part[D3DP_TN_MAX]; float* out[D3DP_TN_MAX]; s
 void d3dp_launch_sum_partials_many(const D3dpSumTable& tb, hipStream_t st);   // out_p[i] = sum_z part_p[z n_p + i], z ascending
 // the training step's weight operands in three launches: absmax -> slot, rows form [N][2 K] at rows_base + 2 off
 // halves, transposed form [K][2 N] at cols_base + 2 off halves, unscale[slot] = 1 / scale
-constexpr int D3DP_WPREP_MAX = 64;
 struct D3dpWPrepItem { const float* w; int N, K, slot, pad; size_t off; };
 struct D3dpWPrepTable { D3dpWPrepItem it[D3DP_WPREP_MAX]; int n; };
 int d3dp_launch_wprep(const D3dpWPrepTable& tb, void* rows_base, void* cols_base, unsigned* amax, float* unscale, hipStream_t st);
@@ -309,8 +306,6 @@ int d3dp_train_ln_pos(const float* x, const float* w, const float* b, float eps,
 //   dxm (optional) = mask[sample] dx, amax (optional) its absmax -- dy and dxm may alias.
 // part_b / part_a: d3dp_train_ln_bwd_blocks(T) rows of [dgamma | dbeta] (2 C floats) per LayerNorm, to be summed in order by
 // d3dp_train_reduce_many (no float atomics anywhere in the backward pass: bit-reproducible gradients).
-constexpr int D3DP_LN_BWD_BLOCKS = 512;
-int d3dp_train_ln_bwd_blocks(int T);
 int d3dp_train_ln_bwd(const float* dy, const float* xb, const float* wb, float eps_b, const float* dres, float* g_out,
                       const float* xa, const float* wa, float eps_a, float* dx, const float* mask, int axis, int F, int J,
                       float* dxm, unsigned* amax, float* part_b, float* part_a, int T, int C, hipStream_t st);
@@ -331,16 +326,13 @@ int d3dp_train_zero_many(const D3dpZeroTable& tb, hipStream_t st);
 // grouped row sums (mode 0: per joint, 1: per frame, 2: per batch element) as `slices` partial tables of groups x C floats
 int d3dp_train_groupsum(const float* in, float* out, int T, int C, int mode, int F, int J, int slices, hipStream_t st);
 int d3dp_train_transpose_pad(const float* in, float* out, int R, int C, int Rpad, hipStream_t st);
-size_t d3dp_train_attn_stats_bytes(int n_seq, int n_tok, int heads);
 int d3dp_train_attn_bwd(const float* qkv, const float* o, const float* dout, float* dqkv, void* stats, int n_seq,
                         SeqMap map, int C, int heads, hipStream_t st);
-constexpr int D3DP_EMBED_BWD_ROWS = 64;
 // ---- train_attn.hip: the training step's attention on split-fp16 operands (head dim 64, 32 or 16, and 24 / 40 / 48 / 56 padded to 32 / 64
 // inside the kernels: -2 for any other; <= 1024 tokens per sequence) ----
 // stats: d3dp_train_attn_x2_stats_bytes per attention (the forward leaves the log-sum-exp of every query for the backward pass);
 // amax_qkv / amax_do: absmax slots of the whole qkv tensor / of dout (left by the Linears that produced them); amax_out
 // (optional): absmax slot of the result.
-size_t d3dp_train_attn_x2_stats_bytes(int n_seq, int n_tok, int heads);
 int d3dp_train_attn_x2_fwd(const float* qkv, float* out, void* stats, int n_seq, SeqMap map, int C, int heads,
                            const unsigned* amax_qkv, unsigned* amax_out, hipStream_t st, void* op = nullptr, int T = 0, int Tp = 0,
                            float* op_unscale = nullptr);

@@ -946,7 +946,7 @@ int d3dp_train_ln_pos(const float* x, const float* w, const float* b, float eps,
   return 0;
 }
 // (D3DP_LN_BWD_BLOCKS workgroups: two per CU; every workgroup ends with one partial row per LayerNorm)
-int d3dp_train_ln_bwd_blocks(int T) { return (T + 3) / 4 < D3DP_LN_BWD_BLOCKS ? (T + 3) / 4 : D3DP_LN_BWD_BLOCKS; }
+// (d3dp_train_ln_bwd_blocks(T), train_plan.h: the workgroups of a call over T tokens)
 int d3dp_train_ln_bwd(const float* dy, const float* xb, const float* wb, float eps_b, const float* dres, float* g_out,
                       const float* xa, const float* wa, float eps_a, float* dx, const float* mask, int axis, int F, int J,
                       float* dxm, unsigned* amax, float* part_b, float* part_a, int T, int C, hipStream_t st) {
@@ -1012,7 +1012,7 @@ int d3dp_train_transpose_pad(const float* in, float* out, int R, int C, int Rpad
   hipLaunchKernelGGL(transpose_pad_kernel, dim3((Rpad + 31) / 32, (C + 31) / 32), dim3(256), 0, st, in, out, R, C, Rpad);
   return 0;
 }
-size_t d3dp_train_attn_stats_bytes(int n_seq, int n_tok, int heads) { return (size_t)n_seq * heads * n_tok * sizeof(AttnStats); }
+static_assert(sizeof(AttnStats) == D3DP_TRAIN_ATTN_STAT_BYTES, "train_plan.h: d3dp_train_attn_stats_bytes");
 
 // ------------------------------------------------------------------------------------------------
 // Attention backward on the fp32 matrix cores (v_mfma_f32_16x16x4_f32: exact fp32 fma chains), head dim 64, sequences of

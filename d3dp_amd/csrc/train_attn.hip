@@ -681,7 +681,7 @@ int ta_dispatch(int which, const float* qkv, const float* o, const float* dout, 
   const int n = map.n_tok;
   if (heads < 1 || C % heads != 0 || C % 4 != 0 || n < 1 || n > 1024 || !amax_qkv || !stats) return -2;
   if (po.op && (po.Tp < po.T || !po.unscale || C % 32 != 0)) return -1;
-  switch (C / heads) {                                 // the head dims these kernels take (ctx.h mfma_head_dim, train_attn_head_dim)
+  switch (C / heads) {                                 // the head dims these kernels take (ctx_plan.h mfma_head_dim, train_plan.h train_attn_head_dim)
     case 64: { TA_LENGTHS(64) }
     case 32: { TA_LENGTHS(32) }
     case 16: { TA_LENGTHS(16) }
@@ -716,7 +716,7 @@ int d3dp_train_attn_x2_padded(int which, const float* qkv, const float* o, const
   return -2;
 }
 #else
-size_t d3dp_train_attn_x2_stats_bytes(int n_seq, int n_tok, int heads) { return (size_t)n_seq * heads * n_tok * sizeof(TAStat); }
+static_assert(sizeof(TAStat) == D3DP_TRAIN_ATTN_X2_STAT_BYTES, "train_plan.h: d3dp_train_attn_x2_stats_bytes");
 
 // out [T, C] = softmax(q k^T HD^-0.5) v per (sequence, head), HD = C / heads in {64, 32, 16} or, with the head padded inside the kernels,
 // {24, 40, 48, 56} (-2 for any other; the padded forms write no operand rows: -1 if `op` is asked of them); stats: n_seq x heads x n_tok (L, D) pairs for the backward pass;

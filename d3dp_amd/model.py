@@ -535,7 +535,7 @@ class MixSTE2(nn.Module):
         # D3DP_TRAIN_IMPL=f16x2 (capi.hip d3dp_create): the split-fp16 step at channels 192 / 320 / 384 / 448, heads padded to 32 / 64
         widths = (not inst and os.environ.get("D3DP_TRAIN_IMPL") == "f16x2" and self.embed_dim in (192, 320, 384, 448)
                   and hd % 8 == 0 and hd <= 64 and self.hidden >= 64 and self.hidden % 64 == 0)
-        x2_ok = hd in ((64, 32, 16, 56, 48, 40, 24) if widths else (64, 32, 16)) and self.num_frame <= 1024   # (ctx.h TrainPath)
+        x2_ok = hd in ((64, 32, 16, 56, 48, 40, 24) if widths else (64, 32, 16)) and self.num_frame <= 1024   # (train_plan.h plan_train_path)
         if ta == "f32" or not x2_ok:
             attn = "fp32 attention (fp32 MFMA: temporal forward, backward of both axes; spatial forward on the VALU)"
         elif ta == "x2t":

@@ -1,7 +1,7 @@
 """The caller's workspaces (include/d3dp_hip.h d3dp_workspace_bytes / d3dp_train_workspace_bytes): a call runs in exactly the
 byte count its size query returns, writes nothing outside it, computes what it computes in a roomier one, and refuses a
 smaller one before it writes anything.  The size query and the carve come from one layout each (capi_denoise.hip InferLayout,
-capi_train.hip TrainLayout); the shapes are the smallest that reach each branch of the two.
+train_plan.h TrainLayout); the shapes are the smallest that reach each branch of the two.
 
 Every workspace lies inside a larger torch byte buffer with a 4,096-byte guard of a fixed pattern on each side: an overrun
 changes bytes of an allocation the test owns.

@@ -66,11 +66,11 @@ def r16(x: torch.Tensor) -> torch.Tensor:
 
 
 def x2_linears() -> Tuple[str, ...]:
-    """The weights d3dp_train_forward hands to X2Train::forward, read from capi_train.hip: the arguments `(const float*)w.NAME_w`
-    of its `lin(...)` calls.  (The embedding, the time MLP and the head have launchers of their own there.)"""
+    """The Linears d3dp_train_forward hands to X2Train::forward, read from capi_train.hip: the TrainLinearId `kName` its
+    `lin(blk, kName, ...)` calls name.  (The embedding, the time MLP and the head have launchers of their own there.)"""
     src = open(os.path.join(REPO, "d3dp_amd", "csrc", "capi_train.hip")).read()
     fwd = src[src.index("int d3dp_train_forward("):src.index("int d3dp_train_backward(")]
-    names = sorted(set(re.findall(r"lin\(4 \* blk[^;]*?\(const float\*\)w\.(\w+)_w", fwd)))
+    names = sorted(set(n.lower() for n in re.findall(r"\blin\(blk, k(\w+),", fwd)))
     for other in ("d3dp_train_time_mlp(", "d3dp_launch_embed_ln(", "d3dp_train_head_linear("):
         assert other in fwd, other
     return tuple(names)

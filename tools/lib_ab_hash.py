@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """What one build of the library computes on a table of tiny contexts, as text: per entry the two workspace sizes, the sha256
-of the d3dp_denoise output or of every gradient of one training step.  The library is bit-deterministic, so two builds that
+of the d3dp_denoise output or of every gradient of one training step, and for a training step the launches per profile class of one
+more, profiled, step (d3dp_profile_read).  The library is bit-deterministic, so two builds that
 compute the same thing print the same lines: `D3DP_LIB=a.so python tools/lib_ab_hash.py > a.txt`, the same for b.so, `diff`.
 An entry with environment switches runs in a fresh child process (`--only NAME`: that entry alone, in this process; the form
-to put behind `rocprofv3 --kernel-trace --stats --`): d3dp_create reads the switches once.
+to put behind `rocprofv3 --kernel-trace --stats --`): d3dp_create reads the switches once.  `--match TEXT`: the entries whose
+name contains TEXT.
 
 RawCtx, a context over seeded random weights straight on the C ABI, at any (C, F, J), also serves tests/test_hip_workspace.py."""
 import ctypes as C
@@ -125,6 +127,14 @@ for key, val in [("D3DP_EXACT_IMPL", "bf16x3"), ("D3DP_EXACT_IMPL", "f32"), ("D3
     TABLE[f"exact_c512_{key[5:].lower()}_{val}"] = dict(TABLE["exact_c512"], env={key: val})
 for key, val in [("D3DP_TRAIN_IMPL", "f32"), ("D3DP_TRAIN_ATTN", "f32"), ("D3DP_TRAIN_ATTN", "x2t"), ("D3DP_TRAIN_OVERLAP", "0")]:
     TABLE[f"train_c512_{key[5:].lower()}_{val}"] = dict(TABLE["train_c512"], env={key: val})
+# the smallest training shapes that reach each branch of the step's plan (csrc/train_plan.h)
+TABLE["train_c128"] = dict(TABLE["train_c64"], C=128)                    # transposed-operand weight gradients (fc1 alone is TN)
+TABLE["train_c96"] = dict(TABLE["train_c64"], C=96)                      # the fp32 path at a run-time width
+TABLE["train_c384_f16x2"] = dict(TABLE["train_c64"], C=384, env={"D3DP_TRAIN_IMPL": "f16x2"})   # the mixed case: fc1 alone is TN
+TABLE["train_c256_dep9"] = dict(TABLE["train_c256"], depth=9)            # more than 64 Linears: every weight prepared where it is used
+TABLE["train_c512_tail"] = dict(TABLE["train_c512"], F=159, J=17)        # T = 21 x 256 + 30: qkv's remainder rows as 16 x 64 blocks
+for key, val in [("D3DP_TRAIN_TAIL", "split"), ("D3DP_TRAIN_WGRAD", "each"), ("D3DP_TRAIN_GELU", "pass"), ("D3DP_TRAIN_LN_OPERAND", "pass")]:
+    TABLE[f"train_c512_tail_{key[11:].lower()}_{val}"] = dict(TABLE["train_c512_tail"], env={key: val}, variants=True)
 
 
 def sha(t):
@@ -133,7 +143,7 @@ def sha(t):
 
 def run(name):
     e = TABLE[name]
-    if "D3DP_FOLD_LN" in e["env"] and _lib.load().d3dp_debug_x2_variants() != 1:
+    if ("D3DP_FOLD_LN" in e["env"] or e.get("variants")) and _lib.load().d3dp_debug_x2_variants() != 1:
         print(f"{name}: needs the variants build")
         return
     c = RawCtx(e["mode"], e["C"], e["F"], e["J"], e["depth"], e["chunk"])
@@ -148,6 +158,13 @@ def run(name):
         assert rcs == (0, 0), (rcs, c.lib.d3dp_last_error())
         torch.cuda.synchronize()
         line += f" out {sha(out)} grads " + " ".join(sha(g) for g in c.flat_grads(grads))
+        counts, ms = (C.c_int64 * _lib.PROFILE_CLASSES)(), (C.c_double * _lib.PROFILE_CLASSES)()
+        _lib.check(c.lib.d3dp_profile_enable(c.ctx, 1), "d3dp_profile_enable")
+        rcs = c.train_forward(inputs, out, B, ws.data_ptr(), n), c.train_backward(inputs, grads, B, ws.data_ptr(), n)
+        assert rcs == (0, 0), (rcs, c.lib.d3dp_last_error())
+        _lib.check(c.lib.d3dp_profile_read(c.ctx, counts, ms), "d3dp_profile_read")
+        _lib.check(c.lib.d3dp_profile_enable(c.ctx, 0), "d3dp_profile_enable")
+        line += " launches " + ",".join(str(k) for k in counts)
     else:
         n = c.infer_bytes(B, H)
         ws = torch.empty(n, dtype=torch.uint8, device="cuda")
@@ -162,7 +179,10 @@ def run(name):
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == "--only":
         return run(sys.argv[2])
+    match = sys.argv[2] if len(sys.argv) == 3 and sys.argv[1] == "--match" else ""
     for name, e in TABLE.items():
+        if match not in name:
+            continue
         if e["env"]:
             subprocess.run([sys.executable, os.path.abspath(__file__), "--only", name], env=dict(os.environ, **e["env"]), check=True,
                            timeout=300)
