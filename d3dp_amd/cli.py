@@ -65,6 +65,9 @@ def parse_args(argv=None):
     p.add_argument('--train-passes', type=int, default=None, choices=[1, 3],
                    help='fp16-MFMA passes per product of the training Linears: 1 = D3DP_TRAIN_PASSES=1 (fp16 operands at their own '
                         'scale, fp32 accumulation), 3 = the split-fp16 default; set around the creation of the training model only')
+    p.add_argument('--train-long-attn', action='store_true',
+                   help='D3DP_TRAIN_LONG_ATTN=chunked: the fp32 attention backward of the training step on its chunked kernels -- '
+                        'trains at any -cs and -f (e.g. -cs 1024 -f 243, -cs 96 -f 351); set around the creation of the training model only')
     p.add_argument('--seed', type=int, default=1)
     a = p.parse_args(argv)
     a.test_time_augmentation = True          # arguments.py:112 (no flag turns it off in the reference)
@@ -200,6 +203,24 @@ def train_passes_env(passes):
             os.environ["D3DP_TRAIN_PASSES"] = saved
 
 
+@contextlib.contextmanager
+def train_long_attn_env(on):
+    """D3DP_TRAIN_LONG_ATTN=chunked inside the block (false: the environment as it is), restored on exit.  The library reads the switch
+    when a TRAIN context is created -- the training model's first step -- and for no context of another mode."""
+    if not on:
+        yield
+        return
+    saved = os.environ.get("D3DP_TRAIN_LONG_ATTN")
+    os.environ["D3DP_TRAIN_LONG_ATTN"] = "chunked"
+    try:
+        yield
+    finally:
+        if saved is None:
+            os.environ.pop("D3DP_TRAIN_LONG_ATTN", None)
+        else:
+            os.environ["D3DP_TRAIN_LONG_ATTN"] = saved
+
+
 def run_train(args, rank, world, device):
     """main.py:305-593 on synthetic sequences: ChunkedBatcher (pools in HBM) -> D3DP(is_train=True) -> HipAdamW."""
     from .data import ChunkedBatcher
@@ -214,9 +235,9 @@ def run_train(args, rank, world, device):
     model_eval = D3DP(args, kl, kr, is_train=False, numerics=args.numerics).to(device)
     if not args.resume:
         model_train.load_state_dict(make_state_dict(7, args.cs, args.dep, args.number_of_frames), strict=False)
-    # --train-passes: the TRAIN context is created HERE, inside the switch's block, instead of at the first step (the eval model's
+    # --train-passes / --train-long-attn: the TRAIN context is created HERE, inside the switch's block, instead of at the first step (the eval model's
     # contexts, created later in the same process, never see the variable)
-    with train_passes_env(args.train_passes):
+    with train_passes_env(args.train_passes), train_long_attn_env(getattr(args, 'train_long_attn', False)):
         model_train.pose_estimator._context(device)
         print('INFO: training arithmetic:', model_train.pose_estimator.train_arithmetic())
     n_params = sum(p.numel() for p in model_train.parameters())

@@ -314,8 +314,9 @@ int d3dp_train_forward(d3dp_ctx* c, const float* x2d, const float* x3d, const in
   // clips longer than 256 frames (reference common/arguments.py:58, main.py:325 train at any `-f`): the split-fp16 attention kernels
   // pass their keys / queries through LDS in chunks (train_attn.hip: head dims 64, 32 and 16, and 24 / 40 / 48 / 56 at the widths
   // D3DP_TRAIN_IMPL=f16x2 opts in); the fp32 kernels hold whole sequences, and they are what head dim 8, a width on the fp32 path
-  // and the cross-check switches run
-  if (g.frames > 256 && !(P.path.attn_x2(0) && P.path.attn_x2(1)))
+  // and the cross-check switches run -- unless D3DP_TRAIN_LONG_ATTN=chunked (CtxPlan::train_long_attn) put their backward on the
+  // chunked kernels (the forward side, d3dp_launch_attn_rows, passes K and V through LDS in chunks at every length)
+  if (g.frames > 256 && !(P.path.attn_x2(0) && P.path.attn_x2(1)) && !P.attn_bwd_chunked)
     return d3dp_fail(D3DP_ENOTSUP, "frames=%d > 256: the training step runs such clips on its split-fp16 attention kernels only, which take "
                               "head dims 64, 32 and 16 -- 24, 40, 48 and 56 under D3DP_TRAIN_IMPL=f16x2 -- (channels=%d heads=%d is head dim %d) and are switched off by the cross-check "
                               "switches D3DP_TRAIN_IMPL=f32 and D3DP_TRAIN_ATTN=f32|x2t; the fp32 attention holds a whole sequence "
@@ -637,7 +638,8 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
       LAUNCH_TRY(dgrad(blk, kProj, dy, dB));                                                                            // d att
       // (fp32 kernels: both passes behind one launcher -- timed together under the pass-Q class)
       TP(kind ? T_ATTN_BQ_T : T_ATTN_BQ_S, d3dp_train_attn_bwd(S + L.o_qkv, S + L.o_att, dB, dqkv, ws + L.stats, kind ? B * J : B * F,
-                                                             kind ? temporal_map(F, J) : spatial_map(F, J), C, g.heads, st));
+                                                             kind ? temporal_map(F, J) : spatial_map(F, J), C, g.heads, st,
+                                                             P.attn_bwd_chunked));
     }
     if (!x2) TP(T_LN_FWD, d3dp_train_ln_pos(S + L.o_xin, w.n1w, w.n1b, g.eps_block, nullptr, F, J, xn, T, C, st));    // xn1
     LAUNCH_TRY(wgrad(blk, kQkv, dqkv, xn, G(gw.qkv_w), G(gw.qkv_b), ps_dqkv));

@@ -17,7 +17,7 @@ struct CtxEnv {
   const char *exact_impl = nullptr, *long_attn = nullptr, *no_fold = nullptr, *defer_norm = nullptr, *train_impl = nullptr,
              *train_overlap = nullptr, *train_gelu = nullptr, *train_wgrad = nullptr, *train_ln_operand = nullptr, *train_tail = nullptr,
              *train_attn = nullptr, *train_passes = nullptr, *fast_impl = nullptr, *fast16_range = nullptr, *x2_skew = nullptr,
-             *x2_pp = nullptr, *x2_wide = nullptr, *seq_pad = nullptr, *fold_ln = nullptr;
+             *x2_pp = nullptr, *x2_wide = nullptr, *seq_pad = nullptr, *fold_ln = nullptr, *train_long_attn = nullptr;
   static CtxEnv from_process() {
     CtxEnv e;
     e.exact_impl = getenv("D3DP_EXACT_IMPL");                 // bf16x3 | f32: cross-check implementations of EXACT mode; f16x2: opt-in at 192 ... 448
@@ -39,6 +39,7 @@ struct CtxEnv {
     e.x2_wide = getenv("D3DP_X2_WIDE");                       // 1: experiment, its 256 x 256 tile form
     e.seq_pad = getenv("D3DP_SEQ_PAD");                       // 0 | 1: experiment, the sequence padding of the skewed schedule without it / the reverse
     e.fold_ln = getenv("D3DP_FOLD_LN");                       // 1: experiment, norm2 folded into proj / fc1
+    e.train_long_attn = getenv("D3DP_TRAIN_LONG_ATTN");       // chunked: opt-in, the fp32 training attention backward at any sequence length
     return e;
   }
 };
@@ -80,6 +81,10 @@ struct CtxPlan {
   int train_attn_x2 = 2;         // the training step's attention on the split-fp16 kernels of train_attn.hip: 2 = both axes (default),
                                  // 1 = D3DP_TRAIN_ATTN=x2t: the temporal axis only, 0 = D3DP_TRAIN_ATTN=f32: neither (the round-4
                                  // fp32 kernels -- fp32-MFMA temporal forward and backward, VALU spatial forward: the cross-check)
+  bool train_long_attn = false;  // D3DP_TRAIN_LONG_ATTN=chunked (TRAIN contexts alone): every fp32 attention backward of the training step
+                                 // that runs on the VALU kernels takes their chunked forms (train.hip attn_bwd_*_chunk_kernel: K / V,
+                                 // then Q / dO / statistics pass through LDS in chunks of rows, a row block of 256 per workgroup), which
+                                 // take any sequence length: no token limit in step 6, no frames <= 256 in d3dp_train_forward
   int skew_d = 0;                // D3DP_X2_SKEW=1|2|4: k-steps a parked row class takes to leave.  OFF by default: measured
                                  // 3 % slower on the whole step (gemm_x2.hip, DESIGN.md 7: the Linear is bound by its vector-memory
                                  // instruction rate, and an epilogue's stores cost the same wherever they issue)
@@ -151,7 +156,8 @@ inline int plan_context(const d3dp_cfg& g, const CtxEnv& e, bool variants_built,
   //  instantiated set runs that fp32 attention with a run-time head dim and is refused in step 6 beyond 256 tokens, 153 at head dims
   //  above 64 -- unless D3DP_TRAIN_IMPL=f16x2 opted it into the split-fp16 step: head dims 24 / 40 / 48 / 56 then run padded forms
   //  of the split-fp16 attention and take every length up to 1024 too, and what the cross-check switches or head dim 8 leave on the
-  //  fp32 attention there is refused by d3dp_train_forward like at every width.)
+  //  fp32 attention there is refused by d3dp_train_forward like at every width.  D3DP_TRAIN_LONG_ATTN=chunked, step 5a, lifts both
+  //  refusals: the fp32 attention backward then passes its rows through LDS in chunks, as the fp32 row attention forward does.)
   if (g.frames < 1 || g.frames > 1024) return d3dp_fail(D3DP_ENOTSUP, "frames=%d not in [1,1024]", g.frames);
   // (more than 32 joints: the spatial axis takes the whole-sequence attention kernels the temporal axis runs on, round 6)
   if (g.joints < 1 || g.joints > 256) return d3dp_fail(D3DP_ENOTSUP, "joints=%d not in [1,256]", g.joints);
@@ -221,6 +227,14 @@ inline int plan_context(const d3dp_cfg& g, const CtxEnv& e, bool variants_built,
                                 "and 1024", g.hidden);
     p.fast16_scale = inst;             // (any other width: refused in step 6 like every FAST16 context there)
   }
+  // 5a. D3DP_TRAIN_LONG_ATTN (TRAIN contexts alone; in front of step 6 because it lifts that step's token limit): =chunked moves the
+  // fp32 attention backward onto the chunked VALU kernels (CtxPlan::train_long_attn).  Any other value is refused -- never ignored.
+  if (train && e.train_long_attn) {
+    if (strcmp(e.train_long_attn, "chunked"))
+      return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_LONG_ATTN=%.32s: the one value a TRAIN context takes is D3DP_TRAIN_LONG_ATTN=chunked (the fp32 "
+                                "attention backward passes its rows through LDS in chunks and takes any sequence length)", e.train_long_attn);
+    p.train_long_attn = true;
+  }
   // 6. A width neither instantiated nor padded: the fp32 implementation, EXACT and TRAIN contexts alone.
   const bool width_inst = inst || p.hdp != 0;
   if (!width_inst) {
@@ -236,9 +250,10 @@ inline int plan_context(const d3dp_cfg& g, const CtxEnv& e, bool variants_built,
     if (g.channels > 1024 || g.channels % 4 || hd % 4 || hd > 128 || g.hidden < 4 || g.hidden % 4)
       return d3dp_fail(D3DP_ENOTSUP, "channels=%d heads=%d hidden=%d: the fp32 implementation takes channels <= 1024, head dim a multiple of 4 up to 128 "
                                 "and hidden a multiple of 4", g.channels, g.heads, g.hidden);
-    // (the fp32 attention backward holds two whole-sequence images of its capacity head dim + the statistics in the CU's 160 KiB)
+    // (the fp32 attention backward holds two whole-sequence images of its capacity head dim + the statistics in the CU's 160 KiB;
+    //  its chunked form -- D3DP_TRAIN_LONG_ATTN=chunked -- holds a chunk of rows and takes every length step 1 lets through)
     const int nmax = std::max(g.frames, g.joints), cap = hd <= 16 ? 16 : hd <= 32 ? 32 : hd <= 64 ? 64 : 128;
-    if (train && !train_widths && (nmax > 256 || (size_t)nmax * (8 * (cap + 4) + 12) > 160 * 1024))
+    if (train && !train_widths && !p.train_long_attn && (nmax > 256 || (size_t)nmax * (8 * (cap + 4) + 12) > 160 * 1024))
       return d3dp_fail(D3DP_ENOTSUP, "channels=%d heads=%d frames=%d joints=%d: training at a width outside {64,128,256,512} runs the fp32 attention "
                                 "backward, which holds a whole sequence in LDS (<= 256 tokens; <= 153 at head dims above 64)",
                   g.channels, g.heads, g.frames, g.joints);

@@ -326,8 +326,10 @@ int d3dp_train_zero_many(const D3dpZeroTable& tb, hipStream_t st);
 // grouped row sums (mode 0: per joint, 1: per frame, 2: per batch element) as `slices` partial tables of groups x C floats
 int d3dp_train_groupsum(const float* in, float* out, int T, int C, int mode, int F, int J, int slices, hipStream_t st);
 int d3dp_train_transpose_pad(const float* in, float* out, int R, int C, int Rpad, hipStream_t st);
+// chunked (CtxPlan::train_long_attn): every launch that goes to the whole-sequence VALU pair, or that they refuse with -2 (more than
+// 256 tokens, or two images beyond 160 KiB), goes to the chunked pair instead -- any n, bit-equal gradients where both run
 int d3dp_train_attn_bwd(const float* qkv, const float* o, const float* dout, float* dqkv, void* stats, int n_seq,
-                        SeqMap map, int C, int heads, hipStream_t st);
+                        SeqMap map, int C, int heads, hipStream_t st, bool chunked = false);
 // ---- train_attn.hip: the training step's attention on split-fp16 operands (head dim 64, 32 or 16, and 24 / 40 / 48 / 56 padded to 32 / 64
 // inside the kernels: -2 for any other; <= 1024 tokens per sequence) ----
 // stats: d3dp_train_attn_x2_stats_bytes per attention (the forward leaves the log-sum-exp of every query for the backward pass);

@@ -732,6 +732,244 @@ __global__ __launch_bounds__(512) void attn_bwd_kv_kernel(const float* __restric
   }
 }
 
+// ---- the chunked forms of the two kernels above (D3DP_TRAIN_LONG_ATTN=chunked): any sequence length -------------------------------
+// Grid (sequence x head, row blocks of 256): a thread pair still owns one query row (pass 1) / one key row (pass 2), and what the
+// whole-sequence kernels hold in LDS for the whole sequence -- K, V; Q, dO, the statistics -- passes through it in chunks of CH rows
+// (attn_bwd_chunk_rows: two images of pitch HD + 4 and the statistics within the CU's 160 KiB).  CH is a multiple of both kernels' KB, so
+// that the groups of KB rows start where they start in the whole-sequence kernels and a clamped row min(j0 + u, n - 1) lies in the chunk
+// being read.  Pass 1 walks the chunks twice: the online (m, l) recurrence, then dS and dQ -- what the whole-sequence kernel does over
+// its one image.  The arithmetic and its order are those kernels': the same fmaf chains over keys / queries in ascending order, the
+// same KB grouping, expf(m - gm) once per group, inv = 1 / l, / a.l in pass 2 -- so the gradients are bit-equal wherever both forms
+// run (tests/test_hip_train_long.py).  Every thread of a block takes part in every barrier: a thread whose row lies beyond n stages,
+// computes on row n - 1 and returns behind the last chunk without storing.  Two barriers per chunk, each in front of ~CH x HD
+// fmaf per thread: their cost is noise.  LDS reads are one row address per half of a lane pair (a broadcast; the two halves lie
+// HD / 2 dwords apart), the staging writes are 16-byte slots of consecutive lanes along rows of pitch HD + 4.  Pass 2 keeps a chunk
+// row's Q and dO rows side by side (one per-lane LDS address and a constant offset serve both images: at capacity 128, where k, v,
+// dK and dV alone fill the register file, that keeps its scratch below the whole-sequence kernel's; profiles/train_long_f32.md).
+template <int HD> constexpr int attn_bwd_chunk_rows() { return HD <= 64 ? 256 : 128; }
+constexpr int ATTN_BWD_BLOCK_ROWS = 256;
+
+template <int HD, bool GEN = false>
+__global__ __launch_bounds__(512) void attn_bwd_q_chunk_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
+                                                               const float* __restrict__ dout, float* __restrict__ dqkv,
+                                                               AttnStats* __restrict__ stats, SeqMap map, int C, int heads, int hd_rt) {
+  const int hd = GEN ? hd_rt : HD;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* Ks = reinterpret_cast<float*>(smem_raw);
+  const int n = map.n_tok;
+  constexpr int LDR = HD + 4, CH = attn_bwd_chunk_rows<HD>();
+  float* Vs = Ks + (size_t)min(n, CH) * LDR;
+  const int seq = blockIdx.x / heads, head = blockIdx.x % heads;
+  const int base = (seq / map.inner) * map.outer_stride + (seq % map.inner) * map.inner_stride;
+  // rows [c0, c0 + rows) of K (and of V) -> LDS; the barrier in front keeps the chunk before it until every thread has read it
+  auto stage = [&](int c0, int rows, bool with_v) {
+    __syncthreads();
+    for (int u = threadIdx.x; u < rows * (HD / 4); u += blockDim.x) {
+      const int j = u / (HD / 4), c = u % (HD / 4);
+      const float* src = qkv + (size_t)(base + (c0 + j) * map.tok_stride) * 3 * C + C + head * hd + c * 4;
+      const bool in = !GEN || c * 4 < hd;
+      *reinterpret_cast<float4*>(Ks + j * LDR + c * 4) = in ? *reinterpret_cast<const float4*>(src) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (with_v)
+        *reinterpret_cast<float4*>(Vs + j * LDR + c * 4) = in ? *reinterpret_cast<const float4*>(src + C) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+  };
+  const bool one = n <= CH;                              // one chunk: staged once, K and V, for both walks
+  const int i = blockIdx.y * ATTN_BWD_BLOCK_ROWS + (threadIdx.x >> 1), half = threadIdx.x & 1;
+  const bool live = i < n;
+  const int ii = live ? i : n - 1;
+  constexpr int HH = HD / 2;
+  const size_t tok = (size_t)(base + ii * map.tok_stride);
+  const float scale = 1.0f / sqrtf((float)hd);
+  float q[HH], dO[HH], dq[HH];
+  float D = 0.f;
+#pragma unroll
+  for (int d = 0; d < HH; ++d) {
+    const bool in = !GEN || half * HH + d < hd;
+    q[d] = in ? qkv[tok * 3 * C + head * hd + half * HH + d] : 0.f;
+    dO[d] = in ? dout[tok * C + head * hd + half * HH + d] : 0.f;
+    D = fmaf(dO[d], in ? o[tok * C + head * hd + half * HH + d] : 0.f, D);
+    dq[d] = 0.f;
+  }
+  D += __shfl_xor(D, 1, 64);
+  const float* Kh = Ks + half * HH;
+  const float* Vh = Vs + half * HH;
+  constexpr int KB = 4;
+  static_assert(CH % KB == 0, "a group of KB keys lies in one chunk");
+  // Walk A: row max and denominator (online recurrence)
+  float m = -INFINITY, l = 0.f;
+  for (int c0 = 0; c0 < n; c0 += CH) {
+    const int c1 = min(c0 + CH, n);
+    stage(c0, c1 - c0, one);
+    for (int j0 = c0; j0 < c1; j0 += KB) {
+      float sc[KB];
+#pragma unroll
+      for (int u = 0; u < KB; ++u) sc[u] = 0.f;
+#pragma unroll
+      for (int c = 0; c < HH / 4; ++c) {
+#pragma unroll
+        for (int u = 0; u < KB; ++u) {
+          const float4 kv = *reinterpret_cast<const float4*>(Kh + (min(j0 + u, n - 1) - c0) * LDR + c * 4);
+          sc[u] = fmaf(q[c * 4], kv.x, sc[u]); sc[u] = fmaf(q[c * 4 + 1], kv.y, sc[u]);
+          sc[u] = fmaf(q[c * 4 + 2], kv.z, sc[u]); sc[u] = fmaf(q[c * 4 + 3], kv.w, sc[u]);
+        }
+      }
+      float gm = m;
+#pragma unroll
+      for (int u = 0; u < KB; ++u) {
+        sc[u] += __shfl_xor(sc[u], 1, 64);
+        sc[u] = (j0 + u < n) ? sc[u] * scale : -INFINITY;
+        gm = fmaxf(gm, sc[u]);
+      }
+      l *= expf(m - gm);
+#pragma unroll
+      for (int u = 0; u < KB; ++u) l += expf(sc[u] - gm);
+      m = gm;
+    }
+  }
+  const float inv = 1.0f / l;
+  // Walk B: dS_ij = P_ij (dO_i . V_j - D_i) s ;  dQ_i += dS_ij K_j
+  for (int c0 = 0; c0 < n; c0 += CH) {
+    const int c1 = min(c0 + CH, n);
+    if (!one) stage(c0, c1 - c0, true);
+    for (int j0 = c0; j0 < c1; j0 += KB) {
+      float sc[KB], dp[KB];
+#pragma unroll
+      for (int u = 0; u < KB; ++u) { sc[u] = 0.f; dp[u] = 0.f; }
+#pragma unroll
+      for (int c = 0; c < HH / 4; ++c) {
+#pragma unroll
+        for (int u = 0; u < KB; ++u) {
+          const int j = min(j0 + u, n - 1) - c0;
+          const float4 kv = *reinterpret_cast<const float4*>(Kh + j * LDR + c * 4);
+          const float4 vv = *reinterpret_cast<const float4*>(Vh + j * LDR + c * 4);
+          sc[u] = fmaf(q[c * 4], kv.x, sc[u]); sc[u] = fmaf(q[c * 4 + 1], kv.y, sc[u]);
+          sc[u] = fmaf(q[c * 4 + 2], kv.z, sc[u]); sc[u] = fmaf(q[c * 4 + 3], kv.w, sc[u]);
+          dp[u] = fmaf(dO[c * 4], vv.x, dp[u]); dp[u] = fmaf(dO[c * 4 + 1], vv.y, dp[u]);
+          dp[u] = fmaf(dO[c * 4 + 2], vv.z, dp[u]); dp[u] = fmaf(dO[c * 4 + 3], vv.w, dp[u]);
+        }
+      }
+      float ds[KB];
+#pragma unroll
+      for (int u = 0; u < KB; ++u) {
+        sc[u] += __shfl_xor(sc[u], 1, 64);
+        dp[u] += __shfl_xor(dp[u], 1, 64);
+        ds[u] = (j0 + u < n) ? expf(sc[u] * scale - m) * inv * (dp[u] - D) * scale : 0.f;
+      }
+#pragma unroll
+      for (int c = 0; c < HH / 4; ++c) {
+#pragma unroll
+        for (int u = 0; u < KB; ++u) {
+          const float4 kv = *reinterpret_cast<const float4*>(Kh + (min(j0 + u, n - 1) - c0) * LDR + c * 4);
+          dq[c * 4] = fmaf(ds[u], kv.x, dq[c * 4]); dq[c * 4 + 1] = fmaf(ds[u], kv.y, dq[c * 4 + 1]);
+          dq[c * 4 + 2] = fmaf(ds[u], kv.z, dq[c * 4 + 2]); dq[c * 4 + 3] = fmaf(ds[u], kv.w, dq[c * 4 + 3]);
+        }
+      }
+    }
+  }
+  if (!live) return;
+#pragma unroll
+  for (int d = 0; d < HH; ++d)
+    if (!GEN || half * HH + d < hd) dqkv[tok * 3 * C + head * hd + half * HH + d] = dq[d];
+  if (half == 0) stats[(size_t)blockIdx.x * n + i] = AttnStats{m, l, D};
+}
+
+template <int HD, bool GEN = false>
+__global__ __launch_bounds__(512) void attn_bwd_kv_chunk_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
+                                                                float* __restrict__ dqkv, const AttnStats* __restrict__ stats,
+                                                                SeqMap map, int C, int heads, int hd_rt) {
+  const int hd = GEN ? hd_rt : HD;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* Qs = reinterpret_cast<float*>(smem_raw);
+  const int n = map.n_tok;
+  // (row i of the chunk: its Q row, then its dO row, each of pitch HD + 4 -- one per-lane LDS address serves both images)
+  constexpr int LDR = HD + 4, LD2 = 2 * LDR, CH = attn_bwd_chunk_rows<HD>();
+  float* Os = Qs + LDR;
+  AttnStats* st = reinterpret_cast<AttnStats*>(Qs + (size_t)min(n, CH) * LD2);
+  const int seq = blockIdx.x / heads, head = blockIdx.x % heads;
+  const int base = (seq / map.inner) * map.outer_stride + (seq % map.inner) * map.inner_stride;
+  const int j = blockIdx.y * ATTN_BWD_BLOCK_ROWS + (threadIdx.x >> 1), half = threadIdx.x & 1;
+  const bool live = j < n;
+  const int jj = live ? j : n - 1;
+  constexpr int HH = HD / 2;
+  const size_t tok = (size_t)(base + jj * map.tok_stride);
+  const float scale = 1.0f / sqrtf((float)hd);
+  float k[HH], v[HH], dk[HH], dv[HH];
+#pragma unroll
+  for (int d = 0; d < HH; ++d) {
+    const bool in = !GEN || half * HH + d < hd;
+    k[d] = in ? qkv[tok * 3 * C + C + head * hd + half * HH + d] : 0.f;
+    v[d] = in ? qkv[tok * 3 * C + 2 * C + head * hd + half * HH + d] : 0.f;
+    dk[d] = 0.f; dv[d] = 0.f;
+  }
+  const float* Qh = Qs + half * HH;
+  const float* Oh = Os + half * HH;
+  constexpr int KB = 2;
+  static_assert(CH % KB == 0, "a group of KB queries lies in one chunk");
+  for (int c0 = 0; c0 < n; c0 += CH) {
+    const int c1 = min(c0 + CH, n);
+    __syncthreads();                                     // (every thread has read the chunk before this one)
+    for (int u = threadIdx.x; u < (c1 - c0) * (HD / 4); u += blockDim.x) {
+      const int i = u / (HD / 4), c = u % (HD / 4);
+      const size_t tk = (size_t)(base + (c0 + i) * map.tok_stride);
+      const bool in = !GEN || c * 4 < hd;
+      *reinterpret_cast<float4*>(Qs + i * LD2 + c * 4) =
+          in ? *reinterpret_cast<const float4*>(qkv + tk * 3 * C + head * hd + c * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(Os + i * LD2 + c * 4) =
+          in ? *reinterpret_cast<const float4*>(dout + tk * C + head * hd + c * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int i = threadIdx.x; i < c1 - c0; i += blockDim.x) st[i] = stats[(size_t)blockIdx.x * n + c0 + i];
+    __syncthreads();
+    for (int i0 = c0; i0 < c1; i0 += KB) {
+      float sc[KB], dp[KB];
+#pragma unroll
+      for (int u = 0; u < KB; ++u) { sc[u] = 0.f; dp[u] = 0.f; }
+#pragma unroll
+      for (int c = 0; c < HH / 4; ++c) {
+#pragma unroll
+        for (int u = 0; u < KB; ++u) {
+          const int i = min(i0 + u, n - 1) - c0;
+          const float4 qv = *reinterpret_cast<const float4*>(Qh + i * LD2 + c * 4);
+          const float4 ov = *reinterpret_cast<const float4*>(Oh + i * LD2 + c * 4);
+          sc[u] = fmaf(qv.x, k[c * 4], sc[u]); sc[u] = fmaf(qv.y, k[c * 4 + 1], sc[u]);
+          sc[u] = fmaf(qv.z, k[c * 4 + 2], sc[u]); sc[u] = fmaf(qv.w, k[c * 4 + 3], sc[u]);
+          dp[u] = fmaf(ov.x, v[c * 4], dp[u]); dp[u] = fmaf(ov.y, v[c * 4 + 1], dp[u]);
+          dp[u] = fmaf(ov.z, v[c * 4 + 2], dp[u]); dp[u] = fmaf(ov.w, v[c * 4 + 3], dp[u]);
+        }
+      }
+      float pr[KB], ds[KB];
+#pragma unroll
+      for (int u = 0; u < KB; ++u) {
+        sc[u] += __shfl_xor(sc[u], 1, 64);
+        dp[u] += __shfl_xor(dp[u], 1, 64);
+        const AttnStats a = st[min(i0 + u, n - 1) - c0];
+        pr[u] = (i0 + u < n) ? expf(sc[u] * scale - a.m) / a.l : 0.f;
+        ds[u] = pr[u] * (dp[u] - a.D) * scale;
+      }
+#pragma unroll
+      for (int c = 0; c < HH / 4; ++c) {
+#pragma unroll
+        for (int u = 0; u < KB; ++u) {
+          const int i = min(i0 + u, n - 1) - c0;
+          const float4 qv = *reinterpret_cast<const float4*>(Qh + i * LD2 + c * 4);
+          const float4 ov = *reinterpret_cast<const float4*>(Oh + i * LD2 + c * 4);
+          dk[c * 4] = fmaf(ds[u], qv.x, dk[c * 4]); dk[c * 4 + 1] = fmaf(ds[u], qv.y, dk[c * 4 + 1]);
+          dk[c * 4 + 2] = fmaf(ds[u], qv.z, dk[c * 4 + 2]); dk[c * 4 + 3] = fmaf(ds[u], qv.w, dk[c * 4 + 3]);
+          dv[c * 4] = fmaf(pr[u], ov.x, dv[c * 4]); dv[c * 4 + 1] = fmaf(pr[u], ov.y, dv[c * 4 + 1]);
+          dv[c * 4 + 2] = fmaf(pr[u], ov.z, dv[c * 4 + 2]); dv[c * 4 + 3] = fmaf(pr[u], ov.w, dv[c * 4 + 3]);
+        }
+      }
+    }
+  }
+  if (!live) return;
+#pragma unroll
+  for (int d = 0; d < HH; ++d) {
+    if (GEN && half * HH + d >= hd) continue;
+    dqkv[tok * 3 * C + C + head * hd + half * HH + d] = dk[d];
+    dqkv[tok * 3 * C + 2 * C + head * hd + half * HH + d] = dv[d];
+  }
+}
+
 // ---- embedding backward: dW[c, i] = sum_t dx[t, c] in5[t, i] ; in5 = (u, v, x, y, z); gridDim.y partial tables of 5 C floats ----
 __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict__ dx, const float* __restrict__ x2d,
                                                         const float* __restrict__ x3d, float* __restrict__ part, int T, int C) {
@@ -1256,9 +1494,35 @@ static int launch_attn_bwd_mfma(const float* qkv, const float* o, const float* d
   return 0;
 }
 
+// the chunked VALU pair: any n >= 1
+template <int HD, bool GEN>
+static int launch_attn_bwd_chunked(const float* qkv, const float* o, const float* dout, float* dqkv, void* stats, int n_seq,
+                                   SeqMap map, int C, int heads, hipStream_t st) {
+  const int n = map.n_tok;
+  if (n < 1) return -1;
+  const int rows = n < attn_bwd_chunk_rows<HD>() ? n : attn_bwd_chunk_rows<HD>();            // rows of a chunk's LDS images
+  const size_t lds_q = (size_t)2 * rows * (HD + 4) * 4;
+  const size_t lds_kv = lds_q + (size_t)rows * sizeof(AttnStats);
+  static_assert((size_t)2 * attn_bwd_chunk_rows<HD>() * (HD + 4) * 4 + attn_bwd_chunk_rows<HD>() * sizeof(AttnStats) <= 160 * 1024,
+                "a chunk's two images and its statistics fit the CU's LDS");
+  static PerDeviceOnce once;
+  if (once.get([&](int) {
+        return d3dp_lds_opt_in(reinterpret_cast<const void*>(attn_bwd_q_chunk_kernel<HD, GEN>), 160 * 1024) < 0 ? -3
+               : d3dp_lds_opt_in(reinterpret_cast<const void*>(attn_bwd_kv_chunk_kernel<HD, GEN>), 160 * 1024);
+      }) < 0) return -3;
+  // two threads per row in both passes; a row block of ATTN_BWD_BLOCK_ROWS rows per workgroup
+  const int threads = 2 * n <= 64 ? 64 : (2 * n <= 256 ? 256 : 512);
+  const dim3 grid(n_seq * heads, (n + ATTN_BWD_BLOCK_ROWS - 1) / ATTN_BWD_BLOCK_ROWS);
+  hipLaunchKernelGGL((attn_bwd_q_chunk_kernel<HD, GEN>), grid, dim3(threads), lds_q, st, qkv, o, dout, dqkv, (AttnStats*)stats, map, C,
+                     heads, C / heads);
+  hipLaunchKernelGGL((attn_bwd_kv_chunk_kernel<HD, GEN>), grid, dim3(threads), lds_kv, st, qkv, dout, dqkv, (const AttnStats*)stats, map,
+                     C, heads, C / heads);
+  return 0;
+}
+
 template <int HD, bool GEN = false>
 static int launch_attn_bwd(const float* qkv, const float* o, const float* dout, float* dqkv, void* stats, int n_seq,
-                           SeqMap map, int C, int heads, hipStream_t st) {
+                           SeqMap map, int C, int heads, hipStream_t st, bool chunked) {
   const int n = map.n_tok;
   if constexpr (HD == 64 && !GEN) {
     // head dim 64 on the fp32 matrix cores; D3DP_TRAIN_ATTN_BWD=valu keeps the kernels below (cross-check)
@@ -1271,6 +1535,7 @@ static int launch_attn_bwd(const float* qkv, const float* o, const float* dout, 
       return launch_attn_bwd_mfma<16>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st);
     }
   }
+  if (chunked) return launch_attn_bwd_chunked<HD, GEN>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st);
   const size_t lds_q = (size_t)2 * n * (HD + 4) * 4;
   const size_t lds_kv = lds_q + (size_t)n * sizeof(AttnStats);
   if (lds_kv > 160 * 1024 || n > 256) return -2;
@@ -1288,21 +1553,21 @@ static int launch_attn_bwd(const float* qkv, const float* o, const float* dout, 
 }
 
 int d3dp_train_attn_bwd(const float* qkv, const float* o, const float* dout, float* dqkv, void* stats, int n_seq,
-                        SeqMap map, int C, int heads, hipStream_t st) {
+                        SeqMap map, int C, int heads, hipStream_t st, bool chunked) {
   switch (C / heads) {
-    case 64: return launch_attn_bwd<64>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st);
-    case 32: return launch_attn_bwd<32>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st);
-    case 16: return launch_attn_bwd<16>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st);
-    case 8: return launch_attn_bwd<8>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st);
+    case 64: return launch_attn_bwd<64>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st, chunked);
+    case 32: return launch_attn_bwd<32>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st, chunked);
+    case 16: return launch_attn_bwd<16>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st, chunked);
+    case 8: return launch_attn_bwd<8>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st, chunked);
     default: break;
   }
   // any other head dim (a multiple of 4 up to 128): the run-time form on the next capacity
   const int hd = C / heads;
   if (hd < 4 || hd % 4 || hd > 128 || hd * heads != C) return -2;
-  if (hd <= 16) return launch_attn_bwd<16, true>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st);
-  if (hd <= 32) return launch_attn_bwd<32, true>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st);
-  if (hd <= 64) return launch_attn_bwd<64, true>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st);
-  return launch_attn_bwd<128, true>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st);
+  if (hd <= 16) return launch_attn_bwd<16, true>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st, chunked);
+  if (hd <= 32) return launch_attn_bwd<32, true>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st, chunked);
+  if (hd <= 64) return launch_attn_bwd<64, true>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st, chunked);
+  return launch_attn_bwd<128, true>(qkv, o, dout, dqkv, stats, n_seq, map, C, heads, st, chunked);
 }
 // part: D3DP_EMBED_BWD_ROWS partial tables of 5 C floats
 int d3dp_train_embed_bwd(const float* dx, const float* x2d, const float* x3d, float* part, int T, int C, hipStream_t st) {

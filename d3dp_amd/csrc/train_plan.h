@@ -133,7 +133,8 @@ inline bool train_attn_head_dim(int hd) { return mfma_head_dim(hd) || hd == 24 |
 //              and a head dim those kernels take (train_attn_head_dim: 64, 32, 16 -- `-cs` 512 / 256 / 128 with the model's 8 heads --
 //              and 56, 48, 40, 24 -- `-cs` 448 / 384 / 320 / 192 -- padded to 64 / 32 inside the kernels); clips of up to 1024 frames
 //              (beyond 256 their keys / queries pass through LDS in chunks).  Head dim 8, the cross-check switches and every
-//              context on the fp32 path stay on the fp32 kernels of train.hip (<= 256 frames)
+//              context on the fp32 path stay on the fp32 kernels of train.hip (<= 256 frames; any length up to 1024 under
+//              D3DP_TRAIN_LONG_ATTN=chunked: TrainPlan::attn_bwd_chunked)
 //   needs_aux  the backward pass forks its weight-gradient products onto the context's second stream (made by d3dp_create)
 struct TrainPath {
   bool use_x2, attn_x2_t, attn_x2_s, needs_aux;
@@ -195,6 +196,9 @@ struct TrainPlan {
   TrainPath path;
   bool use_x2;                       // = path.use_x2; everything below but T, passes and overlap_sets is false / unused without it
   int T, passes, overlap_sets;
+  // D3DP_TRAIN_LONG_ATTN=chunked (CtxPlan::train_long_attn): an axis on the fp32 attention runs the chunked VALU backward of train.hip
+  // wherever the whole-sequence VALU pair ran or refused, so the forward pass takes clips beyond 256 frames there too
+  bool attn_bwd_chunked;
   TrainLinear lin[4];                // by TrainLinearId
   // the qkv / fc1 operands straight from the INPUT of the LayerNorm in front of them (no fp32 normalised activation is written)
   bool ln_fused;
@@ -235,6 +239,7 @@ inline TrainPlan plan_train_step(const CtxPlan& c, const d3dp_cfg& g, int B, int
   P.path = plan_train_path(c, g);
   P.use_x2 = P.path.use_x2;
   P.T = T; P.passes = c.train_passes; P.overlap_sets = c.train_overlap_sets;
+  P.attn_bwd_chunked = c.train_long_attn;
   const int shape[4][2] = {{3 * C, C}, {C, C}, {Hd, C}, {C, Hd}};       // [N, K] by TrainLinearId
   for (int j = 0; j < 4; ++j) { P.lin[j].N = shape[j][0]; P.lin[j].K = shape[j][1]; }
   if (!P.use_x2) return P;                                              // (the fp32 path: four plain products per block, nothing to route)

@@ -529,6 +529,15 @@ class MixSTE2(nn.Module):
 
     def train_arithmetic(self) -> str:
         """What the training step's Linears run on (bench.py reports it next to the step time)."""
+        text = self._train_arithmetic_default()
+        # D3DP_TRAIN_LONG_ATTN=chunked (ctx_plan.h plan_context, step 5a): the route is named behind the unchanged text
+        if os.environ.get("D3DP_TRAIN_LONG_ATTN") == "chunked":
+            text += ("; D3DP_TRAIN_LONG_ATTN=chunked: every fp32 attention backward that runs on the VALU kernels takes their chunked "
+                     "form (K / V, then Q / dO / statistics pass through LDS in chunks of rows: any clip length up to 1024 frames and "
+                     "any joint count up to 256, bit-equal to the whole-sequence kernels where both run)")
+        return text
+
+    def _train_arithmetic_default(self) -> str:
         ta = os.environ.get("D3DP_TRAIN_ATTN", "")
         hd = self.embed_dim // self.num_heads
         inst = self.embed_dim in (64, 128, 256, 512) and hd in (8, 16, 32, 64) and self.hidden >= 64 and self.hidden % 64 == 0

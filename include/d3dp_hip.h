@@ -203,14 +203,15 @@ D3DP_API const char* d3dp_last_error(void);
  *                         the attention of both axes on the split-fp16 matrix-core kernels (train_attn.hip), which pass keys /
  *                         queries through LDS in chunks: every frames <= 1024 and joints <= 256 above;
  *   head dim 8 (`-cs 64`): split-fp16 Linears, fp32 attention (VALU / row kernels), whose backward holds a whole sequence in LDS:
- *                         d3dp_create accepts the context, d3dp_train_forward answers D3DP_ENOTSUP beyond 256 frames;
+ *                         d3dp_create accepts the context, d3dp_train_forward answers D3DP_ENOTSUP beyond 256 frames (unless
+ *                         D3DP_TRAIN_LONG_ATTN=chunked, below);
  *   the cross-check switches at the widths above (D3DP_TRAIN_IMPL=f32, D3DP_TRAIN_ATTN=f32|x2t in the environment of d3dp_create)
- *                         select that fp32 attention too, with the same limit of 256 frames;
+ *                         select that fp32 attention too, with the same limit of 256 frames (and the same exception);
  *   any other width (see above: channels <= 1024, head dim % 4 == 0 and <= 128, hidden % 4 == 0): the fp32 path of the training step
  *                         (what D3DP_TRAIN_IMPL=f32 selects for the instantiated widths: fp32-MFMA Linears, run-time-width row
  *                         kernels, VALU attention backward with a run-time head dim).  There d3dp_create itself refuses
  *                         max(frames, joints) > 256 tokens, and > 153 tokens at head dims above 64 (two whole-sequence images
- *                         of the capacity head dim + the statistics in 160 KiB of LDS);
+ *                         of the capacity head dim + the statistics in 160 KiB of LDS) -- unless D3DP_TRAIN_LONG_ATTN=chunked;
  *   channels in {192, 320, 384, 448} with head dim % 8 == 0 and <= 64 and hidden % 64 == 0, with D3DP_TRAIN_IMPL=f16x2 in the
  *                         environment of d3dp_create (OPT-IN: without the switch such a context is the line above, bit for bit
  *                         as before): the split-fp16 training step of the instantiated widths -- every Linear (forward, dgrad,
@@ -237,6 +238,19 @@ D3DP_API const char* d3dp_last_error(void);
  *                         =1 for a context on the fp32 path (D3DP_TRAIN_IMPL=f32, a width outside the sets above); =1 beside
  *                         D3DP_TRAIN_WGRAD=each, D3DP_TRAIN_TAIL=split, D3DP_TRAIN_GELU=pass or D3DP_TRAIN_LN_OPERAND=pass (launch
  *                         forms of the variants build, which have no one-pass form).  D3DP_TRAIN_ATTN, D3DP_TRAIN_ATTN_BWD and
+ *                         D3DP_TRAIN_OVERLAP compose with it.  Contexts of the other modes do not read it.
+ *   D3DP_TRAIN_LONG_ATTN=chunked in the environment of d3dp_create (OPT-IN; read for D3DP_MODE_TRAIN contexts alone; unset: every
+ *                         context plans, refuses and launches as in the lines above, bit for bit): every fp32 attention backward
+ *                         of the step that runs on the VALU kernels -- head dim 8, a width on the fp32 path, the cross-check
+ *                         switches beyond 256 tokens or under D3DP_TRAIN_ATTN_BWD=valu -- takes their chunked forms: a workgroup
+ *                         per 256 rows of a (sequence, head), K / V and then Q / dO / the statistics passing through LDS in chunks
+ *                         of 256 rows (128 at head dims above 64).  Such a context trains at every frames <= 1024 and joints <=
+ *                         256 at every width the fp32 implementation takes (`-cs 1024 -f 243`, `-cs 96 -f 351`, `-cs 64 -f 351`):
+ *                         neither d3dp_create's token limit nor d3dp_train_forward's 256 frames applies.  Same arithmetic in the
+ *                         same order as the whole-sequence kernels: where both run the gradients are the same bits.  Same
+ *                         workspace, same launches per step, no atomics.  The fp32-MFMA backward (head dim 64, <= 256 tokens)
+ *                         stays.  Any other value in a TRAIN context: D3DP_ENOTSUP naming the switch, decided before the device
+ *                         is looked for.  D3DP_TRAIN_IMPL, D3DP_TRAIN_ATTN, D3DP_TRAIN_ATTN_BWD, D3DP_TRAIN_PASSES and
  *                         D3DP_TRAIN_OVERLAP compose with it.  Contexts of the other modes do not read it.
  * A D3DP_MODE_TRAIN context whose backward pass overlaps (split-fp16 Linears, D3DP_TRAIN_OVERLAP not 0) gets its second stream
  * and three events here, so that d3dp_train_backward never creates anything. */
@@ -384,7 +398,8 @@ D3DP_API int d3dp_jpma_ex(const float* pred, const float* traj, const float* cam
  * Clip length: any F <= 1024 like inference (reference common/arguments.py:58); beyond 256 frames the step needs its split-fp16
  * attention kernels (head dims 64, 32 and 16, and 24 / 40 / 48 / 56 under D3DP_TRAIN_IMPL=f16x2; keys / queries through LDS in
  * chunks) -- head dim 8, the fp32 path of the other widths and the fp32 cross-check implementations (D3DP_TRAIN_IMPL=f32,
- * D3DP_TRAIN_ATTN=f32|x2t) hold whole sequences and answer D3DP_ENOTSUP there (d3dp_create). */
+ * D3DP_TRAIN_ATTN=f32|x2t) hold whole sequences and answer D3DP_ENOTSUP there (d3dp_create), unless the context was created under
+ * D3DP_TRAIN_LONG_ATTN=chunked: their backward then passes its rows through LDS in chunks and takes every length too. */
 D3DP_API int d3dp_train_workspace_bytes(const d3dp_ctx* ctx, int32_t B, size_t* bytes);
 D3DP_API int d3dp_train_forward(d3dp_ctx* ctx, const float* x2d, const float* x3d, const int64_t* t, const float* masks, float* out,
                        int32_t B, void* workspace, size_t workspace_bytes, void* stream);
