@@ -65,6 +65,10 @@ def parse_args(argv=None):
     p.add_argument('--train-passes', type=int, default=None, choices=[1, 3],
                    help='fp16-MFMA passes per product of the training Linears: 1 = D3DP_TRAIN_PASSES=1 (fp16 operands at their own '
                         'scale, fp32 accumulation), 3 = the split-fp16 default; set around the creation of the training model only')
+    p.add_argument('--train-attn-passes', type=int, default=None, choices=[1, 3],
+                   help='fp16-MFMA passes per product of the split-fp16 training attention: 1 = D3DP_TRAIN_ATTN_PASSES=1 (q, k, v, dO, P '
+                        'and dS rounded once to fp16 at their scale, fp32 accumulation), 3 = the split-fp16 default; set around the '
+                        'creation of the training model only')
     p.add_argument('--train-long-attn', action='store_true',
                    help='D3DP_TRAIN_LONG_ATTN=chunked: the fp32 attention backward of the training step on its chunked kernels -- '
                         'trains at any -cs and -f (e.g. -cs 1024 -f 243, -cs 96 -f 351); set around the creation of the training model only')
@@ -204,6 +208,24 @@ def train_passes_env(passes):
 
 
 @contextlib.contextmanager
+def train_attn_passes_env(passes):
+    """D3DP_TRAIN_ATTN_PASSES=<passes> inside the block (None: the environment as it is), restored on exit.  The library reads the
+    switch when a TRAIN context is created -- the training model's first step -- and for no context of another mode."""
+    if passes is None:
+        yield
+        return
+    saved = os.environ.get("D3DP_TRAIN_ATTN_PASSES")
+    os.environ["D3DP_TRAIN_ATTN_PASSES"] = str(passes)
+    try:
+        yield
+    finally:
+        if saved is None:
+            os.environ.pop("D3DP_TRAIN_ATTN_PASSES", None)
+        else:
+            os.environ["D3DP_TRAIN_ATTN_PASSES"] = saved
+
+
+@contextlib.contextmanager
 def train_long_attn_env(on):
     """D3DP_TRAIN_LONG_ATTN=chunked inside the block (false: the environment as it is), restored on exit.  The library reads the switch
     when a TRAIN context is created -- the training model's first step -- and for no context of another mode."""
@@ -235,9 +257,10 @@ def run_train(args, rank, world, device):
     model_eval = D3DP(args, kl, kr, is_train=False, numerics=args.numerics).to(device)
     if not args.resume:
         model_train.load_state_dict(make_state_dict(7, args.cs, args.dep, args.number_of_frames), strict=False)
-    # --train-passes / --train-long-attn: the TRAIN context is created HERE, inside the switch's block, instead of at the first step (the eval model's
+    # --train-passes / --train-attn-passes / --train-long-attn: the TRAIN context is created HERE, inside the switch's block, instead of at the first step (the eval model's
     # contexts, created later in the same process, never see the variable)
-    with train_passes_env(args.train_passes), train_long_attn_env(getattr(args, 'train_long_attn', False)):
+    with train_passes_env(args.train_passes), train_attn_passes_env(getattr(args, 'train_attn_passes', None)), \
+            train_long_attn_env(getattr(args, 'train_long_attn', False)):
         model_train.pose_estimator._context(device)
         print('INFO: training arithmetic:', model_train.pose_estimator.train_arithmetic())
     n_params = sum(p.numel() for p in model_train.parameters())

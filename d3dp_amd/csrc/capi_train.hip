@@ -369,7 +369,7 @@ int d3dp_train_forward(d3dp_ctx* c, const float* x2d, const float* x3d, const in
     auto attention = [&]() -> int {                      // (the launcher's own return code)
       if (ax2)
         return d3dp_train_attn_x2_fwd(S + L.o_qkv, S + L.o_att, ws + L.stats_x2 + (size_t)blk * L.stats_x2_stride, n_seq, map, C,
-                                      g.heads, x2->qkv_amax(blk), slot(4 * blk + 1), st, att_op, T, att_tp, att_un);
+                                      g.heads, x2->qkv_amax(blk), slot(4 * blk + 1), st, att_op, T, att_tp, att_un, P.attn_passes);
       if (kind == 1 && P.attn_t_f32_mfma)                // temporal axis on the fp32 matrix cores (bitwise an fp32 fmaf chain per product)
         return d3dp_launch_attn_temporal_f32(0, S + L.o_qkv, S + L.o_att, n_seq, map, C, g.heads, st);
       return d3dp_launch_attn_rows(0, S + L.o_qkv, S + L.o_att, n_seq, map, C, g.heads, st, slot(4 * blk + 1));
@@ -632,7 +632,7 @@ int d3dp_train_backward(d3dp_ctx* c, const float* x2d, const float* x3d, const i
         TP(part == 2 ? (kind ? T_ATTN_BKV_T : T_ATTN_BKV_S) : (kind ? T_ATTN_BQ_T : T_ATTN_BQ_S),
            d3dp_train_attn_x2_bwd(S + L.o_qkv, S + L.o_att, dB, dqkv, ws + L.stats_x2 + (size_t)blk * L.stats_x2_stride,
                                   kind ? B * J : B * F, kind ? temporal_map(F, J) : spatial_map(F, J), C, g.heads,
-                                  x2->qkv_amax(blk), pado, paq, st, part));
+                                  x2->qkv_amax(blk), pado, paq, st, part, P.attn_passes));
       ps_dqkv = pq;
     } else {
       LAUNCH_TRY(dgrad(blk, kProj, dy, dB));                                                                            // d att

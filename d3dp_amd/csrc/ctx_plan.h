@@ -17,7 +17,8 @@ struct CtxEnv {
   const char *exact_impl = nullptr, *long_attn = nullptr, *no_fold = nullptr, *defer_norm = nullptr, *train_impl = nullptr,
              *train_overlap = nullptr, *train_gelu = nullptr, *train_wgrad = nullptr, *train_ln_operand = nullptr, *train_tail = nullptr,
              *train_attn = nullptr, *train_passes = nullptr, *fast_impl = nullptr, *fast16_range = nullptr, *x2_skew = nullptr,
-             *x2_pp = nullptr, *x2_wide = nullptr, *seq_pad = nullptr, *fold_ln = nullptr, *train_long_attn = nullptr;
+             *x2_pp = nullptr, *x2_wide = nullptr, *seq_pad = nullptr, *fold_ln = nullptr, *train_long_attn = nullptr,
+             *train_attn_passes = nullptr;
   static CtxEnv from_process() {
     CtxEnv e;
     e.exact_impl = getenv("D3DP_EXACT_IMPL");                 // bf16x3 | f32: cross-check implementations of EXACT mode; f16x2: opt-in at 192 ... 448
@@ -40,6 +41,7 @@ struct CtxEnv {
     e.seq_pad = getenv("D3DP_SEQ_PAD");                       // 0 | 1: experiment, the sequence padding of the skewed schedule without it / the reverse
     e.fold_ln = getenv("D3DP_FOLD_LN");                       // 1: experiment, norm2 folded into proj / fc1
     e.train_long_attn = getenv("D3DP_TRAIN_LONG_ATTN");       // chunked: opt-in, the fp32 training attention backward at any sequence length
+    e.train_attn_passes = getenv("D3DP_TRAIN_ATTN_PASSES");   // 1: opt-in, one fp16-MFMA pass per product of the split-fp16 training attention
     return e;
   }
 };
@@ -64,6 +66,10 @@ struct CtxPlan {
   int train_passes = 3;          // D3DP_TRAIN_PASSES=1 (TRAIN contexts with train_x2 alone): every product of X2Train's Linears --
                                  // forward, dgrad, both wgrad forms -- as ONE fp16-MFMA pass hi(A) x hi(W): the hi plane of a split operand
                                  // is that tensor rounded to fp16 at its own power-of-two scale, so nothing else in the step changes
+  int train_attn_passes = 3;     // D3DP_TRAIN_ATTN_PASSES=1 (TRAIN contexts alone): every attention of the step that runs on the unpadded
+                                 // kernels of train_attn.hip -- both axes, or the temporal one under D3DP_TRAIN_ATTN=x2t -- runs each of
+                                 // its products (S, O; S, dP, dQ, dK, dV) as ONE fp16-MFMA pass on operands rounded once to fp16 at
+                                 // their device-side scale, from one-plane LDS images (train_attn_1p.hip)
   int exact_impl_req = 0;        // what D3DP_EXACT_IMPL asked for (0 = f16x2, 1 = bf16x3, 2 = f32): d3dp_ctx::exact_impl starts from it
   bool long_rows = false;        // D3DP_LONG_ATTN=rows: the row-kernel cross-check
   bool fold = true;              // proj / fc2 add into the residual stream in their epilogue (d3dp_ctx::fold_resid)
@@ -290,6 +296,32 @@ inline int plan_context(const d3dp_cfg& g, const CtxEnv& e, bool variants_built,
         return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_PASSES=1 beside D3DP_TRAIN_WGRAD=each / D3DP_TRAIN_TAIL=split / D3DP_TRAIN_GELU=pass / "
                                   "D3DP_TRAIN_LN_OPERAND=pass: the superseded launch forms have no one-pass form");
       p.train_passes = 1;
+    }
+  }
+  // 7a. D3DP_TRAIN_ATTN_PASSES (TRAIN contexts alone; behind step 7 so that every earlier refusal keeps its place): =1 runs every
+  // product of the split-fp16 training attention as one fp16-MFMA pass (train_attn_1p.hip); =3 names the default.  It exists where at
+  // least one axis runs train_attn.hip UNPADDED: the split-fp16 Linears (their epilogues leave the device-side scales), head dim 64,
+  // 32 or 16, and not D3DP_TRAIN_ATTN=f32.  Under D3DP_TRAIN_ATTN=x2t it applies to the temporal axis alone.  D3DP_TRAIN_PASSES,
+  // D3DP_TRAIN_OVERLAP, D3DP_TRAIN_LONG_ATTN and D3DP_TRAIN_ATTN_BWD compose with it.
+  if (train && e.train_attn_passes) {
+    if (strcmp(e.train_attn_passes, "1") && strcmp(e.train_attn_passes, "3"))
+      return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ATTN_PASSES=%.32s: the values a TRAIN context takes are D3DP_TRAIN_ATTN_PASSES=1 (one fp16-MFMA "
+                                "pass per product of the split-fp16 training attention) and 3 (the default)", e.train_attn_passes);
+    if (e.train_attn_passes[0] == '1') {
+      if (!train_linears_split(p, g))
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ATTN_PASSES=1 exists for the split-fp16 training attention; channels=%d%s trains on the fp32 "
+                                  "path (its attention runs the fp32 kernels, which have no one-pass form)", g.channels,
+                    train_f32 ? " under D3DP_TRAIN_IMPL=f32" : "");
+      if (hd == 24 || hd == 40 || hd == 48 || hd == 56)
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ATTN_PASSES=1 at head dim %d (channels=%d heads=%d): the padded forms of the split-fp16 "
+                                  "training attention have no one-pass form", hd, g.channels, g.heads);
+      if (!mfma_head_dim(hd))
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ATTN_PASSES=1 at head dim %d (channels=%d heads=%d): the one-pass training attention exists at "
+                                  "head dims 64, 32 and 16 (this head dim runs the fp32 attention kernels)", hd, g.channels, g.heads);
+      if (p.train_attn_x2 == 0)
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ATTN_PASSES=1 beside D3DP_TRAIN_ATTN=f32: both axes then run the fp32 attention kernels, which "
+                                  "have no one-pass form");
+      p.train_attn_passes = 1;
     }
   }
   // 8. The EXACT cross-check implementations: bf16x3 exists at the instantiated widths; a width neither instantiated nor padded

@@ -337,15 +337,20 @@ int d3dp_train_attn_bwd(const float* qkv, const float* o, const float* dout, flo
 // (optional): absmax slot of the result.
 int d3dp_train_attn_x2_fwd(const float* qkv, float* out, void* stats, int n_seq, SeqMap map, int C, int heads,
                            const unsigned* amax_qkv, unsigned* amax_out, hipStream_t st, void* op = nullptr, int T = 0, int Tp = 0,
-                           float* op_unscale = nullptr);
+                           float* op_unscale = nullptr, int passes = 3);
 int d3dp_train_attn_x2_bwd(const float* qkv, const float* o, const float* dout, float* dqkv, void* stats, int n_seq, SeqMap map,
                            int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
-                           hipStream_t st, int part = 0);
+                           hipStream_t st, int part = 0, int passes = 3);
 // train_attn_pad.hip: the padded-head instantiations behind the two launchers above (which: 0 = forward, 1 = both backward passes,
 // 2 = pass Q alone, 3 = pass KV alone); called by train_attn.hip only
 int d3dp_train_attn_x2_padded(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats,
                               int n_seq, SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do,
                               unsigned* amax_out, hipStream_t st);
+// train_attn_1p.hip: the one-pass instantiations (passes = 1: every product as ONE fp16-MFMA pass on the hi planes, one-plane LDS
+// images; head dims 64 / 32 / 16) behind the same two launchers; called by train_attn.hip only
+int d3dp_train_attn_x2_1p(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats,
+                          int n_seq, SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do,
+                          unsigned* amax_out, hipStream_t st, void* op, int T, int Tp, float* op_unscale);
 int d3dp_train_embed_bwd(const float* dx, const float* x2d, const float* x3d, float* part, int T, int C, hipStream_t st);
 int d3dp_train_head_linear(const float* z, const float* w, const float* b, float* out, int T, int C, hipStream_t st);
 int d3dp_train_head_bwd(const float* g, const float* z, const float* w, float* dz, float* part, int* rows, int T, int C,

@@ -86,11 +86,24 @@ __device__ __forceinline__ void ta_split8(const float4 a, const float4 b, f16x8&
 #pragma unroll
   for (int e = 0; e < 8; ++e) { f16 h, l; split2h_scaled(v[e] * sc, h, l); hi[e] = h; lo[e] = l; }
 }
+// PASSES (template parameter of everything below that holds three-pass logic, default 3): the fp16-MFMA passes per product.
+//   3: x 2^s = hi + lo, lo.hi + hi.lo + hi.hi into one fp32 accumulator; an image is two planes (hi | lo).
+//   1 (train_attn_1p.hip, D3DP_TRAIN_ATTN_PASSES=1): the hi value alone -- the operand rounded ONCE to fp16 at its scale -- one MFMA
+//      chain per product, and an image is ONE plane: no lo value is formed, stored or read anywhere.
+// ta_planes is the ONE constant the kernels' image offsets and the launcher's LDS sizes both derive the plane count from: a mismatch
+// between the two would be an out-of-bounds LDS access, not a wrong digit.
+constexpr int ta_planes(int passes) { return passes == 1 ? 1 : 2; }
+// the hi halves of ta_split8 alone: fp16(v sc)
+__device__ __forceinline__ void ta_round8(const float4 a, const float4 b, f16x8& hi, float sc) {
+  const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+  for (int e = 0; e < 8; ++e) hi[e] = (f16)(v[e] * sc);
+}
 
 // rows [0, n) x HD channels of an fp32 matrix (row stride `rs` floats) -> the hi / lo images (values x sc); rows [n, NK)
 // zero.  Four 16-byte slots per thread and pass, all loads of a pass in flight before the first conversion.
 // PAD: the matrix has hdt < HD channels; the slots behind them are not loaded and hold zeros.
-template <int NK, int NT, int HD = 64, bool PAD = false>
+template <int NK, int NT, int HD = 64, bool PAD = false, int PASSES = 3>
 __device__ __forceinline__ void ta_stage(const float* __restrict__ src, size_t rs, int n, float sc, char* img, int tid, int hdt = HD) {
   constexpr int ROWB = 2 * HD, SL = HD / 8, LS = HD == 64 ? 3 : HD == 32 ? 2 : 1;   // bytes / 16-byte slots (2^LS) of an image row
   constexpr int PLANE = NK * ROWB;
@@ -114,6 +127,11 @@ __device__ __forceinline__ void ta_stage(const float* __restrict__ src, size_t r
     for (int u = 0; u < 4; ++u) {
       const int idx = i0 + u * NT + tid, row = idx >> LS, slot = idx & (SL - 1);
       if (idx < ITEMS) {
+        if constexpr (PASSES == 1) {                   // one plane: the value rounded once
+          f16x8 hi;
+          ta_round8(a[u], b[u], hi, sc);
+          *reinterpret_cast<f16x8*>(img + row * ROWB + ((slot ^ ta_sw<HD>(row)) << 4)) = hi;
+        } else {
         f16x8 hi, lo;
 #if defined(D3DP_TA_PROBE) && D3DP_TA_PROBE == 2
         hi = __builtin_bit_cast(f16x8, a[u]); lo = __builtin_bit_cast(f16x8, b[u]);
@@ -123,6 +141,7 @@ __device__ __forceinline__ void ta_stage(const float* __restrict__ src, size_t r
         const int off = row * ROWB + ((slot ^ ta_sw<HD>(row)) << 4);
         *reinterpret_cast<f16x8*>(img + off) = hi;
         *reinterpret_cast<f16x8*>(img + PLANE + off) = lo;
+        }
       }
     }
   }
@@ -131,7 +150,7 @@ __device__ __forceinline__ void ta_stage(const float* __restrict__ src, size_t r
 // The same for NS matrices at once: every matrix's loads of a pass are in flight before the first conversion -- ONE exposed memory round
 // trip per chunk instead of one per operand (round 6: with the operands staged one after the other the loads' latency, not the
 // split arithmetic, was 20 - 40 % of the training attention kernels: D3DP_TA_PROBE builds).  rows [0, n) valid for all of them.
-template <int NK, int NT, int NS, int HD = 64, bool PAD = false>
+template <int NK, int NT, int NS, int HD = 64, bool PAD = false, int PASSES = 3>
 __device__ __forceinline__ void ta_stage_many(const float* const (&src)[NS], const size_t (&rs)[NS], const float (&sc)[NS],
                                               char* const (&img)[NS], int n, int tid, int hdt = HD) {
   constexpr int ROWB = 2 * HD, SL = HD / 8, LS = HD == 64 ? 3 : HD == 32 ? 2 : 1;
@@ -160,6 +179,11 @@ __device__ __forceinline__ void ta_stage_many(const float* const (&src)[NS], con
       for (int u = 0; u < 4; ++u) {
         const int idx = i0 + u * NT + tid, row = idx >> LS, slot = idx & (SL - 1);
         if (idx < ITEMS) {
+          if constexpr (PASSES == 1) {
+            f16x8 hi;
+            ta_round8(a[s][u], b[s][u], hi, sc[s]);
+            *reinterpret_cast<f16x8*>(img[s] + row * ROWB + ((slot ^ ta_sw<HD>(row)) << 4)) = hi;
+          } else {
           f16x8 hi, lo;
 #if defined(D3DP_TA_PROBE) && D3DP_TA_PROBE == 2
           hi = __builtin_bit_cast(f16x8, a[s][u]); lo = __builtin_bit_cast(f16x8, b[s][u]);
@@ -169,6 +193,7 @@ __device__ __forceinline__ void ta_stage_many(const float* const (&src)[NS], con
           const int off = row * ROWB + ((slot ^ ta_sw<HD>(row)) << 4);
           *reinterpret_cast<f16x8*>(img[s] + off) = hi;
           *reinterpret_cast<f16x8*>(img[s] + PLANE + off) = lo;
+          }
         }
       }
   }
@@ -219,11 +244,27 @@ __device__ __forceinline__ f16x8 ta_tr(const char* p) {
 // the two 16-row tiles t, t + 1 of  (image rows) x (a register operand): acc_a / acc_b [row 16 t' + 4 fg + r][column lane & 15]
 //   = sum_d img[row][d] x[column][d]  -- lo.hi + hi.lo + hi.hi over the two 32-deep halves of d (HD = 64), the one 32-deep MFMA
 //   (HD = 32) or the one 16-deep MFMA (HD = 16) per pass.
-template <int PLANE, int HD = 64>
+// PASSES = 1: hi.hi alone; xl is not read and nothing PLANE bytes behind a fragment is.
+template <int PLANE, int HD = 64, int PASSES = 3>
 __device__ __forceinline__ void ta_rows_pair(const TAFragT<HD>& f, int t, const typename TAHead<HD>::frag (&xh)[TAHead<HD>::NQ],
                                              const typename TAHead<HD>::frag (&xl)[TAHead<HD>::NQ], f32x4& a, f32x4& b) {
   constexpr int TILE = 32 * HD;                        // 16 rows
-  if constexpr (HD == 64) {
+  if constexpr (PASSES == 1) {
+    typedef typename TAHead<HD>::frag frag;
+    const char* p0 = f.r0 + t * TILE;
+    const frag ah0 = *reinterpret_cast<const frag*>(p0), bh0 = *reinterpret_cast<const frag*>(p0 + TILE);
+    a = (f32x4){0.f, 0.f, 0.f, 0.f}; b = a;
+    if constexpr (HD == 64) {
+      const char* p1 = f.r1 + t * TILE;
+      const frag ah1 = *reinterpret_cast<const frag*>(p1), bh1 = *reinterpret_cast<const frag*>(p1 + TILE);
+      TA_MFMA(ah0, xh[0], a); TA_MFMA(bh0, xh[0], b);
+      TA_MFMA(ah1, xh[1], a); TA_MFMA(bh1, xh[1], b);
+    } else if constexpr (HD == 32) {
+      TA_MFMA(ah0, xh[0], a); TA_MFMA(bh0, xh[0], b);
+    } else {
+      TA_MFMA16(ah0, xh[0], a); TA_MFMA16(bh0, xh[0], b);
+    }
+  } else if constexpr (HD == 64) {
     const char* p0 = f.r0 + t * 2048;
     const char* p1 = f.r1 + t * 2048;
     const f16x8 al0 = *reinterpret_cast<const f16x8*>(p0 + PLANE), al1 = *reinterpret_cast<const f16x8*>(p1 + PLANE);
@@ -257,9 +298,18 @@ __device__ __forceinline__ void ta_rows_pair(const TAFragT<HD>& f, int t, const 
 // acc[dn][channel dn 16 + 4 fg + i][column] += sum over the 32 image rows of chunk c of img[row][channel] y[row][column]
 // (y as a split register operand in the k order of the transposed fragments: rows 4 fg + r of tile 2 c, then of tile 2 c + 1)
 // HD / 16 channel tiles, 32-deep MFMAs at every head dim.
-template <int PLANE, int HD = 64>
+// PASSES = 1: hi.hi alone; yl is not read.
+template <int PLANE, int HD = 64, int PASSES = 3>
 __device__ __forceinline__ void ta_tr_chunk(const TAFragT<HD>& f, int c, const f16x8& yh, const f16x8& yl, f32x4 (&acc)[HD / 16]) {
   constexpr int ND = HD / 16, CHUNK = 64 * HD;         // 32 rows
+  if constexpr (PASSES == 1) {
+    f16x8 t1[ND];
+#pragma unroll
+    for (int dn = 0; dn < ND; ++dn) t1[dn] = ta_tr<HD>(f.t[dn] + c * CHUNK);
+#pragma unroll
+    for (int dn = 0; dn < ND; ++dn) TA_MFMA(t1[dn], yh, acc[dn]);
+    return;
+  }
   f16x8 th[ND], tl[ND];
 #pragma unroll
   for (int dn = 0; dn < ND; ++dn) { th[dn] = ta_tr<HD>(f.t[dn] + c * CHUNK); tl[dn] = ta_tr<HD>(f.t[dn] + c * CHUNK + PLANE); }
@@ -274,11 +324,26 @@ __device__ __forceinline__ void ta_tr_chunk(const TAFragT<HD>& f, int c, const f
 // this lane's HD / 4 values of a [.][HD] fp32 row as a split register operand (column operand of ta_rows_pair): channels
 // 8 fg .. + 7 and 32 + 8 fg .. + 7 (HD = 64), 8 fg .. + 7 (HD = 32), 4 fg .. + 3 (HD = 16)
 // (PAD: the row has hdt < HD channels; a group of 8 at or behind hdt is not loaded and is zero)
-template <int HD = 64, bool PAD = false>
+// PASSES = 1: h alone, l is left untouched.
+template <int HD = 64, bool PAD = false, int PASSES = 3>
 __device__ __forceinline__ void ta_load_row_op(const float* row, int fg, float sc, typename TAHead<HD>::frag (&h)[TAHead<HD>::NQ],
                                                typename TAHead<HD>::frag (&l)[TAHead<HD>::NQ], int hdt = HD) {
   static_assert(!PAD || HD >= 32, "padded heads: 8-channel groups");
-  if constexpr (HD == 16) {
+  static_assert(!PAD || PASSES == 3, "padded heads: no one-pass form");
+  if constexpr (PASSES == 1) {
+    if constexpr (HD == 16) {
+      const float4 v = *reinterpret_cast<const float4*>(row + fg * 4);
+      const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) h[0][e] = (f16)(x[e] * sc);
+    } else {
+#pragma unroll
+      for (int half = 0; half < TAHead<HD>::NQ; ++half) {
+        const float* p = row + half * 32 + fg * 8;
+        ta_round8(*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4), h[half], sc);
+      }
+    }
+  } else if constexpr (HD == 16) {
     const float4 v = *reinterpret_cast<const float4*>(row + fg * 4);
     const float x[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -299,8 +364,15 @@ __device__ __forceinline__ void ta_load_row_op(const float* row, int fg, float s
 }
 // eight values (two tiles x four rows) -> one split register operand at the power of two 2^(140 - eb) (eb: biased exponent
 // the caller keeps >= that of the largest magnitude: |y| 2^(140 - eb) < 2^14)
+// (PASSES = 1: h = fp16(y 2^(140 - eb)) alone, l untouched)
+template <int PASSES = 3>
 __device__ __forceinline__ void ta_split_run(const float (&y)[8], int eb, f16x8& h, f16x8& l) {
   const float sc = __uint_as_float((unsigned)(267 - eb) << 23);
+  if constexpr (PASSES == 1) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) h[e] = (f16)(y[e] * sc);
+    return;
+  }
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const float v = ta_opaque(y[e] * sc);              // (opaque: both halves must round the SAME number)

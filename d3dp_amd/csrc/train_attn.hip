@@ -5,6 +5,10 @@
 // Head dims 24 and 40 / 48 / 56 (`-cs` 192 and 320 / 384 / 448 under D3DP_TRAIN_IMPL=f16x2) run PADDED forms of the head dim 32 / 64
 // kernels (template parameter PAD): the fp32 tensors keep their true layout, the zero channels exist in the LDS images and the
 // register operands only (ta_common.h), the softmax exponent is the true head dim's.
+// PASSES (last template parameter of every kernel and of ta_launch, default 3): the fp16-MFMA passes per product.  PASSES = 1
+// (D3DP_TRAIN_ATTN_PASSES=1; instantiated in train_attn_1p.hip for head dims 64 / 32 / 16) keeps the hi value of every operand alone
+// -- q, k, v, dO, P x 2^10 and dS each rounded ONCE to fp16 at the scale described below -- runs every product as one MFMA chain and
+// holds ONE plane per LDS image (ta_planes, ta_common.h); scales, softmax, statistics, tiles, chunks and launches are unchanged.
 //
 // Round 4 ran the temporal forward and both backward passes on the FP32 matrix cores (v_mfma_f32_16x16x4_f32: 1/16 of the fp16
 // rate; 5.9 ms of the 27 ms configs[4] step).  Here every product runs on split-fp16 operands like the step's Linears
@@ -53,17 +57,17 @@ __device__ __forceinline__ void ta_block_amax(float am, unsigned* amax, float* p
 // forward
 // (NKC: key tiles per LDS chunk.  Round 6: the images hold 128 keys at a time -- the online softmax runs over key pairs anyway --
 //  so a 243-frame problem needs 64 KiB instead of 128 and TWO workgroups share a CU: four waves per SIMD instead of two)
-template <int NKT, int NW, int NKC, int HD, bool PAD = false>
+template <int NKT, int NW, int NKC, int HD, bool PAD = false, int PASSES = 3>
 __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                            TAStat* __restrict__ stats, SeqMap map, int C, int heads, int groups,
                                                            int n_work, const unsigned* __restrict__ amax_qkv,
                                                            unsigned* __restrict__ amax_out, f16* __restrict__ op, int T, int Tp,
                                                            float* __restrict__ op_unscale) {
-  constexpr int NK = 16 * NKC, PLANE = NK * 2 * HD, ND = HD / 16;
+  constexpr int NK = 16 * NKC, PLANE = NK * 2 * HD, ND = HD / 16, NPL = ta_planes(PASSES);   // (NPL planes per image: ta_common.h)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* kimg = smem;
-  char* vimg = smem + 2 * PLANE;
-  float* part = reinterpret_cast<float*>(smem + 4 * PLANE);
+  char* vimg = smem + NPL * PLANE;
+  float* part = reinterpret_cast<float*>(smem + 2 * NPL * PLANE);
   const int n = map.n_tok;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t ld = (size_t)3 * C, rs = (size_t)map.tok_stride * ld;
@@ -92,7 +96,7 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
   const int q = qt * 16 + fi;
   const size_t tok = (size_t)(base + min(q, n - 1) * map.tok_stride);
   typename TAHead<HD>::frag qh[TAHead<HD>::NQ], ql[TAHead<HD>::NQ];
-  if (active) ta_load_row_op<HD, PAD>(qkv + tok * ld + head * hd, fg, sq, qh, ql, hd);
+  if (active) ta_load_row_op<HD, PAD, PASSES>(qkv + tok * ld + head * hd, fg, sq, qh, ql, hd);
   const TAFragT<HD> fk = ta_frag<HD>(kimg, lane), fv = ta_frag<HD>(vimg, lane);
   const float cexp = scale * kLog2e / (sq * sq);   // raw accumulator -> logit in base-2 units
   float mrun = -INFINITY, lrun = 0.f;                  // running row maximum (base-2 logit units) and denominator
@@ -107,7 +111,7 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
     const size_t rs2[2] = {rs, rs};
     const float sc2[2] = {sq, sq};
     char* const img2[2] = {kimg, vimg};
-    ta_stage_many<NK, NW * 64, 2, HD, PAD>(src2, rs2, sc2, img2, n - 16 * kc, tid, hd);
+    ta_stage_many<NK, NW * 64, 2, HD, PAD, PASSES>(src2, rs2, sc2, img2, n - 16 * kc, tid, hd);
   }
   __syncthreads();
   if (active) {
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
     for (int t = 0; t < NKC; t += 2) {
       if (16 * (kc + t) >= n) break;                   // (uniform: the rest of the chunk lies behind the sequence)
       f32x4 a, b;
-      ta_rows_pair<PLANE>(fk, t, qh, ql, a, b);
+      ta_rows_pair<PLANE, HD, PASSES>(fk, t, qh, ql, a, b);
       float s[8];
 #pragma unroll
       for (int r = 0; r < 4; ++r) { s[r] = a[r] * cexp; s[4 + r] = b[r] * cexp; }
@@ -142,14 +146,14 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
         psum += y;
         const f16 hh = (f16)y;
         ph[e] = hh;
-        pl[e] = (f16)fmaf(y, 1.0f, -(float)hh);
+        if constexpr (PASSES == 3) pl[e] = (f16)fmaf(y, 1.0f, -(float)hh);
       }
       psum += __shfl_xor(psum, 16, 64);
       psum += __shfl_xor(psum, 32, 64);
       lrun = fmaf(lrun, alpha, psum);
 #pragma unroll
       for (int dn = 0; dn < ND; ++dn) o[dn] *= alpha;
-      ta_tr_chunk<PLANE>(fv, t >> 1, ph, pl, o);
+      ta_tr_chunk<PLANE, HD, PASSES>(fv, t >> 1, ph, PASSES == 1 ? ph : pl, o);   // (one pass: no pl exists; the lo argument is not read)
     }
   }
   }
@@ -184,17 +188,17 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
 
 // ------------------------------------------------------------------------------------------------------------------------
 // backward, pass Q: dQ (and D_i into the statistics)
-template <int NKT, int NW, int NKC, int WPE, int HD, bool PAD = false>
+template <int NKT, int NW, int NKC, int WPE, int HD, bool PAD = false, int PASSES = 3>
 __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                              const float* __restrict__ dout, float* __restrict__ dqkv,
                                                              TAStat* __restrict__ stats, SeqMap map, int C, int heads, int groups,
                                                              int n_work, const unsigned* __restrict__ amax_qkv,
                                                              const unsigned* __restrict__ amax_do, unsigned* __restrict__ amax_out) {
-  constexpr int NK = 16 * NKC, PLANE = NK * 2 * HD, ND = HD / 16;      // (the images hold NKC key tiles at a time: see tattn_fwd_kernel)
+  constexpr int NK = 16 * NKC, PLANE = NK * 2 * HD, ND = HD / 16, NPL = ta_planes(PASSES);      // (the images hold NKC key tiles at a time: see tattn_fwd_kernel)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* kimg = smem;
-  char* vimg = smem + 2 * PLANE;
-  float* part = reinterpret_cast<float*>(smem + 4 * PLANE);
+  char* vimg = smem + NPL * PLANE;
+  float* part = reinterpret_cast<float*>(smem + 2 * NPL * PLANE);
   const int n = map.n_tok;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t ld = (size_t)3 * C, rs = (size_t)map.tok_stride * ld;
@@ -215,8 +219,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
   typename TAHead<HD>::frag qh[TAHead<HD>::NQ], ql[TAHead<HD>::NQ], gh[TAHead<HD>::NQ], gl[TAHead<HD>::NQ];
   float D = 0.f, L = 0.f;
   if (active) {
-    ta_load_row_op<HD, PAD>(qkv + tok * ld + head * hd, fg, sq, qh, ql, hd);
-    ta_load_row_op<HD, PAD>(dout + tok * C + head * hd, fg, sg, gh, gl, hd);
+    ta_load_row_op<HD, PAD, PASSES>(qkv + tok * ld + head * hd, fg, sq, qh, ql, hd);
+    ta_load_row_op<HD, PAD, PASSES>(dout + tok * C + head * hd, fg, sg, gh, gl, hd);
     {
       const float* gs = dout + tok * C + head * hd;
       const float* os = o + tok * C + head * hd;
@@ -256,7 +260,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
     const size_t rs2[2] = {rs, rs};
     const float sc2[2] = {sq, sq};
     char* const img2[2] = {kimg, vimg};
-    ta_stage_many<NK, NW * 64, 2, HD, PAD>(src2, rs2, sc2, img2, n - 16 * kc, tid, hd);
+    ta_stage_many<NK, NW * 64, 2, HD, PAD, PASSES>(src2, rs2, sc2, img2, n - 16 * kc, tid, hd);
   }
   __syncthreads();
   if (active) {
@@ -264,8 +268,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
     for (int t = 0; t < NKC; t += 2) {
       if (16 * (kc + t) >= n) break;                   // (uniform)
       f32x4 a, b, c, d;
-      ta_rows_pair<PLANE>(fk, t, qh, ql, a, b);        // S^T  [key][query]
-      ta_rows_pair<PLANE>(fv, t, gh, gl, c, d);        // dP^T [key][query]
+      ta_rows_pair<PLANE, HD, PASSES>(fk, t, qh, ql, a, b);        // S^T  [key][query]
+      ta_rows_pair<PLANE, HD, PASSES>(fv, t, gh, gl, c, d);        // dP^T [key][query]
       float ds[8];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -294,8 +298,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
         eb = en;
       }
       f16x8 sh, sl;
-      ta_split_run(ds, eb, sh, sl);
-      ta_tr_chunk<PLANE>(fk, t >> 1, sh, sl, dq);      // dQ^T[d][query] += K^T dS^T
+      ta_split_run<PASSES>(ds, eb, sh, sl);
+      ta_tr_chunk<PLANE, HD, PASSES>(fk, t >> 1, sh, sl, dq);      // dQ^T[d][query] += K^T dS^T
     }
   }
   }
@@ -320,18 +324,18 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_q_kernel(const float* 
 
 // ------------------------------------------------------------------------------------------------------------------------
 // backward, pass KV: dK, dV
-template <int NKT, int NW, int NKC, int WPE, int HD, bool PAD = false>
+template <int NKT, int NW, int NKC, int WPE, int HD, bool PAD = false, int PASSES = 3>
 __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                               float* __restrict__ dqkv, const TAStat* __restrict__ stats,
                                                               SeqMap map, int C, int heads, int groups, int n_work,
                                                               const unsigned* __restrict__ amax_qkv,
                                                               const unsigned* __restrict__ amax_do, unsigned* __restrict__ amax_out) {
-  constexpr int NK = 16 * NKC, PLANE = NK * 2 * HD, ND = HD / 16;      // (the images hold NKC QUERY tiles at a time)
+  constexpr int NK = 16 * NKC, PLANE = NK * 2 * HD, ND = HD / 16, NPL = ta_planes(PASSES);      // (the images hold NKC QUERY tiles at a time)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* qimg = smem;
-  char* gimg = smem + 2 * PLANE;
-  float2* st = reinterpret_cast<float2*>(smem + 4 * PLANE);          // [NK] (L, D)
-  float* part = reinterpret_cast<float*>(smem + 4 * PLANE + NK * 8);
+  char* gimg = smem + NPL * PLANE;
+  float2* st = reinterpret_cast<float2*>(smem + 2 * NPL * PLANE);    // [NK] (L, D)
+  float* part = reinterpret_cast<float*>(smem + 2 * NPL * PLANE + NK * 8);
   const int n = map.n_tok;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t ld = (size_t)3 * C, rs = (size_t)map.tok_stride * ld;
@@ -351,8 +355,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
   const size_t tok = (size_t)(base + min(key, n - 1) * map.tok_stride);
   typename TAHead<HD>::frag kh[TAHead<HD>::NQ], kl[TAHead<HD>::NQ], vh[TAHead<HD>::NQ], vl[TAHead<HD>::NQ];
   if (active) {
-    ta_load_row_op<HD, PAD>(qkv + tok * ld + C + head * hd, fg, sq, kh, kl, hd);
-    ta_load_row_op<HD, PAD>(qkv + tok * ld + 2 * C + head * hd, fg, sq, vh, vl, hd);
+    ta_load_row_op<HD, PAD, PASSES>(qkv + tok * ld + C + head * hd, fg, sq, kh, kl, hd);
+    ta_load_row_op<HD, PAD, PASSES>(qkv + tok * ld + 2 * C + head * hd, fg, sq, vh, vl, hd);
   }
   const TAFragT<HD> fq = ta_frag<HD>(qimg, lane), fgr = ta_frag<HD>(gimg, lane);
   const float cexp = scale * kLog2e / (sq * sq);
@@ -366,8 +370,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
   if (unit != (int)blockIdx.x || qc != 0) __syncthreads();
   // (one operand after the other here: both at once -- ta_stage_many, as in the forward pass and pass Q -- costs this 200-register
   //  kernel more than the second round trip: 98 -> 105 us)
-  ta_stage<NK, NW * 64, HD, PAD>(qkv + (size_t)base * ld + (size_t)head * hd + (size_t)qc * 16 * rs, rs, n - 16 * qc, sq, qimg, tid, hd);
-  ta_stage<NK, NW * 64, HD, PAD>(dout + (size_t)base * C + (size_t)head * hd + (size_t)qc * 16 * map.tok_stride * C, (size_t)map.tok_stride * C,
+  ta_stage<NK, NW * 64, HD, PAD, PASSES>(qkv + (size_t)base * ld + (size_t)head * hd + (size_t)qc * 16 * rs, rs, n - 16 * qc, sq, qimg, tid, hd);
+  ta_stage<NK, NW * 64, HD, PAD, PASSES>(dout + (size_t)base * C + (size_t)head * hd + (size_t)qc * 16 * map.tok_stride * C, (size_t)map.tok_stride * C,
                         n - 16 * qc, sg, gimg, tid, hd);
   for (int i = tid; i < NK; i += NW * 64) {
     // rows >= n: their Q and dO image rows are zero, so any FINITE p and dS contribute nothing: L = +large keeps p = 0
@@ -381,8 +385,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
     for (int t = 0; t < NKC; t += 2) {
       if (16 * (qc + t) >= n) break;                   // (uniform)
       f32x4 a, b, c, d;
-      ta_rows_pair<PLANE>(fq, t, kh, kl, a, b);        // S  [query][key]
-      ta_rows_pair<PLANE>(fgr, t, vh, vl, c, d);       // dP [query][key]
+      ta_rows_pair<PLANE, HD, PASSES>(fq, t, kh, kl, a, b);        // S  [query][key]
+      ta_rows_pair<PLANE, HD, PASSES>(fgr, t, vh, vl, c, d);       // dP [query][key]
       float ds[8];
       f16x8 ph, pl;
 #pragma unroll
@@ -392,12 +396,16 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
         if (!live) { pa = 0.f; pb = 0.f; }
         ds[r] = pa * (fmaf(c[r], cdp, -sa.y)) * scale;
         ds[4 + r] = pb * (fmaf(d[r], cdp, -sb.y)) * scale;
+        if constexpr (PASSES == 1) {
+          ph[r] = (f16)(pa * 1024.0f); ph[4 + r] = (f16)(pb * 1024.0f);
+        } else {
         const float ya = ta_opaque(pa * 1024.0f), yb = ta_opaque(pb * 1024.0f);
         const f16 ha = (f16)ya, hb = (f16)yb;
         ph[r] = ha; pl[r] = (f16)(ya - (float)ha);
         ph[4 + r] = hb; pl[4 + r] = (f16)(yb - (float)hb);
+        }
       }
-      ta_tr_chunk<PLANE>(fgr, t >> 1, ph, pl, dv);     // dV^T[d][key] += dO^T P
+      ta_tr_chunk<PLANE, HD, PASSES>(fgr, t >> 1, ph, PASSES == 1 ? ph : pl, dv);     // dV^T[d][key] += dO^T P
       const int en = max(eb, ta_exp_of_max(ds));
       if (en != eb) {
 #pragma unroll
@@ -407,8 +415,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
         eb = en;
       }
       f16x8 sh, sl;
-      ta_split_run(ds, eb, sh, sl);
-      ta_tr_chunk<PLANE>(fq, t >> 1, sh, sl, dk);      // dK^T[d][key] += Q^T dS
+      ta_split_run<PASSES>(ds, eb, sh, sl);
+      ta_tr_chunk<PLANE, HD, PASSES>(fq, t >> 1, sh, sl, dk);      // dK^T[d][key] += Q^T dS
     }
   }
   }
@@ -441,20 +449,20 @@ __global__ __launch_bounds__(NW * 64, WPE) void tattn_bwd_kv_kernel(const float*
 // are row-fragment reads of the very images the other wave's products contract over -- and D_i = dO_i . O_i goes from pass Q to
 // pass KV through LDS instead of the statistics buffer.  Same products, same splits, same accumulation order as the two
 // kernels: bit-identical gradients (test_attention_backward_on_matrix_cores_matches_the_valu_kernels covers n = 9, 17 through it).
-template <int HD, bool PAD = false>
+template <int HD, bool PAD = false, int PASSES = 3>
 __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                               const float* __restrict__ dout, float* __restrict__ dqkv,
                                                               const TAStat* __restrict__ stats, SeqMap map, int C, int heads,
                                                               int n_work, const unsigned* __restrict__ amax_qkv,
                                                               const unsigned* __restrict__ amax_do, unsigned* __restrict__ amax_out) {
-  constexpr int NK = 32, PLANE = NK * 2 * HD, NW = 2, ND = HD / 16;
-  __shared__ __attribute__((aligned(16))) char smem[8 * PLANE];
+  constexpr int NK = 32, PLANE = NK * 2 * HD, NW = 2, ND = HD / 16, NPL = ta_planes(PASSES);
+  __shared__ __attribute__((aligned(16))) char smem[4 * NPL * PLANE];
   __shared__ float2 st[NK];                              // (L, D) of the sequence's queries
   __shared__ float part[NW];
   char* qimg = smem;
-  char* kimg = smem + 2 * PLANE;
-  char* vimg = smem + 4 * PLANE;
-  char* gimg = smem + 6 * PLANE;
+  char* kimg = smem + NPL * PLANE;
+  char* vimg = smem + 2 * NPL * PLANE;
+  char* gimg = smem + 3 * NPL * PLANE;
   const int n = map.n_tok;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fi = lane & 15, fg = lane >> 4;
@@ -469,10 +477,10 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
   constexpr int NQ = TAHead<HD>::NQ, TILE = 32 * HD;     // (16 image rows)
   auto row_op = [&](const TAFragT<HD>& f, int t, frag (&h)[NQ], frag (&l)[NQ]) {   // tile t's rows as a split register operand
     h[0] = *reinterpret_cast<const frag*>(f.r0 + t * TILE);
-    l[0] = *reinterpret_cast<const frag*>(f.r0 + t * TILE + PLANE);
+    if constexpr (PASSES == 3) l[0] = *reinterpret_cast<const frag*>(f.r0 + t * TILE + PLANE);
     if constexpr (NQ == 2) {
       h[1] = *reinterpret_cast<const frag*>(f.r1 + t * TILE);
-      l[1] = *reinterpret_cast<const frag*>(f.r1 + t * TILE + PLANE);
+      if constexpr (PASSES == 3) l[1] = *reinterpret_cast<const frag*>(f.r1 + t * TILE + PLANE);
     }
   };
   float am = 0.f;
@@ -487,7 +495,7 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
       const size_t rs4[4] = {rs, rs, rs, (size_t)map.tok_stride * C};
       const float sc4[4] = {sq, sq, sq, sg};
       char* const img4[4] = {qimg, kimg, vimg, gimg};
-      ta_stage_many<NK, NW * 64, 4, HD, PAD>(src4, rs4, sc4, img4, n, tid, hd);
+      ta_stage_many<NK, NW * 64, 4, HD, PAD, PASSES>(src4, rs4, sc4, img4, n, tid, hd);
     }
     const int row = wave * 16 + fi;                      // this lane's query (pass Q) and key (pass KV)
     const bool live = row < n;
@@ -520,8 +528,8 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
         row_op(fgr, wave, gh, gl);
         const float2 ld_ = st[row];
         f32x4 a, b, c, d;
-        ta_rows_pair<PLANE>(fk, 0, qh, ql, a, b);        // S^T  [key][query]
-        ta_rows_pair<PLANE>(fv, 0, gh, gl, c, d);        // dP^T [key][query]
+        ta_rows_pair<PLANE, HD, PASSES>(fk, 0, qh, ql, a, b);        // S^T  [key][query]
+        ta_rows_pair<PLANE, HD, PASSES>(fv, 0, gh, gl, c, d);        // dP^T [key][query]
         float ds[8];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -533,11 +541,11 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
         }
         const int eb = max(20, ta_exp_of_max(ds));
         f16x8 sh, sl;
-        ta_split_run(ds, eb, sh, sl);
+        ta_split_run<PASSES>(ds, eb, sh, sl);
         f32x4 dq[ND];
 #pragma unroll
         for (int dn = 0; dn < ND; ++dn) dq[dn] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        ta_tr_chunk<PLANE>(fk, 0, sh, sl, dq);           // dQ^T[d][query] = K^T dS^T
+        ta_tr_chunk<PLANE, HD, PASSES>(fk, 0, sh, sl, dq);           // dQ^T[d][query] = K^T dS^T
         if (live) {
           const float un = 1.0f / sq;
           float* dst = dqkv + tok * ld + head * hd + fg * 4;
@@ -557,8 +565,8 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
         row_op(fk, wave, kh, kl);
         row_op(fv, wave, vh, vl);
         f32x4 a, b, c, d;
-        ta_rows_pair<PLANE>(fq, 0, kh, kl, a, b);        // S  [query][key]
-        ta_rows_pair<PLANE>(fgr, 0, vh, vl, c, d);       // dP [query][key]
+        ta_rows_pair<PLANE, HD, PASSES>(fq, 0, kh, kl, a, b);        // S  [query][key]
+        ta_rows_pair<PLANE, HD, PASSES>(fgr, 0, vh, vl, c, d);       // dP [query][key]
         float ds[8];
         f16x8 ph, pl;
 #pragma unroll
@@ -568,19 +576,23 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
           if (!live) { pa = 0.f; pb = 0.f; }
           ds[r] = pa * (fmaf(c[r], cdp, -sa.y)) * scale;
           ds[4 + r] = pb * (fmaf(d[r], cdp, -sb.y)) * scale;
+          if constexpr (PASSES == 1) {
+            ph[r] = (f16)(pa * 1024.0f); ph[4 + r] = (f16)(pb * 1024.0f);
+          } else {
           const float ya = ta_opaque(pa * 1024.0f), yb = ta_opaque(pb * 1024.0f);
           const f16 ha = (f16)ya, hb = (f16)yb;
           ph[r] = ha; pl[r] = (f16)(ya - (float)ha);
           ph[4 + r] = hb; pl[4 + r] = (f16)(yb - (float)hb);
+          }
         }
         f32x4 dk[ND], dv[ND];
 #pragma unroll
         for (int dn = 0; dn < ND; ++dn) { dk[dn] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[dn] = dk[dn]; }
-        ta_tr_chunk<PLANE>(fgr, 0, ph, pl, dv);          // dV^T[d][key] = dO^T P
+        ta_tr_chunk<PLANE, HD, PASSES>(fgr, 0, ph, PASSES == 1 ? ph : pl, dv);          // dV^T[d][key] = dO^T P
         const int eb = max(20, ta_exp_of_max(ds));
         f16x8 sh, sl;
-        ta_split_run(ds, eb, sh, sl);
-        ta_tr_chunk<PLANE>(fq, 0, sh, sl, dk);           // dK^T[d][key] = Q^T dS
+        ta_split_run<PASSES>(ds, eb, sh, sl);
+        ta_tr_chunk<PLANE, HD, PASSES>(fq, 0, sh, sl, dk);           // dK^T[d][key] = Q^T dS
         if (live) {
           const float uk = 1.0f / sq, uv = 1.0f / (sg * 1024.0f);
           float* dst = dqkv + tok * ld + C + head * hd + fg * 4;
@@ -603,7 +615,7 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
 }
 
 struct TAOperand { f16* op; int T, Tp; float* unscale; };   // forward only: the output also as the next Linear's operand rows
-template <int NKT, int HD, bool PAD = false>
+template <int NKT, int HD, bool PAD = false, int PASSES = 3>
 int ta_launch(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats, int n_seq,
               SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
               hipStream_t st, TAOperand po = {nullptr, 0, 0, nullptr}) {
@@ -620,39 +632,43 @@ int ta_launch(int which, const float* qkv, const float* o, const float* dout, fl
   // waves per CU in all three kernels.
   // PAD: a true head dim of 24 (HD 32) or 40 / 48 / 56 (HD 64) in the images of HD -- LDS sizes, chunking, waves per workgroup and
   // register budgets are those of the HD instantiation (compiler's figures: profiles/train_widths.md); no operand rows.
+  // PASSES = 1 (train_attn_1p.hip): the same tiles, waves and chunk sizes; an image is ta_planes(PASSES) = 1 plane, so every LDS size
+  // below halves (a 243-frame forward or pass Q at head dim 64: 32 KiB + 64 B) -- the kernels' offsets read the same constant.
+  static_assert(!PAD || PASSES == 3, "padded heads: no one-pass form");
   if (PAD && po.op) return -1;                         // (never asked: ta_dispatch refuses it)
   constexpr int NKC_KV = (NKT > 16 || (HD < 64 && NKT > 8)) ? 8 : NKT;
   constexpr int WPE_KV = HD < 64 ? 4 : 2;
   constexpr int ROWB = 2 * HD;                         // bytes of an image row
-  const size_t lds = (size_t)4 * NKC * 16 * ROWB + 64, lds_kv = (size_t)4 * NKC_KV * 16 * ROWB + NKC_KV * 16 * 8 + 64, lds_fwd = lds;
+  constexpr int NPL = ta_planes(PASSES);               // planes per image; two images per kernel
+  const size_t lds = (size_t)2 * NPL * NKC * 16 * ROWB + 64, lds_kv = (size_t)2 * NPL * NKC_KV * 16 * ROWB + NKC_KV * 16 * 8 + 64, lds_fwd = lds;
   (void)NK;
   static PerDeviceOnce once;
   if (once.get([&](int) {
-        return d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_fwd_kernel<NKT, NW, NKC, HD, PAD>), 160 * 1024) < 0 ? -3
-               : d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_bwd_q_kernel<NKT, NW, NKC, 4, HD, PAD>), 160 * 1024) < 0 ? -3
-               : d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_bwd_kv_kernel<NKT, NW, NKC_KV, WPE_KV, HD, PAD>), 160 * 1024);
+        return d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_fwd_kernel<NKT, NW, NKC, HD, PAD, PASSES>), 160 * 1024) < 0 ? -3
+               : d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_bwd_q_kernel<NKT, NW, NKC, 4, HD, PAD, PASSES>), 160 * 1024) < 0 ? -3
+               : d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_bwd_kv_kernel<NKT, NW, NKC_KV, WPE_KV, HD, PAD, PASSES>), 160 * 1024);
       }) < 0) return -3;
   const int tiles = (map.n_tok + 15) / 16, groups = (tiles + NW - 1) / NW;
   const int n_work = n_seq * heads * groups;
   const dim3 grid(n_work < 2048 ? n_work : 2048), blk(NW * 64);   // (<= 2048 absmax atomics per launch)
   TAStat* s = reinterpret_cast<TAStat*>(stats);
   if (which == 0)
-    hipLaunchKernelGGL((tattn_fwd_kernel<NKT, NW, NKC, HD, PAD>), grid, blk, lds_fwd, st, qkv, out, s, map, C, heads, groups, n_work, amax_qkv, amax_out,
+    hipLaunchKernelGGL((tattn_fwd_kernel<NKT, NW, NKC, HD, PAD, PASSES>), grid, blk, lds_fwd, st, qkv, out, s, map, C, heads, groups, n_work, amax_qkv, amax_out,
                        po.op, po.T, po.Tp, po.unscale);
   else if (NKT == 2) {
     // sequences of at most 32 tokens: both passes in ONE kernel (tattn_bwd_small_kernel); under the per-kernel profile it is timed as
     // pass Q and the pass-KV call is empty
     if (which != 3) {
       const dim3 g2(n_seq * heads < 4096 ? n_seq * heads : 4096);
-      hipLaunchKernelGGL((tattn_bwd_small_kernel<HD, PAD>), g2, dim3(128), 0, st, qkv, o, dout, dqkv, (const TAStat*)s, map, C, heads, n_seq * heads,
+      hipLaunchKernelGGL((tattn_bwd_small_kernel<HD, PAD, PASSES>), g2, dim3(128), 0, st, qkv, o, dout, dqkv, (const TAStat*)s, map, C, heads, n_seq * heads,
                          amax_qkv, amax_do, amax_out);
     }
   } else {                                             // which: 1 = both passes, 2 = pass Q alone, 3 = pass KV alone (needs pass Q's D_i)
     if (which != 3)
-      hipLaunchKernelGGL((tattn_bwd_q_kernel<NKT, NW, NKC, 4, HD, PAD>), grid, blk, lds, st, qkv, o, dout, dqkv, s, map, C, heads, groups, n_work,
+      hipLaunchKernelGGL((tattn_bwd_q_kernel<NKT, NW, NKC, 4, HD, PAD, PASSES>), grid, blk, lds, st, qkv, o, dout, dqkv, s, map, C, heads, groups, n_work,
                          amax_qkv, amax_do, amax_out);
     if (which != 2)
-      hipLaunchKernelGGL((tattn_bwd_kv_kernel<NKT, NW, NKC_KV, WPE_KV, HD, PAD>), grid, blk, lds_kv, st, qkv, dout, dqkv, (const TAStat*)s, map, C, heads, groups,
+      hipLaunchKernelGGL((tattn_bwd_kv_kernel<NKT, NW, NKC_KV, WPE_KV, HD, PAD, PASSES>), grid, blk, lds_kv, st, qkv, dout, dqkv, (const TAStat*)s, map, C, heads, groups,
                          n_work, amax_qkv, amax_do, amax_out);
   }
   return 0;
@@ -661,8 +677,11 @@ int ta_launch(int which, const float* qkv, const float* o, const float* dout, fl
 // The padded forms are compiled in a translation unit of their own (train_attn_pad.hip includes this file with D3DP_TA_PAD_TU
 // defined): beside them in one module the compiler allocated registers differently in 15 of the 57 existing instantiations; apart,
 // every one of those keeps its device code instruction for instruction (profiles/train_widths.md).
+// The one-pass forms (PASSES = 1, head dims 64 / 32 / 16) likewise: train_attn_1p.hip includes this file with D3DP_TA_1P_TU defined.
 #ifdef D3DP_TA_PAD_TU
 #define TA_CASE(NKT_, HD_) return ta_launch<NKT_, HD_, true>(which, qkv, o, dout, out, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st);
+#elif defined(D3DP_TA_1P_TU)
+#define TA_CASE(NKT_, HD_) return ta_launch<NKT_, HD_, false, 1>(which, qkv, o, dout, out, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st, po);
 #else
 #define TA_CASE(NKT_, HD_) return ta_launch<NKT_, HD_>(which, qkv, o, dout, out, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st, po);
 #endif
@@ -674,13 +693,20 @@ int ta_launch(int which, const float* qkv, const float* o, const float* dout, fl
   if (n <= 512) { TA_CASE(32, HD_) } \
   TA_CASE(64, HD_)
 
-#ifndef D3DP_TA_PAD_TU
+#if !defined(D3DP_TA_PAD_TU) && !defined(D3DP_TA_1P_TU)
 int ta_dispatch(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats, int n_seq,
                 SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
-                hipStream_t st, TAOperand po = {nullptr, 0, 0, nullptr}) {
+                hipStream_t st, int passes, TAOperand po = {nullptr, 0, 0, nullptr}) {
   const int n = map.n_tok;
+  if (passes != 1 && passes != 3) return -1;
   if (heads < 1 || C % heads != 0 || C % 4 != 0 || n < 1 || n > 1024 || !amax_qkv || !stats) return -2;
   if (po.op && (po.Tp < po.T || !po.unscale || C % 32 != 0)) return -1;
+  if (passes == 1) {                                   // (head dims 64 / 32 / 16 alone: -2 for the padded ones too, plan_context refuses them)
+    const int hd1 = C / heads;
+    if (hd1 != 64 && hd1 != 32 && hd1 != 16) return -2;
+    return d3dp_train_attn_x2_1p(which, qkv, o, dout, out, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st, po.op, po.T,
+                                 po.Tp, po.unscale);
+  }
   switch (C / heads) {                                 // the head dims these kernels take (ctx_plan.h mfma_head_dim, train_plan.h train_attn_head_dim)
     case 64: { TA_LENGTHS(64) }
     case 32: { TA_LENGTHS(32) }
@@ -715,6 +741,20 @@ int d3dp_train_attn_x2_padded(int which, const float* qkv, const float* o, const
   }
   return -2;
 }
+#elif defined(D3DP_TA_1P_TU)
+// which: 0 = forward, 1 = both backward passes, 2 = pass Q alone, 3 = pass KV alone; op / T / Tp / op_unscale: the forward's operand
+// rows, as d3dp_train_attn_x2_fwd (ta_dispatch has checked everything else)
+int d3dp_train_attn_x2_1p(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats,
+                          int n_seq, SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do,
+                          unsigned* amax_out, hipStream_t st, void* op, int T, int Tp, float* op_unscale) {
+  const int n = map.n_tok, hd = heads > 0 ? C / heads : 0;
+  if (heads < 1 || hd * heads != C || n < 1 || n > 1024 || !amax_qkv || !stats) return -2;
+  const TAOperand po{(f16*)op, T, Tp, op_unscale};
+  if (hd == 64) { TA_LENGTHS(64) }
+  if (hd == 32) { TA_LENGTHS(32) }
+  if (hd == 16) { TA_LENGTHS(16) }
+  return -2;
+}
 #else
 static_assert(sizeof(TAStat) == D3DP_TRAIN_ATTN_X2_STAT_BYTES, "train_plan.h: d3dp_train_attn_x2_stats_bytes");
 
@@ -725,20 +765,22 @@ static_assert(sizeof(TAStat) == D3DP_TRAIN_ATTN_X2_STAT_BYTES, "train_plan.h: d3
 // scale of q / k / v, op_unscale[0] = 1 / scale, amax_out[0] = the bound (the qkv absmax) -- see tattn_fwd_kernel
 int d3dp_train_attn_x2_fwd(const float* qkv, float* out, void* stats, int n_seq, SeqMap map, int C, int heads,
                            const unsigned* amax_qkv, unsigned* amax_out, hipStream_t st, void* op, int T, int Tp,
-                           float* op_unscale) {
+                           float* op_unscale, int passes) {
   if (!qkv || !out) return -1;
-  return ta_dispatch(0, qkv, nullptr, nullptr, out, nullptr, stats, n_seq, map, C, heads, amax_qkv, nullptr, amax_out, st,
+  return ta_dispatch(0, qkv, nullptr, nullptr, out, nullptr, stats, n_seq, map, C, heads, amax_qkv, nullptr, amax_out, st, passes,
                      TAOperand{(f16*)op, T, Tp, op_unscale});
 }
 // dqkv [T, 3C] = the gradient of (q | k | v) given dout [T, C]; o: the forward output; amax_do: absmax slot of dout;
 // amax_out (optional): absmax slot of dqkv (both passes add to it)
+// passes (both launchers): 3 = the split products above; 1 = every product as one fp16-MFMA pass on the hi planes
+// (train_attn_1p.hip; head dims 64 / 32 / 16 alone); any other value: -1
 // (part: 0 = both passes, 1 = pass Q alone (dq, D_i), 2 = pass KV alone (dk, dv; after pass Q): the library's per-kernel
 //  profile times them apart)
 int d3dp_train_attn_x2_bwd(const float* qkv, const float* o, const float* dout, float* dqkv, void* stats, int n_seq, SeqMap map,
                            int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
-                           hipStream_t st, int part) {
+                           hipStream_t st, int part, int passes) {
   if (!qkv || !o || !dout || !dqkv || !amax_do || part < 0 || part > 2) return -1;
-  return ta_dispatch(1 + part, qkv, o, dout, nullptr, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st);
+  return ta_dispatch(1 + part, qkv, o, dout, nullptr, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st, passes);
 }
 #endif
 #undef TA_LENGTHS

@@ -194,8 +194,11 @@ struct TrainLinear {
 
 struct TrainPlan {
   TrainPath path;
-  bool use_x2;                       // = path.use_x2; everything below but T, passes and overlap_sets is false / unused without it
+  bool use_x2;                       // = path.use_x2; everything below but T, passes, attn_passes and overlap_sets is false / unused without it
   int T, passes, overlap_sets;
+  // D3DP_TRAIN_ATTN_PASSES (CtxPlan::train_attn_passes): the fp16-MFMA passes per product of every attention that runs on
+  // train_attn.hip (path.attn_x2); 1 = its one-pass kernels (train_attn_1p.hip).  The fp32 attention of an axis does not read it.
+  int attn_passes;
   // D3DP_TRAIN_LONG_ATTN=chunked (CtxPlan::train_long_attn): an axis on the fp32 attention runs the chunked VALU backward of train.hip
   // wherever the whole-sequence VALU pair ran or refused, so the forward pass takes clips beyond 256 frames there too
   bool attn_bwd_chunked;
@@ -239,6 +242,7 @@ inline TrainPlan plan_train_step(const CtxPlan& c, const d3dp_cfg& g, int B, int
   P.path = plan_train_path(c, g);
   P.use_x2 = P.path.use_x2;
   P.T = T; P.passes = c.train_passes; P.overlap_sets = c.train_overlap_sets;
+  P.attn_passes = c.train_attn_passes;
   P.attn_bwd_chunked = c.train_long_attn;
   const int shape[4][2] = {{3 * C, C}, {C, C}, {Hd, C}, {C, Hd}};       // [N, K] by TrainLinearId
   for (int j = 0; j < 4; ++j) { P.lin[j].N = shape[j][0]; P.lin[j].K = shape[j][1]; }

@@ -535,7 +535,25 @@ class MixSTE2(nn.Module):
             text += ("; D3DP_TRAIN_LONG_ATTN=chunked: every fp32 attention backward that runs on the VALU kernels takes their chunked "
                      "form (K / V, then Q / dO / statistics pass through LDS in chunks of rows: any clip length up to 1024 frames and "
                      "any joint count up to 256, bit-equal to the whole-sequence kernels where both run)")
+        # D3DP_TRAIN_ATTN_PASSES=1 (ctx_plan.h plan_context, step 7a): named behind the unchanged text where a context takes it
+        if os.environ.get("D3DP_TRAIN_ATTN_PASSES") == "1" and self._train_attn_one_pass_axes():
+            text += ("; D3DP_TRAIN_ATTN_PASSES=1: every product of the " + self._train_attn_one_pass_axes() + " on split-fp16 operands "
+                     "-- S, O, dP, dQ, dK, dV -- as one fp16-MFMA pass from one-plane LDS images (q, k, v at the qkv scale, dO at its "
+                     "own, P x 2^10 and dS at its running power of two each rounded once to fp16; fp32 accumulate, softmax "
+                     "denominator, L and D in fp32)")
         return text
+
+    def _train_attn_one_pass_axes(self) -> str:
+        """Which attention D3DP_TRAIN_ATTN_PASSES=1 applies to in a context of this shape under the environment's other switches
+        ('' where plan_context refuses it: the fp32 path, head dims other than 64 / 32 / 16, D3DP_TRAIN_ATTN=f32)."""
+        hd = self.embed_dim // self.num_heads
+        inst = self.embed_dim in (64, 128, 256, 512) and self.hidden >= 64 and self.hidden % 64 == 0
+        widths = (not inst and os.environ.get("D3DP_TRAIN_IMPL") == "f16x2" and self.embed_dim in (192, 320, 384, 448)
+                  and self.hidden >= 64 and self.hidden % 64 == 0)
+        ta = os.environ.get("D3DP_TRAIN_ATTN", "")
+        if not (inst or widths) or os.environ.get("D3DP_TRAIN_IMPL") == "f32" or hd not in (64, 32, 16) or ta == "f32":
+            return ""
+        return "temporal attention" if ta == "x2t" else "attention of both axes"
 
     def _train_arithmetic_default(self) -> str:
         ta = os.environ.get("D3DP_TRAIN_ATTN", "")

@@ -239,6 +239,21 @@ D3DP_API const char* d3dp_last_error(void);
  *                         D3DP_TRAIN_WGRAD=each, D3DP_TRAIN_TAIL=split, D3DP_TRAIN_GELU=pass or D3DP_TRAIN_LN_OPERAND=pass (launch
  *                         forms of the variants build, which have no one-pass form).  D3DP_TRAIN_ATTN, D3DP_TRAIN_ATTN_BWD and
  *                         D3DP_TRAIN_OVERLAP compose with it.  Contexts of the other modes do not read it.
+ *   D3DP_TRAIN_ATTN_PASSES=1 in the environment of d3dp_create (OPT-IN; read for D3DP_MODE_TRAIN contexts alone; unset or =3: every
+ *                         context plans, refuses and launches as in the lines above, bit for bit): every attention of the step
+ *                         that runs on the split-fp16 kernels at head dim 64, 32 or 16 -- both axes, or the temporal axis alone
+ *                         under D3DP_TRAIN_ATTN=x2t -- runs each of its products (S = Q K^T and O = P V forward; S, dP = dO V^T,
+ *                         dQ = dS K, dK = dS^T Q, dV = P^T dO backward) as ONE fp16-MFMA pass: q, k, v rounded to IEEE fp16 at the
+ *                         power of two of the qkv absmax, dO at that of its own, P x 2^10 and dS at its running power of two per
+ *                         query / per key; fp32 accumulation, the softmax denominator, the log-sum-exp and dO . O in fp32.  Every
+ *                         scale is a device value: neither a range proof nor loss scaling is needed.  Same launches, streams and
+ *                         workspace; the LDS images halve.  A mixed-precision route -- gradients about 2^-13 from fp32's in the norm
+ *                         -- that costs nothing measurable beside D3DP_TRAIN_PASSES=1, whose Linears are ten times farther.
+ *                         D3DP_ENOTSUP, decided before the device is looked for and naming the switch: any other value; =1 for a
+ *                         context on the fp32 path (D3DP_TRAIN_IMPL=f32, a width outside the instantiated set), at head dim 8,
+ *                         beside D3DP_TRAIN_ATTN=f32, and at head dims 24 / 40 / 48 / 56 under D3DP_TRAIN_IMPL=f16x2 (the padded
+ *                         kernels have no one-pass form).  D3DP_TRAIN_PASSES, D3DP_TRAIN_OVERLAP, D3DP_TRAIN_LONG_ATTN and
+ *                         D3DP_TRAIN_ATTN_BWD compose with it.  Contexts of the other modes do not read it.
  *   D3DP_TRAIN_LONG_ATTN=chunked in the environment of d3dp_create (OPT-IN; read for D3DP_MODE_TRAIN contexts alone; unset: every
  *                         context plans, refuses and launches as in the lines above, bit for bit): every fp32 attention backward
  *                         of the step that runs on the VALU kernels -- head dim 8, a width on the fp32 path, the cross-check
@@ -395,6 +410,8 @@ D3DP_API int d3dp_jpma_ex(const float* pred, const float* traj, const float* cam
  * No gradient is accumulated with float atomics: the same inputs give the same bits.
  * Arithmetic of the Linears: three fp16-MFMA passes on split operands (fp32-class), or one pass on their hi planes under
  * D3DP_TRAIN_PASSES=1 (fp16 operands at their own scale, fp32 accumulation: d3dp_create) -- same launches, same workspace.
+ * Arithmetic of the split-fp16 attention: three fp16-MFMA passes per product, or one under D3DP_TRAIN_ATTN_PASSES=1 (q, k, v, dO, P
+ * and dS rounded once to fp16 at their device-side scales: d3dp_create) -- same launches, same workspace, same profile classes.
  * Clip length: any F <= 1024 like inference (reference common/arguments.py:58); beyond 256 frames the step needs its split-fp16
  * attention kernels (head dims 64, 32 and 16, and 24 / 40 / 48 / 56 under D3DP_TRAIN_IMPL=f16x2; keys / queries through LDS in
  * chunks) -- head dim 8, the fp32 path of the other widths and the fp32 cross-check implementations (D3DP_TRAIN_IMPL=f32,
