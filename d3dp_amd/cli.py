@@ -69,6 +69,10 @@ def parse_args(argv=None):
                    help='fp16-MFMA passes per product of the split-fp16 training attention: 1 = D3DP_TRAIN_ATTN_PASSES=1 (q, k, v, dO, P '
                         'and dS rounded once to fp16 at their scale, fp32 accumulation), 3 = the split-fp16 default; set around the '
                         'creation of the training model only')
+    p.add_argument('--train-rows', default=None, choices=['hi', 'split'],
+                   help='operand rows of the training Linears: hi = D3DP_TRAIN_ROWS=hi (plain fp16 rows read in whole lines; beside '
+                        '--train-passes 1 at -cs 256 / 512, bit-equal to it), split = the default; set around the creation of the '
+                        'training model only')
     p.add_argument('--train-long-attn', action='store_true',
                    help='D3DP_TRAIN_LONG_ATTN=chunked: the fp32 attention backward of the training step on its chunked kernels -- '
                         'trains at any -cs and -f (e.g. -cs 1024 -f 243, -cs 96 -f 351); set around the creation of the training model only')
@@ -226,6 +230,24 @@ def train_attn_passes_env(passes):
 
 
 @contextlib.contextmanager
+def train_rows_env(rows):
+    """D3DP_TRAIN_ROWS=<rows> inside the block (None: the environment as it is), restored on exit.  The library reads the switch
+    when a TRAIN context is created -- the training model's first step -- and for no context of another mode."""
+    if rows is None:
+        yield
+        return
+    saved = os.environ.get("D3DP_TRAIN_ROWS")
+    os.environ["D3DP_TRAIN_ROWS"] = str(rows)
+    try:
+        yield
+    finally:
+        if saved is None:
+            os.environ.pop("D3DP_TRAIN_ROWS", None)
+        else:
+            os.environ["D3DP_TRAIN_ROWS"] = saved
+
+
+@contextlib.contextmanager
 def train_long_attn_env(on):
     """D3DP_TRAIN_LONG_ATTN=chunked inside the block (false: the environment as it is), restored on exit.  The library reads the switch
     when a TRAIN context is created -- the training model's first step -- and for no context of another mode."""
@@ -257,10 +279,10 @@ def run_train(args, rank, world, device):
     model_eval = D3DP(args, kl, kr, is_train=False, numerics=args.numerics).to(device)
     if not args.resume:
         model_train.load_state_dict(make_state_dict(7, args.cs, args.dep, args.number_of_frames), strict=False)
-    # --train-passes / --train-attn-passes / --train-long-attn: the TRAIN context is created HERE, inside the switch's block, instead of at the first step (the eval model's
+    # --train-passes / --train-attn-passes / --train-rows / --train-long-attn: the TRAIN context is created HERE, inside the switch's block, instead of at the first step (the eval model's
     # contexts, created later in the same process, never see the variable)
     with train_passes_env(args.train_passes), train_attn_passes_env(getattr(args, 'train_attn_passes', None)), \
-            train_long_attn_env(getattr(args, 'train_long_attn', False)):
+            train_rows_env(getattr(args, 'train_rows', None)), train_long_attn_env(getattr(args, 'train_long_attn', False)):
         model_train.pose_estimator._context(device)
         print('INFO: training arithmetic:', model_train.pose_estimator.train_arithmetic())
     n_params = sum(p.numel() for p in model_train.parameters())

@@ -7,13 +7,19 @@ extern "C" {
 // test hook (include/d3dp_hip.h, "test hooks"): the training step's split-fp16 Linear alone, out[M, N] = A[M, K] W[N, K]^T + bias on fp32
 // device operands -- absmax, operand passes and gemm_f16x2_dyn_kernel as the step launches them.  tail: 0 = the rows behind the
 // last whole 256-row tile as one more row of tiles, 1 = as 16 x 64 blocks at the end of the kernel; | 16 = the one-pass
-// instantiation (hi x hi alone: what D3DP_TRAIN_PASSES=1 launches); any other bit is refused.  amax_out: optional
-// pre-zeroed device slot (amax_pos: see kernels.h).  Allocates its operand buffers and synchronises the stream.
+// instantiation (hi x hi alone: what D3DP_TRAIN_PASSES=1 launches); | 16 | 32 = that product on hi-only operand rows (what
+// D3DP_TRAIN_ROWS=hi launches: split2h_dyn_kernel's and gemm_f16x2_dyn_kernel's HI forms; K % 64 == 0); 32 without 16 and any other
+// bit are refused.  amax_out: optional pre-zeroed device slot (amax_pos: see kernels.h).  Allocates its operand buffers and synchronises the stream.
 int d3dp_debug_train_linear(const float* A, const float* W, const float* bias, float* out, int32_t M, int32_t N, int32_t K,
                             int32_t tail, unsigned* amax_out, int32_t amax_pos, void* stream) {
   if (!A || !W || !out || M < 1 || N < 4 || N % 4 || K < 32 || K % 32) return d3dp_fail(D3DP_EINVAL, "d3dp_debug_train_linear: bad argument");
-  if (tail & ~17) return d3dp_fail(D3DP_EINVAL, "d3dp_debug_train_linear: tail = %d (bit 0: remainder rows as 16 x 64 blocks, bit 4: one pass)", tail);
-  const int passes = (tail & 16) ? 1 : 3;
+  if ((tail & ~49) || (tail & 48) == 32)
+    return d3dp_fail(D3DP_EINVAL, "d3dp_debug_train_linear: tail = %d (bit 0: remainder rows as 16 x 64 blocks, bit 4: one pass, bit 5 beside "
+                             "bit 4: hi-only operand rows)", tail);
+  const int passes = (tail & 16) ? 1 : 3, rows_hi = (tail & 32) ? 1 : 0;
+  if (rows_hi && K % 64)
+    return d3dp_fail(D3DP_EINVAL, "d3dp_debug_train_linear: K = %d under tail | 32: hi-only operand rows are read in whole 128-byte lines of "
+                             "64 columns (K %% 64 == 0)", K);
   tail &= 1;
   hipStream_t st = (hipStream_t)stream;
   char* buf = nullptr;
@@ -25,9 +31,9 @@ int d3dp_debug_train_linear(const float* A, const float* W, const float* bias, f
   if (!rc) {
     d3dp_launch_absmax(A, (size_t)M * K, amax, st);
     d3dp_launch_absmax(W, (size_t)N * K, amax + 1, st);
-    d3dp_launch_split2_dyn(A, buf, M, K, K, amax, uns, st);
-    d3dp_launch_split2_dyn(W, buf + a_bytes, N, K, K, amax + 1, uns + 1, st);
-    rc = d3dp_launch_linear_f16x2_dyn(buf, buf + a_bytes, bias, uns, uns + 1, out, M, N, K, 1, st, amax_out, amax_pos, tail, passes);
+    d3dp_launch_split2_dyn(A, buf, M, K, K, amax, uns, st, rows_hi);
+    d3dp_launch_split2_dyn(W, buf + a_bytes, N, K, K, amax + 1, uns + 1, st, rows_hi);
+    rc = d3dp_launch_linear_f16x2_dyn(buf, buf + a_bytes, bias, uns, uns + 1, out, M, N, K, 1, st, amax_out, amax_pos, tail, passes, rows_hi);
   }
   const hipError_t e = hipStreamSynchronize(st);
   (void)hipFree(buf);

@@ -72,6 +72,8 @@ const float* lin_b(const BlockDev& w, int j) { return j == kQkv ? w.qkv_b : j ==
 // partial products summed in a fixed order (deterministic; the fp32 path's split-K used atomics).
 // D3DP_TRAIN_PASSES=1 (TrainPlan::passes): the same launches on the one-pass instantiations of the two product kernels -- hi(A) x hi(W)
 // alone, i.e. every operand rounded to fp16 at its own scale; operand passes, scales, k order, partial sums, streams: unchanged.
+// D3DP_TRAIN_ROWS=hi (TrainPlan::rows_hi, beside passes = 1 alone): the same launches again with every operand -- activations, both weight
+// forms, every dY -- as hi-only rows [.][K] at the START of its unchanged region, and the whole-line forms of the two product kernels.
 // What a pass DECIDES is in the plan P (train_plan.h); this holds what a pass is in the middle of: the current operand set, the
 // deferred TN products, the slot counter, the streams.
 struct X2Train {
@@ -102,7 +104,7 @@ struct X2Train {
     if (!n_def) return 0;
     hipStream_t sw = st_w ? st_w : st;
     Scope ps(pc, T_WGRAD, sw);
-    int r = d3dp_launch_linear_f16x2_tn_many(def, n_def, P.mTp, P.mZ, sw, P.passes);
+    int r = d3dp_launch_linear_f16x2_tn_many(def, n_def, P.mTp, P.mZ, sw, P.passes, P.rows_hi);
     if (r) return r;
     D3dpSumTable tb{};
     tb.n = n_def; tb.Z = P.mZ;
@@ -158,7 +160,7 @@ struct X2Train {
       const BlockDev& w = (blk & 1) ? c->tte[blk >> 1] : c->ste[blk >> 1];
       tb.it[l] = D3dpWPrepItem{lin_w(w, j), P.lin[j].N, P.lin[j].K, 2 * l + 1, 0, woff(l)};
     }
-    return d3dp_launch_wprep(tb, ws + L.w_rows, ws + L.w_cols, amax(), uns(), st);
+    return d3dp_launch_wprep(tb, ws + L.w_rows, ws + L.w_cols, amax(), uns(), st, P.rows_hi);
   }
   // out[T, N] = A2 . W2^T (+ bias) with T = 256 q + rem rows.  The persistent kernel works in rounds of n_cu tiles of 256 x 128;
   // the configs[4] batch has T = 16,524 = 64 x 256 + 140, so every forward / dgrad product had ONE row of tiles too many for
@@ -173,7 +175,8 @@ struct X2Train {
     const int T = P.T, passes = P.passes;
     if (tail.form != TrainTailForm::SPLIT_REM)
       return d3dp_launch_linear_f16x2_dyn(A2, W2, bias, ua, uw, out, T, N, K, 1, st, out_amax, amax_pos,
-                                          tail.form == TrainTailForm::REM_BLOCKS ? 1 : 0, passes);
+                                          tail.form == TrainTailForm::REM_BLOCKS ? 1 : 0, passes, P.rows_hi);
+    if (P.rows_hi) return -1;                            // (a superseded form: plan_context refuses it beside D3DP_TRAIN_ROWS=hi)
     const int q = T / 256, rem = T - q * 256;
     int r = d3dp_launch_linear_f16x2_dyn(A2, W2, bias, ua, uw, out, q * 256, N, K, 1, st, out_amax, amax_pos, 0, passes);
     if (r) return r;
@@ -200,6 +203,7 @@ struct X2Train {
     unsigned* out_amax = j == kQkv ? qkv_amax(blk) : pmax ? amax() + kPmaxSlot0 + blk : nullptr;
     const TrainOperand src = P.source(blk, j);
     const float* a2 = x_op(l);
+    if (P.rows_hi && (src == TrainOperand::ROWS_T || !P.batched)) return -1;   // (no hi-only form: plan_context lets no such shape through)
     if (src != TrainOperand::PRODUCER) {
       Scope ps(pc, T_OPERAND, st);
       if (j == kProj && (blk & 1) && P.attn_t_f32_mfma) d3dp_launch_absmax(A, (size_t)T * K, amax() + sa, st);
@@ -209,9 +213,9 @@ struct X2Train {
       const int Tp = p.pad_rows;
       int r;
       if (src == TrainOperand::LN_INPUT)
-        r = d3dp_launch_rowprep_ln(A, j == kQkv ? w.n1w : w.n2w, j == kQkv ? w.n1b : w.n2b, ln_eps, x_op(l), T, Tp, K, amax() + sa, uns() + sa, st);
+        r = d3dp_launch_rowprep_ln(A, j == kQkv ? w.n1w : w.n2w, j == kQkv ? w.n1b : w.n2b, ln_eps, x_op(l), T, Tp, K, amax() + sa, uns() + sa, st, P.rows_hi);
       else if (src == TrainOperand::ROWS)
-        r = d3dp_launch_rowprep(A, x_op(l), nullptr, nullptr, T, Tp, K, amax() + sa, uns() + sa, st);
+        r = d3dp_launch_rowprep(A, x_op(l), nullptr, nullptr, T, Tp, K, amax() + sa, uns() + sa, st, nullptr, 0, 1, 1, nullptr, P.rows_hi);
       else {
         a2 = ws + o_a;
         r = d3dp_launch_dyprep(A, ws + o_a, x_op(l), nullptr, T, K, Tp, amax() + sa, uns() + sa, st);
@@ -231,7 +235,7 @@ struct X2Train {
   int gelu_operand(int blk, const float* hpre) {
     const int l = 4 * blk + kFc2;
     Scope ps(pc, T_OPERAND, st);
-    return d3dp_launch_gelu_rowprep(hpre, x_op(l), P.T, P.lin[kFc2].pad_rows, P.lin[kFc2].K, amax() + kPmaxSlot0 + blk, amax() + 2 * l, uns() + 2 * l, st);
+    return d3dp_launch_gelu_rowprep(hpre, x_op(l), P.T, P.lin[kFc2].pad_rows, P.lin[kFc2].K, amax() + kPmaxSlot0 + blk, amax() + 2 * l, uns() + 2 * l, st, P.rows_hi);
   }
   // dX[T, K] = dY[T, N] W[N, K] of Linear l = 4 blk + j   (sdy: the absmax slot of dY, shared with wgrad; always right behind the
   // wgrad of the same dY, whose prep_dy left the row form of dY in the current set)
@@ -263,7 +267,8 @@ struct X2Train {
     Scope ps(pc, T_OPERAND, st);
     if (p.tn)                        // the row form alone (zero rows behind T): dgrad's operand AND the TN wgrad's
       return d3dp_launch_rowprep(dY, ws + o_a, bias_part, bias_rows, P.T, p.pad_rows, p.N, amax() + sdy, uns() + sdy, st, mask, axis, F, J,
-                                 gelu_pre);
+                                 gelu_pre, P.rows_hi);
+    if (P.rows_hi) return -1;
     *bias_rows = D3DP_DYPREP_ROWS;
     return d3dp_launch_dyprep(dY, ws + o_a, ws + o_at, bias_part, P.T, p.N, p.pad_rows, amax() + sdy, uns() + sdy, st);
   }
@@ -284,7 +289,7 @@ struct X2Train {
     hipStream_t sw = st_w ? st_w : st;
     Scope ps(pc, T_WGRAD, sw);
     if (p.tn)                                          // both operands in their row forms [Tp][2 .]: nothing was transposed
-      r = d3dp_launch_linear_f16x2_tn(ws + o_a, x_op(l), uns() + sdy, uns() + sx, ws + o_part, N, K, p.Tp, p.Z, sw, P.passes);
+      r = d3dp_launch_linear_f16x2_tn(ws + o_a, x_op(l), uns() + sdy, uns() + sx, ws + o_part, N, K, p.Tp, p.Z, sw, P.passes, P.rows_hi);
     else                                               // (the transposed form: left by prep_dy)
       r = d3dp_launch_linear_f16x2_dyn(ws + o_at, x_op(l), nullptr, uns() + sdy, uns() + sx, ws + o_part, N, K, p.Tp, p.Z, sw, nullptr, 0, 0, P.passes);
     if (r) return r;
@@ -369,7 +374,7 @@ int d3dp_train_forward(d3dp_ctx* c, const float* x2d, const float* x3d, const in
     auto attention = [&]() -> int {                      // (the launcher's own return code)
       if (ax2)
         return d3dp_train_attn_x2_fwd(S + L.o_qkv, S + L.o_att, ws + L.stats_x2 + (size_t)blk * L.stats_x2_stride, n_seq, map, C,
-                                      g.heads, x2->qkv_amax(blk), slot(4 * blk + 1), st, att_op, T, att_tp, att_un, P.attn_passes);
+                                      g.heads, x2->qkv_amax(blk), slot(4 * blk + 1), st, att_op, T, att_tp, att_un, P.attn_passes, P.rows_hi);
       if (kind == 1 && P.attn_t_f32_mfma)                // temporal axis on the fp32 matrix cores (bitwise an fp32 fmaf chain per product)
         return d3dp_launch_attn_temporal_f32(0, S + L.o_qkv, S + L.o_att, n_seq, map, C, g.heads, st);
       return d3dp_launch_attn_rows(0, S + L.o_qkv, S + L.o_att, n_seq, map, C, g.heads, st, slot(4 * blk + 1));
@@ -379,7 +384,7 @@ int d3dp_train_forward(d3dp_ctx* c, const float* x2d, const float* x3d, const in
     if (ln_direct)
       TP(T_LN_FWD, d3dp_train_add_mask_ln(S + L.o_xin, y, mask_ptr(masks, g, B, blk, 0), kind, F, J, w.n2w, w.n2b, g.eps_block,
                                           S + L.o_xmid, nullptr, slot(4 * blk + 2), T, C, st, x2->x_op(4 * blk + 2),
-                                          P.lin[kFc1].pad_rows, x2->uns() + 2 * (4 * blk + 2)))
+                                          P.lin[kFc1].pad_rows, x2->uns() + 2 * (4 * blk + 2), P.rows_hi))
     else
       TP(T_LN_FWD, d3dp_train_add_mask_ln(S + L.o_xin, y, mask_ptr(masks, g, B, blk, 0), kind, F, J, w.n2w, w.n2b, g.eps_block,
                                           S + L.o_xmid, ln_fused ? nullptr : xn, slot(4 * blk + 2), T, C, st));
@@ -406,7 +411,7 @@ int d3dp_train_forward(d3dp_ctx* c, const float* x2d, const float* x3d, const in
                                          last ? ws + L.z : (ln_fused ? nullptr : xn), last ? nullptr : slot(4 * (blk + 1)), T, C, st,
                                          (ln_direct && !last) ? x2->x_op(4 * (blk + 1)) : nullptr,
                                          (ln_direct && !last) ? P.lin[kQkv].pad_rows : 0,
-                                         (ln_direct && !last) ? x2->uns() + 2 * 4 * (blk + 1) : nullptr));
+                                         (ln_direct && !last) ? x2->uns() + 2 * 4 * (blk + 1) : nullptr, P.rows_hi));
   }
   TP(T_OTHER, d3dp_train_head_linear(ws + L.z, c->hw, c->hb, out, T, C, st));
   HIP_TRY(hipGetLastError());

@@ -18,7 +18,7 @@ struct CtxEnv {
              *train_overlap = nullptr, *train_gelu = nullptr, *train_wgrad = nullptr, *train_ln_operand = nullptr, *train_tail = nullptr,
              *train_attn = nullptr, *train_passes = nullptr, *fast_impl = nullptr, *fast16_range = nullptr, *x2_skew = nullptr,
              *x2_pp = nullptr, *x2_wide = nullptr, *seq_pad = nullptr, *fold_ln = nullptr, *train_long_attn = nullptr,
-             *train_attn_passes = nullptr;
+             *train_attn_passes = nullptr, *train_rows = nullptr;
   static CtxEnv from_process() {
     CtxEnv e;
     e.exact_impl = getenv("D3DP_EXACT_IMPL");                 // bf16x3 | f32: cross-check implementations of EXACT mode; f16x2: opt-in at 192 ... 448
@@ -42,6 +42,7 @@ struct CtxEnv {
     e.fold_ln = getenv("D3DP_FOLD_LN");                       // 1: experiment, norm2 folded into proj / fc1
     e.train_long_attn = getenv("D3DP_TRAIN_LONG_ATTN");       // chunked: opt-in, the fp32 training attention backward at any sequence length
     e.train_attn_passes = getenv("D3DP_TRAIN_ATTN_PASSES");   // 1: opt-in, one fp16-MFMA pass per product of the split-fp16 training attention
+    e.train_rows = getenv("D3DP_TRAIN_ROWS");                 // hi: opt-in, the one-pass training Linears' operands as plain fp16 rows
     return e;
   }
 };
@@ -70,6 +71,10 @@ struct CtxPlan {
                                  // kernels of train_attn.hip -- both axes, or the temporal one under D3DP_TRAIN_ATTN=x2t -- runs each of
                                  // its products (S, O; S, dP, dQ, dK, dV) as ONE fp16-MFMA pass on operands rounded once to fp16 at
                                  // their device-side scale, from one-plane LDS images (train_attn_1p.hip)
+  bool train_rows_hi = false;    // D3DP_TRAIN_ROWS=hi (TRAIN contexts under D3DP_TRAIN_PASSES=1 alone): every operand of X2Train's Linears --
+                                 // activations, both forms of the weights, every dY -- is stored as plain fp16 rows ("h1": column c at
+                                 // offset c, half the row stride, the regions of the workspace half used) and the one-pass products
+                                 // read whole 128-byte lines of 64 k.  Same hi values, same MFMAs in the same order: bit-equal
   int exact_impl_req = 0;        // what D3DP_EXACT_IMPL asked for (0 = f16x2, 1 = bf16x3, 2 = f32): d3dp_ctx::exact_impl starts from it
   bool long_rows = false;        // D3DP_LONG_ATTN=rows: the row-kernel cross-check
   bool fold = true;              // proj / fc2 add into the residual stream in their epilogue (d3dp_ctx::fold_resid)
@@ -146,6 +151,11 @@ inline bool fast_optin_shape(const d3dp_cfg& g) {
   const int hd = g.channels / g.heads;
   return optin_width(g.channels) && (hd == 24 || hd == 32 || hd == 40 || hd == 48 || hd == 56 || hd == 64) && g.hidden == 2 * g.channels;
 }
+// The tile of the training step's product kernels (gemm_x2_tile.h XBM x XBN) and the weights d3dp_launch_wprep prepares in one call
+constexpr int D3DP_TN_TILE_N = 256, D3DP_TN_TILE_K = 128;
+constexpr int D3DP_WPREP_MAX = 64;
+// the weight gradient dW[N, K] straight from the row forms of its two operands (gemm_f16x2_tn_kernel): whole tiles only
+inline bool d3dp_tn_applies(int N, int K) { return N % D3DP_TN_TILE_N == 0 && K % D3DP_TN_TILE_K == 0; }
 // The training Linears run on split-fp16 operands (X2Train, capi_train.hip); else on the fp32 matrix cores: TrainPath::use_x2 (train_plan.h)
 inline bool train_linears_split(const CtxPlan& p, const d3dp_cfg& g) { return p.train_x2 && g.channels % 32 == 0 && g.hidden % 32 == 0; }
 
@@ -322,6 +332,44 @@ inline int plan_context(const d3dp_cfg& g, const CtxEnv& e, bool variants_built,
         return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ATTN_PASSES=1 beside D3DP_TRAIN_ATTN=f32: both axes then run the fp32 attention kernels, which "
                                   "have no one-pass form");
       p.train_attn_passes = 1;
+    }
+  }
+  // 7b. D3DP_TRAIN_ROWS (TRAIN contexts alone; behind step 7a so that every earlier refusal keeps its place): =hi stores every operand
+  // of the one-pass training Linears as plain fp16 rows and runs their products on the whole-line kernels (gemm_x2_train.hip, HI);
+  // =split names the default.  The route exists where no operand of the step is transposed and every producer writes rows itself:
+  // D3DP_TRAIN_PASSES=1 at an instantiated width, every Linear of a block a TN shape (the merged weight gradient reads row forms),
+  // channels a multiple of 256 (the LayerNorm kernels write the qkv / fc1 operands), depth within the batched weight preparation --
+  // `-cs` 256 and 512 with hidden = 2 x channels, depth <= 8.  Everything else is refused by name.  The attention and stream
+  // switches compose with it: they select no Linear operand.
+  if (train && e.train_rows) {
+    if (strcmp(e.train_rows, "hi") && strcmp(e.train_rows, "split"))
+      return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ROWS=%.32s: the values a TRAIN context takes are D3DP_TRAIN_ROWS=hi (the one-pass training "
+                                "Linears' operands as plain fp16 rows) and split (the default)", e.train_rows);
+    if (e.train_rows[0] == 'h') {
+      if (!train_linears_split(p, g))
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ROWS=hi exists for the split-fp16 training Linears; channels=%d%s trains on the fp32 path "
+                                  "(fp32-MFMA Linears read no operand rows)", g.channels, train_f32 ? " under D3DP_TRAIN_IMPL=f32" : "");
+      if (!inst)
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ROWS=hi at channels=%d under D3DP_TRAIN_IMPL=f16x2: the padded widths run an operand pass in "
+                                  "front of every Linear and transposed weight-gradient operands, which have no hi-only form", g.channels);
+      if (superseded)
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ROWS=hi beside D3DP_TRAIN_WGRAD=each / D3DP_TRAIN_TAIL=split / D3DP_TRAIN_GELU=pass / "
+                                  "D3DP_TRAIN_LN_OPERAND=pass: the superseded launch forms have no hi-only form");
+      if (p.train_passes != 1)
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ROWS=hi without D3DP_TRAIN_PASSES=1: the three-pass products read the lo halves that hi-only "
+                                  "rows do not store");
+      const int C = g.channels, Hd = g.hidden;
+      if (C % 256 != 0 || !d3dp_tn_applies(3 * C, C) || !d3dp_tn_applies(C, C) || !d3dp_tn_applies(Hd, C) || !d3dp_tn_applies(C, Hd))
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ROWS=hi at channels=%d hidden=%d: the hi-only route exists where no operand of the step is "
+                                  "transposed and the LayerNorm kernels write the qkv / fc1 operand rows -- channels a multiple of 256 "
+                                  "and hidden a multiple of 256 (`-cs` 256 and 512); narrower widths use transposed operands", C, Hd);
+      if (hd == 16 && p.train_attn_x2 != 0)
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ROWS=hi at head dim 16 (channels=%d heads=%d): the split-fp16 training attention writes "
+                                  "hi-only proj operand rows at head dims 64 and 32", g.channels, g.heads);
+      if (8 * g.depth > D3DP_WPREP_MAX)
+        return d3dp_fail(D3DP_ENOTSUP, "D3DP_TRAIN_ROWS=hi at depth=%d: the hi-only weight operands are written by the batched weight preparation "
+                                  "(depth <= %d); the per-weight preparation of deeper models has no hi-only form", g.depth, D3DP_WPREP_MAX / 8);
+      p.train_rows_hi = true;
     }
   }
   // 8. The EXACT cross-check implementations: bf16x3 exists at the instantiated widths; a width neither instantiated nor padded

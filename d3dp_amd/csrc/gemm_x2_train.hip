@@ -32,7 +32,12 @@ namespace {
 //     second 64 bytes of a line in the remainder blocks).  The hi plane of an operand IS that tensor rounded to fp16 at its own
 //     power-of-two scale, so the product is fp16 operands, fp32 accumulation, same k order, same scales and epilogue.  The loaders
 //     are the same: whole 128-byte h2i lines, of which this form uses the first 64 bytes.
-template <int PASSES>
+//   * HI (template parameter; PASSES = 1 alone): the operands are hi-only rows of D3DP_TRAIN_ROWS=hi ("h1": Kfull plain fp16 per row,
+//     a 128-byte line = 64 consecutive k).  Same pieces, swizzle and ring; a STAGE carries 256 x 128 x 64 -- two k-steps -- and the
+//     compute waves issue per (mi, ni) the MFMA of the fragments at offA / offW (k 0..31 of the stage) and then the one at offA ^ 64 /
+//     offW ^ 64 (k 32..63): the lanes' k values, their fragment positions and the order of the k-steps per accumulator are those of
+//     the PASSES = 1 form on h2i rows, with half the barriers, waits and staged bytes per product.  NKz stays in k-steps of 32 (even).
+template <int PASSES, bool HI = false>
 __global__ __launch_bounds__(768) void gemm_f16x2_dyn_kernel(const f16* __restrict__ A2, const f16* __restrict__ W2,
                                                              const float* __restrict__ bias, const float* __restrict__ dynA,
                                                              const float* __restrict__ dynW, float* __restrict__ out, int M,
@@ -40,11 +45,14 @@ __global__ __launch_bounds__(768) void gemm_f16x2_dyn_kernel(const f16* __restri
                                                              int total_items, unsigned* __restrict__ amax_out, int amax_pos,
                                                              int rem_m0) {
   static_assert(PASSES == 1 || PASSES == 3, "one pass (hi x hi) or the three-pass split scheme");
+  static_assert(!HI || PASSES == 1, "hi-only rows hold no lo halves");
+  constexpr int RS = HI ? 1 : 2;                       // fp16 elements of an operand row per column of the contraction
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int G = gridDim.x;
   const int L = xcd_remap(blockIdx.x, G);
   const int n_my = (total_items - L + G - 1) / G;      // work items L, L+G, ...: item = z tiles_per_z + tile
-  const int gtot = n_my * NKz;
+  const int NS = HI ? NKz >> 1 : NKz;                  // stages (128-byte lines of a row) per work item
+  const int gtot = n_my * NS;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (gtot <= 0) return;
@@ -63,17 +71,17 @@ __global__ __launch_bounds__(768) void gemm_f16x2_dyn_kernel(const f16* __restri
         const int item = L + ti * G;
         const int z = item / tiles_per_z, t = item - z * tiles_per_z;
         const int m0 = (t / tiles_n) * XBM, n0 = (t % tiles_n) * XBN;
-        const size_t k0 = (size_t)z * NKz * (2 * XBK);   // first k-step of the chunk, in fp16 elements of an h2i row
+        const size_t k0 = (size_t)z * NS * (2 * XBK);    // first k-step of the chunk, in fp16 elements of an h2i (HI: h1) row
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           const int row = (lw * 8 + i) * 8 + lr;
-          pa[i] = A2 + (size_t)min(m0 + row, M - 1) * (2 * Kfull) + k0 + swz128(row, lq) * 8;
+          pa[i] = A2 + (size_t)min(m0 + row, M - 1) * (RS * Kfull) + k0 + swz128(row, lq) * 8;
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int row = (lw * 4 + i) * 8 + lr;
           const int wrow = (row & 64) + colperm(row & 63);
-          pw[i] = W2 + (size_t)min(n0 + wrow, N - 1) * (2 * Kfull) + k0 + swz128(row, lq) * 8;
+          pw[i] = W2 + (size_t)min(n0 + wrow, N - 1) * (RS * Kfull) + k0 + swz128(row, lq) * 8;
         }
       }
       char* base = smem + slot * XSTAGE;
@@ -83,7 +91,7 @@ __global__ __launch_bounds__(768) void gemm_f16x2_dyn_kernel(const f16* __restri
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         __builtin_amdgcn_global_load_lds(GPTR(pw[i] + ko), LPTR(base + XA_BYTES + (lw * 4 + i) * 1024), 16, 0, 0);
-      if (++ks == NKz) { ks = 0; ++ti; }
+      if (++ks == NS) { ks = 0; ++ti; }
       slot = (slot == XNSTAGE - 1) ? 0 : slot + 1;
     };
     issue();
@@ -126,11 +134,11 @@ __global__ __launch_bounds__(768) void gemm_f16x2_dyn_kernel(const f16* __restri
 #pragma unroll 1
     for (int b = L; b < rem_blocks; b += G) {
       const int m0 = rem_m0 + (b / rem_cg) * 16, nb0 = (b % rem_cg) * 64;
-      const size_t kofs = (size_t)wave * ksw * (2 * XBK) + fg * 8;
-      const f16* ap = A2 + (size_t)min(m0 + fi, M - 1) * (2 * Kfull) + kofs;
+      const size_t kofs = (size_t)wave * ksw * (RS * XBK) + fg * 8;   // (HI: the same k-steps, 32 elements each)
+      const f16* ap = A2 + (size_t)min(m0 + fi, M - 1) * (RS * Kfull) + kofs;
       const f16* wp[4];
 #pragma unroll
-      for (int ni = 0; ni < 4; ++ni) wp[ni] = W2 + (size_t)min(nb0 + 4 * fi + ni, N - 1) * (2 * Kfull) + kofs;
+      for (int ni = 0; ni < 4; ++ni) wp[ni] = W2 + (size_t)min(nb0 + 4 * fi + ni, N - 1) * (RS * Kfull) + kofs;
       f32x4 pacc[4];
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) pacc[ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -139,7 +147,7 @@ __global__ __launch_bounds__(768) void gemm_f16x2_dyn_kernel(const f16* __restri
         f16x8 ah[2], al[2], wh[2][4], wl[2][4];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-          const int o = (ks + u) * (2 * XBK);
+          const int o = (ks + u) * (RS * XBK);
           ah[u] = *reinterpret_cast<const f16x8*>(ap + o);
           if constexpr (PASSES == 3) al[u] = *reinterpret_cast<const f16x8*>(ap + o + XBK);
 #pragma unroll
@@ -200,7 +208,7 @@ __global__ __launch_bounds__(768) void gemm_f16x2_dyn_kernel(const f16* __restri
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
-    for (int ks = 0; ks < NKz; ++ks) {
+    for (int ks = 0; ks < NS; ++ks) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       X2_BARRIER();
       const char* sb = smem + slot * XSTAGE;
@@ -209,11 +217,19 @@ __global__ __launch_bounds__(768) void gemm_f16x2_dyn_kernel(const f16* __restri
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-        for (int pl = 0; pl < (PASSES == 3 ? 2 : 1); ++pl)
+        for (int pl = 0; pl < (PASSES == 3 || HI ? 2 : 1); ++pl)   // (HI: pl = the second k-step of the stage)
           wf[ni][pl] = *reinterpret_cast<const f16x8*>(sb + (pl ? offWl : offW) + ni * 2048);
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
         const f16x8 ah = *reinterpret_cast<const f16x8*>(sb + offA + mi * 2048);
+        if constexpr (HI) {
+          const f16x8 a2 = *reinterpret_cast<const f16x8*>(sb + offAl + mi * 2048);
+#pragma unroll
+          for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wf[ni][0], acc[mi][ni], 0, 0, 0);   // k 0..31
+#pragma unroll
+          for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, wf[ni][1], acc[mi][ni], 0, 0, 0);   // k 32..63
+          continue;
+        }
         if constexpr (PASSES == 3) {
           const f16x8 al = *reinterpret_cast<const f16x8*>(sb + offAl + mi * 2048);
 #pragma unroll
@@ -295,9 +311,19 @@ __device__ __forceinline__ int tn_find(const D3dpTnTable& tb, int t) {
   return i;
 }
 // PASSES: as gemm_f16x2_dyn_kernel -- 1 = hi x hi alone, the lo planes of the slabs (pl = 1) are never read from LDS.
-template <int PASSES>
+// HI (PASSES = 1 alone; D3DP_TRAIN_ROWS=hi): both operands are hi-only rows [Tp][N] / [Tp][K].  The k-step stays 32 token rows, so Tp,
+// the split count, the product table, the partial tiles and their ordered sum keep their grouping; the slab rows halve -- A 512 B
+// (256 features), W 256 B (128 features): 24 KiB per stage in the same 3-stage ring (72 KiB), as 16 A pieces of two rows and 8 W
+// pieces of four rows, 1 KiB each: SIX LDS-DMA instructions per loader wave and k-step instead of twelve.  16-byte slot s (8
+// features) of token row r sits at s ^ ((r & 7) << 1) as before: the rows are still whole multiples of 256 B apart, so the eight rows
+// a transposed read touches per cycle land in eight different 32-byte bank groups; the lanes of a fragment read point at the same
+// tokens and features as in the split form, so every MFMA sees the same values in the same positions.
+constexpr int XTN_HI_A = 32 * 512, XTN_HI_STAGE = XTN_HI_A + 32 * 256;   // 16 KiB + 8 KiB per k-step
+template <int PASSES, bool HI = false>
 __global__ __launch_bounds__(768) void gemm_f16x2_tn_kernel(D3dpTnTable tb, int NKz, int tiles_per_z, int total_items) {
   static_assert(PASSES == 1 || PASSES == 3, "one pass (hi x hi) or the three-pass split scheme");
+  static_assert(!HI || PASSES == 1, "hi-only rows hold no lo halves");
+  constexpr int STAGE = HI ? XTN_HI_STAGE : XSTAGE, A_BYTES = HI ? XTN_HI_A : XA_BYTES, A_ROW = HI ? 512 : 1024, W_ROW = HI ? 256 : 512;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int G = gridDim.x;
   const int L = xcd_remap(blockIdx.x, G);
@@ -322,14 +348,29 @@ __global__ __launch_bounds__(768) void gemm_f16x2_tn_kernel(D3dpTnTable tb, int 
         const int t = tt - P.tile0;
         const int n0 = (t / P.tiles_k) * XBM, k0 = (t % P.tiles_k) * XBN;
         const size_t t0 = (size_t)z * NKz * XBK;       // first token row of the chunk
-        a_row = (size_t)2 * P.N; w_row = (size_t)2 * P.K;
+        a_row = (size_t)(HI ? 1 : 2) * P.N; w_row = (size_t)(HI ? 1 : 2) * P.K;
         // A piece i = token row lw 8 + i of the k-step (1 KiB: features n0 .. n0 + 255); lane l fetches logical slot l ^ swz
         // (N % 256 == 0 and K % 128 == 0: the launcher sends other shapes to gemm_f16x2_dyn_kernel)
-        pa = (const f16*)P.A2 + (t0 + lw * 8) * a_row + (size_t)n0 * 2;
-        pw = (const f16*)P.W2 + (t0 + lw * 8) * w_row + (size_t)k0 * 2;
+        pa = (const f16*)P.A2 + (t0 + lw * 8) * a_row + (size_t)n0 * (HI ? 1 : 2);
+        pw = (const f16*)P.W2 + (t0 + lw * 8) * w_row + (size_t)k0 * (HI ? 1 : 2);
       }
-      char* base = smem + slot * XSTAGE;
+      char* base = smem + slot * STAGE;
       const size_t ro = (size_t)ks * XBK;              // token rows into the chunk
+      if constexpr (HI) {
+        // this wave's token rows lw 8 .. lw 8 + 7 of the k-step: A pieces of two rows (32 lanes each), W pieces of four (16 lanes each)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int rr = 2 * i + (lane >> 5);              // row within the wave's eight; (lw 8 + rr) & 7 == rr
+          __builtin_amdgcn_global_load_lds(GPTR(pa + (ro + rr) * a_row + (((lane & 31) ^ (rr << 1)) << 3)),
+                                           LPTR(base + (lw * 8 + 2 * i) * 512), 16, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int rr = 4 * i + (lane >> 4);
+          __builtin_amdgcn_global_load_lds(GPTR(pw + (ro + rr) * w_row + (((lane & 15) ^ (rr << 1)) << 3)),
+                                           LPTR(base + A_BYTES + (lw * 8 + 4 * i) * 256), 16, 0, 0);
+        }
+      } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int r = lw * 8 + i;                      // token row of the k-step; r & 7 == i
@@ -342,13 +383,14 @@ __global__ __launch_bounds__(768) void gemm_f16x2_tn_kernel(D3dpTnTable tb, int 
         __builtin_amdgcn_global_load_lds(GPTR(pw + (ro + 2 * i + (lane >> 5)) * w_row + ((l32 ^ ((r & 7) << 1)) << 3)),
                                          LPTR(base + XA_BYTES + (lw * 8 + 2 * i) * 512), 16, 0, 0);
       }
+      }
       if (++ks == NKz) { ks = 0; ++ti; }
       slot = (slot == XNSTAGE - 1) ? 0 : slot + 1;
     };
     issue();
     if (gtot > 1) issue();
     for (int g = 0; g < gtot; ++g) {
-      if (g + 1 < gtot) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+      if (g + 1 < gtot) { if constexpr (HI) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); }
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       X2_BARRIER();
       if (g + 2 < gtot) issue();
@@ -362,8 +404,15 @@ __global__ __launch_bounds__(768) void gemm_f16x2_tn_kernel(D3dpTnTable tb, int 
   const int j = fi >> 2, qd = fi & 3, row = 4 * fg + j;        // transposed read: lanes 4 j .. 4 j + 3 point at token row 4 fg + j
   // slot of the 16 features (mi / ni) x plane inside a token row: block b = wr 2 + (mi >> 1) (A) / wc 2 + (ni >> 1) (W),
   // slot = b 8 + plane 4 + (mi & 1) 2 + (qd >> 1); the swizzle of rows `row` and `row + 16` is the same (r & 7)
-  auto a_off = [&](int mi, int pl) { return row * 1024 + (((((wr * 2 + (mi >> 1)) << 3) | (pl << 2) | ((mi & 1) << 1) | (qd >> 1)) ^ ((row & 7) << 1)) << 4) + ((qd & 1) << 3); };
-  auto w_off = [&](int ni, int pl) { return XA_BYTES + row * 512 + (((((wc * 2 + (ni >> 1)) << 3) | (pl << 2) | ((ni & 1) << 1) | (qd >> 1)) ^ ((row & 7) << 1)) << 4) + ((qd & 1) << 3); };
+  // (HI: no plane bit -- slot = b 4 + (mi & 1) 2 + (qd >> 1) of a 512 B / 256 B row)
+  auto a_off = [&](int mi, int pl) {
+    if constexpr (HI) return row * 512 + (((((wr * 2 + (mi >> 1)) << 2) | ((mi & 1) << 1) | (qd >> 1)) ^ ((row & 7) << 1)) << 4) + ((qd & 1) << 3);
+    else return row * 1024 + (((((wr * 2 + (mi >> 1)) << 3) | (pl << 2) | ((mi & 1) << 1) | (qd >> 1)) ^ ((row & 7) << 1)) << 4) + ((qd & 1) << 3);
+  };
+  auto w_off = [&](int ni, int pl) {
+    if constexpr (HI) return A_BYTES + row * 256 + (((((wc * 2 + (ni >> 1)) << 2) | ((ni & 1) << 1) | (qd >> 1)) ^ ((row & 7) << 1)) << 4) + ((qd & 1) << 3);
+    else return XA_BYTES + row * 512 + (((((wc * 2 + (ni >> 1)) << 3) | (pl << 2) | ((ni & 1) << 1) | (qd >> 1)) ^ ((row & 7) << 1)) << 4) + ((qd & 1) << 3);
+  };
   typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
   typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
   auto tr8 = [&](const char* p, int second) {         // 8 tokens of one feature: rows 4 fg + {0..3} and 16 + 4 fg + {0..3}
@@ -389,18 +438,18 @@ __global__ __launch_bounds__(768) void gemm_f16x2_tn_kernel(D3dpTnTable tb, int 
     for (int ks = 0; ks < NKz; ++ks) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       X2_BARRIER();
-      const char* sb = smem + slot * XSTAGE;
+      const char* sb = smem + slot * STAGE;
       slot = (slot == XNSTAGE - 1) ? 0 : slot + 1;
       f16x8 wf[4][2];
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-        for (int pl = 0; pl < (PASSES == 3 ? 2 : 1); ++pl) wf[ni][pl] = tr8(sb + offW[ni][pl], 16 * 512);
+        for (int pl = 0; pl < (PASSES == 3 ? 2 : 1); ++pl) wf[ni][pl] = tr8(sb + offW[ni][pl], 16 * W_ROW);
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
-        const f16x8 ah = tr8(sb + offA[mi][0], 16 * 1024);
+        const f16x8 ah = tr8(sb + offA[mi][0], 16 * A_ROW);
         if constexpr (PASSES == 3) {
-          const f16x8 al = tr8(sb + offA[mi][1], 16 * 1024);
+          const f16x8 al = tr8(sb + offA[mi][1], 16 * A_ROW);
 #pragma unroll
           for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wf[ni][1], acc[mi][ni], 0, 0, 0);
 #pragma unroll
@@ -437,8 +486,12 @@ __device__ __forceinline__ float dyn_scale(unsigned amax_bits) {
   return ldexpf(1.0f, 14 - e);
 }
 
+// HI (template parameter of the operand kernels below; D3DP_TRAIN_ROWS=hi): the destination rows are hi-only, [.][C] plain fp16 with
+// column c at offset c -- the hi value of split2h_scaled at the same scale, no lo value and no store of one.
+
 // src [R][C] fp32 -> dst [R][2 Cpad] h2i (columns C .. Cpad - 1 zero), scale from the tensor's absmax; unscale[0] = 1 / scale.
 // A thread owns 8 consecutive columns (C % 8 == 0, Cpad % 32 == 0): two 16-byte loads, one 16-byte store per plane.
+template <bool HI = false>
 __global__ void split2h_dyn_kernel(const float* __restrict__ s, f16* __restrict__ d, int R, int C, int Cpad,
                                    const unsigned* __restrict__ amax, float* __restrict__ unscale) {
   const float sc = dyn_scale(amax[0]);
@@ -455,9 +508,9 @@ __global__ void split2h_dyn_kernel(const float* __restrict__ s, f16* __restrict_
 #pragma unroll
       for (int e = 0; e < 8; ++e) { f16 h, l; split2h_scaled(v[e] * sc, h, l); hi[e] = h; lo[e] = l; }
     }
-    f16* row = d + r * 2 * (size_t)Cpad + h2i_col(c);
+    f16* row = HI ? d + r * (size_t)Cpad + c : d + r * 2 * (size_t)Cpad + h2i_col(c);
     *reinterpret_cast<f16x8*>(row) = hi;
-    *reinterpret_cast<f16x8*>(row + kH2iLo) = lo;
+    if constexpr (!HI) *reinterpret_cast<f16x8*>(row + kH2iLo) = lo;
   }
 }
 
@@ -592,7 +645,7 @@ __global__ __launch_bounds__(256) void dyprep_kernel(const float* __restrict__ s
 // kernel read again).  `amax` then holds the absmax of SRC (left by the fc2 dgrad's epilogue) and the operand scale follows
 // from the bound |gelu'| <= 1.13: at most one binade below the scale of the true absmax whenever the largest |src| sits where
 // gelu' >= 0.57, and never an overflow -- the two fp16 planes keep 22 bits below whatever power of two is chosen.
-template <int P, bool GELU>
+template <int P, bool GELU, bool HI = false>
 __global__ __launch_bounds__(256) void rowprep_kernel(const float* __restrict__ s, f16* __restrict__ drow, float* __restrict__ colpart,
                                                       int R, int Rpad, int C, const unsigned* __restrict__ amax,
                                                       float* __restrict__ unscale, const float* __restrict__ mask, int axis, int F,
@@ -644,9 +697,9 @@ __global__ __launch_bounds__(256) void rowprep_kernel(const float* __restrict__ 
           f16x8 hi, lo;
 #pragma unroll
           for (int e = 0; e < 8; ++e) { acc[p][e] += v[e]; f16 h, lw; split2h_scaled(v[e] * sc, h, lw); hi[e] = h; lo[e] = lw; }
-          f16* row = drow + (size_t)r * 2 * C + h2i_col(c);
+          f16* row = HI ? drow + (size_t)r * C + c : drow + (size_t)r * 2 * C + h2i_col(c);
           *reinterpret_cast<f16x8*>(row) = hi;
-          *reinterpret_cast<f16x8*>(row + kH2iLo) = lo;
+          if constexpr (!HI) *reinterpret_cast<f16x8*>(row + kH2iLo) = lo;
         }
       }
   }
@@ -665,6 +718,7 @@ __global__ __launch_bounds__(256) void rowprep_kernel(const float* __restrict__ 
 // zero), the scale from `amax` -- which the kernel that produced src left there as the absmax of this very LayerNorm output,
 // computed on the fly and not stored.  The forward pass of the training step then never writes the fp32 normalised activation
 // (its only reader was this operand pass).  One wave per row, a lane owns 8 consecutive columns (C <= 512, C % 8 == 0).
+template <bool HI = false>
 __global__ __launch_bounds__(256) void rowprep_ln_kernel(const float* __restrict__ s, const float* __restrict__ w,
                                                          const float* __restrict__ b, float eps, f16* __restrict__ drow, int R,
                                                          int Rpad, int C, const unsigned* __restrict__ amax,
@@ -729,9 +783,9 @@ __global__ __launch_bounds__(256) void rowprep_ln_kernel(const float* __restrict
           split2h_scaled(y * sc, h, lw);
           hi[e] = h; lo[e] = lw;
         }
-        f16* row = drow + (size_t)r * 2 * C + h2i_col(c);
+        f16* row = HI ? drow + (size_t)r * C + c : drow + (size_t)r * 2 * C + h2i_col(c);
         *reinterpret_cast<f16x8*>(row) = hi;
-        *reinterpret_cast<f16x8*>(row + kH2iLo) = lo;
+        if constexpr (!HI) *reinterpret_cast<f16x8*>(row + kH2iLo) = lo;
       }
     }
   }
@@ -743,6 +797,7 @@ __global__ __launch_bounds__(256) void rowprep_ln_kernel(const float* __restrict
 // which the fc1 Linear's epilogue leaves in `pmax` (gemm_f16x2_dyn_kernel, amax_pos): GELU is increasing on x > -0.75 and
 // |GELU(x)| <= 0.17 for x < 0, so max |GELU| = max(GELU(pmax), at most 0.17) -- exact whenever GELU(pmax) >= 0.17, and the
 // same power of two otherwise unless every activation is tiny.  Writes amax_out[0] (the bits of that bound) and unscale[0].
+template <bool HI = false>
 __global__ __launch_bounds__(256) void gelu_rowprep_kernel(const float* __restrict__ s, f16* __restrict__ drow, int R, int Rpad,
                                                            int C, const unsigned* __restrict__ pmax, unsigned* __restrict__ amax_out,
                                                            float* __restrict__ unscale) {
@@ -780,9 +835,9 @@ __global__ __launch_bounds__(256) void gelu_rowprep_kernel(const float* __restri
           split2h_scaled(g * sc, h, l);
           hi[e] = h; lo[e] = l;
         }
-        f16* row = drow + r * 2 * (size_t)C + h2i_col(c);
+        f16* row = HI ? drow + r * (size_t)C + c : drow + r * 2 * (size_t)C + h2i_col(c);
         *reinterpret_cast<f16x8*>(row) = hi;
-        *reinterpret_cast<f16x8*>(row + kH2iLo) = lo;
+        if constexpr (!HI) *reinterpret_cast<f16x8*>(row + kH2iLo) = lo;
       }
     }
   }
@@ -807,12 +862,13 @@ __global__ __launch_bounds__(256) void wprep_absmax_kernel(D3dpWPrepTable tb, un
   if (threadIdx.x == 0) atomicMax(amax + it.slot, __float_as_uint(fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]))));
 }
 // rows form [N][2 K] (the forward operand) of every weight: the loop of split2h_dyn_kernel
+template <bool HI = false>
 __global__ __launch_bounds__(256) void wprep_rows_kernel(D3dpWPrepTable tb, f16* __restrict__ base, const unsigned* __restrict__ amax,
                                                          float* __restrict__ unscale) {
   const D3dpWPrepItem it = tb.it[blockIdx.y];
   const float sc = dyn_scale(amax[it.slot]);
   if (blockIdx.x == 0 && threadIdx.x == 0) unscale[it.slot] = 1.0f / sc;
-  f16* d = base + 2 * it.off;
+  f16* d = base + 2 * it.off;                           // (HI too: the start of the same region, half used)
   const int G8 = it.K / 8;
   const size_t n = (size_t)it.N * G8;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -823,18 +879,20 @@ __global__ __launch_bounds__(256) void wprep_rows_kernel(D3dpWPrepTable tb, f16*
     f16x8 hi, lo;
 #pragma unroll
     for (int e = 0; e < 8; ++e) { f16 h, l; split2h_scaled(v[e] * sc, h, l); hi[e] = h; lo[e] = l; }
-    f16* row = d + r * 2 * (size_t)it.K + h2i_col(c);
+    f16* row = HI ? d + r * (size_t)it.K + c : d + r * 2 * (size_t)it.K + h2i_col(c);
     *reinterpret_cast<f16x8*>(row) = hi;
-    *reinterpret_cast<f16x8*>(row + kH2iLo) = lo;
+    if constexpr (!HI) *reinterpret_cast<f16x8*>(row + kH2iLo) = lo;
   }
 }
 // transposed form [K][2 N] (the dgrad operand) of every weight: the tiles of split2h_t_dyn_kernel, strided over by a
 // workgroup row (N % 32 == 0, K % 32 == 0)
+// (HI: [K][N] hi-only -- source row r0 + tx lands at column r0 + tx of destination row c0 + k)
+template <bool HI = false>
 __global__ __launch_bounds__(256) void wprep_cols_kernel(D3dpWPrepTable tb, f16* __restrict__ base, const unsigned* __restrict__ amax) {
   __shared__ float tile[32][33];
   const D3dpWPrepItem it = tb.it[blockIdx.y];
   const float sc = dyn_scale(amax[it.slot]);
-  f16* d = base + 2 * it.off;
+  f16* d = base + 2 * it.off;                           // (HI too: the start of the same region, half used)
   const int tr = it.N / 32, tc = it.K / 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   for (int tI = blockIdx.x; tI < tr * tc; tI += gridDim.x) {
@@ -845,9 +903,13 @@ __global__ __launch_bounds__(256) void wprep_cols_kernel(D3dpWPrepTable tb, f16*
     for (int k = ty; k < 32; k += 8) {
       f16 a, b;
       split2h_scaled(tile[tx][k], a, b);
-      f16* blk = d + (size_t)(c0 + k) * 2 * it.N + (size_t)(r0 / 32) * 64;
-      blk[tx] = a;
-      blk[32 + tx] = b;
+      if constexpr (HI) {
+        d[(size_t)(c0 + k) * it.N + r0 + tx] = a;
+      } else {
+        f16* blk = d + (size_t)(c0 + k) * 2 * it.N + (size_t)(r0 / 32) * 64;
+        blk[tx] = a;
+        blk[32 + tx] = b;
+      }
     }
   }
 }
@@ -928,15 +990,18 @@ __global__ __launch_bounds__(256) void sum_partials_bias_kernel(const float* __r
 // out_z[M, N] = A2 (chunk z) . W2 (chunk z)^T x dynA x dynW (+ bias): Kfull = Z NKz 32 columns per operand row
 int d3dp_launch_linear_f16x2_dyn(const void* A2, const void* W2, const float* bias, const float* dynA, const float* dynW,
                                  float* out, int M, int N, int Kfull, int Z, hipStream_t st, unsigned* amax_out, int amax_pos,
-                                 int rem_blocks, int passes) {
+                                 int rem_blocks, int passes, int rows_hi) {
   if (M <= 0 || N % 4 != 0 || Z < 1 || Kfull % (XBK * Z) != 0 || (amax_out && Z != 1) || (passes != 1 && passes != 3)) return -1;
+  // hi-only rows: a stage is a 128-byte line of 64 k, so every chunk of the contraction is a whole number of k-step PAIRS -- the
+  // grouping of the one-pass form on split rows is kept or the launch is refused, never regrouped
+  if (rows_hi && (passes != 1 || Kfull % (2 * XBK * Z) != 0)) return -1;
   const int NKz = Kfull / XBK / Z;
   // rem_blocks: the rows behind the last whole 256-row tile as 16 x 64 blocks at the end of the kernel (see there)
   const bool rem = rem_blocks && Z == 1 && M > XBM && M % XBM != 0 && NKz % (2 * XNCW) == 0;
   const int tm = rem ? M / XBM : (M + XBM - 1) / XBM, tn = (N + XBN - 1) / XBN;
-  static PerDeviceOnce once, once1;                    // (one opt-in per kernel: the one-pass twin asks when it is first launched)
-  const auto kern = passes == 1 ? gemm_f16x2_dyn_kernel<1> : gemm_f16x2_dyn_kernel<3>;
-  const int cus = (passes == 1 ? once1 : once).get([&](int dev) {
+  static PerDeviceOnce once, once1, once_hi;           // (one opt-in per kernel: the one-pass twins ask when they are first launched)
+  const auto kern = rows_hi ? gemm_f16x2_dyn_kernel<1, true> : passes == 1 ? gemm_f16x2_dyn_kernel<1> : gemm_f16x2_dyn_kernel<3>;
+  const int cus = (rows_hi ? once_hi : passes == 1 ? once1 : once).get([&](int dev) {
     return d3dp_lds_opt_in(reinterpret_cast<const void*>(kern), XNSTAGE * XSTAGE + 64) < 0 ? -3 : d3dp_cu_count(dev);
   });
   if (cus < 0) return -3;
@@ -948,10 +1013,10 @@ int d3dp_launch_linear_f16x2_dyn(const void* A2, const void* W2, const float* bi
 }
 
 void d3dp_launch_split2_dyn(const float* src, void* dst, int R, int C, int Cpad, const unsigned* amax, float* unscale,
-                            hipStream_t st) {
+                            hipStream_t st, int rows_hi) {
   const size_t n = (size_t)R * (Cpad / 8);
   const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-  hipLaunchKernelGGL(split2h_dyn_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, st, src, (f16*)dst, R, C, Cpad, amax, unscale);
+  hipLaunchKernelGGL((rows_hi ? split2h_dyn_kernel<true> : split2h_dyn_kernel<false>), dim3(blocks ? blocks : 1), dim3(256), 0, st, src, (f16*)dst, R, C, Cpad, amax, unscale);
 }
 
 void d3dp_launch_split2_t_dyn(const float* src, void* dst, int R, int C, int Rpad, const unsigned* amax, float* unscale,
@@ -971,16 +1036,16 @@ int d3dp_launch_dyprep(const float* src, void* drow, void* dcol, float* colpart,
 
 // the row form alone (+ column sums): see rowprep_kernel.  *rows = partial rows written to colpart (<= D3DP_ROWPREP_ROWS)
 int d3dp_launch_rowprep_ln(const float* src, const float* w, const float* b, float eps, void* drow, int R, int Rpad, int C,
-                           const unsigned* amax, float* unscale, hipStream_t st) {
+                           const unsigned* amax, float* unscale, hipStream_t st, int rows_hi) {
   if (C % 32 != 0 || C > 512 || Rpad < R || !w || !b) return -1;
   int g = (Rpad + 3) / 4;
   if (g > 1024) g = 1024;
-  hipLaunchKernelGGL(rowprep_ln_kernel, dim3(g), dim3(256), 0, st, src, w, b, eps, (f16*)drow, R, Rpad, C, amax, unscale);
+  hipLaunchKernelGGL((rows_hi ? rowprep_ln_kernel<true> : rowprep_ln_kernel<false>), dim3(g), dim3(256), 0, st, src, w, b, eps, (f16*)drow, R, Rpad, C, amax, unscale);
   return 0;
 }
 
 int d3dp_launch_rowprep(const float* src, void* drow, float* colpart, int* rows, int R, int Rpad, int C, const unsigned* amax,
-                        float* unscale, hipStream_t st, const float* mask, int axis, int F, int J, const float* gelu_pre) {
+                        float* unscale, hipStream_t st, const float* mask, int axis, int F, int J, const float* gelu_pre, int rows_hi) {
   if (C % 32 != 0 || Rpad < R || C > 1536) return -1;      // (P = ceil(C / 512) column passes; a lane whose 8 columns lie behind C idles)
   int g = (Rpad + 3) / 4;
   const int cap = colpart ? D3DP_ROWPREP_ROWS : 1024;   // (every workgroup leaves one partial row of column sums)
@@ -989,7 +1054,7 @@ int d3dp_launch_rowprep(const float* src, void* drow, float* colpart, int* rows,
   const int P = (C + 511) / 512;
   f16* d = (f16*)drow;
   if (mask && (J < 1 || F < 1)) return -1;
-#define D3DP_ROWPREP(PP, GG) hipLaunchKernelGGL((rowprep_kernel<PP, GG>), dim3(g), dim3(256), 0, st, src, d, colpart, R, Rpad, C, amax, unscale, mask, axis, F, J, gelu_pre)
+#define D3DP_ROWPREP(PP, GG) hipLaunchKernelGGL((rows_hi ? rowprep_kernel<PP, GG, true> : rowprep_kernel<PP, GG, false>), dim3(g), dim3(256), 0, st, src, d, colpart, R, Rpad, C, amax, unscale, mask, axis, F, J, gelu_pre)
   if (gelu_pre) {
     if (P == 1) D3DP_ROWPREP(1, true); else if (P == 2) D3DP_ROWPREP(2, true); else D3DP_ROWPREP(3, true);
   } else {
@@ -1000,11 +1065,11 @@ int d3dp_launch_rowprep(const float* src, void* drow, float* colpart, int* rows,
 }
 
 int d3dp_launch_gelu_rowprep(const float* src, void* drow, int R, int Rpad, int C, const unsigned* pmax, unsigned* amax_out,
-                             float* unscale, hipStream_t st) {
+                             float* unscale, hipStream_t st, int rows_hi) {
   if (C % 32 != 0 || Rpad < R) return -1;
   const size_t n = (size_t)Rpad * (C / 8);
   const unsigned blocks = (unsigned)((n + 511) / 512 < 2048 ? (n + 511) / 512 : 2048);
-  hipLaunchKernelGGL(gelu_rowprep_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, st, src, (f16*)drow, R, Rpad, C, pmax, amax_out, unscale);
+  hipLaunchKernelGGL((rows_hi ? gelu_rowprep_kernel<true> : gelu_rowprep_kernel<false>), dim3(blocks ? blocks : 1), dim3(256), 0, st, src, (f16*)drow, R, Rpad, C, pmax, amax_out, unscale);
   return 0;
 }
 
@@ -1012,8 +1077,8 @@ int d3dp_launch_gelu_rowprep(const float* src, void* drow, int R, int Rpad, int 
 // beyond the real ones zero), N % 256 == 0, K % 128 == 0 (d3dp_tn_applies)
 static_assert(XBM == D3DP_TN_TILE_N && XBN == D3DP_TN_TILE_K, "train_plan.h: the tile d3dp_tn_applies asks whole multiples of");
 // n products over the same Tp token rows in one launch: out_p,z[N_p, K_p] (z = 0 .. Z - 1, N_p K_p floats apart)
-int d3dp_launch_linear_f16x2_tn_many(const D3dpTnProduct* prods, int n, int Tp, int Z, hipStream_t st, int passes) {
-  if (n < 1 || n > D3DP_TN_MAX || Z < 1 || Tp % (XBK * Z) != 0 || (passes != 1 && passes != 3)) return -1;
+int d3dp_launch_linear_f16x2_tn_many(const D3dpTnProduct* prods, int n, int Tp, int Z, hipStream_t st, int passes, int rows_hi) {
+  if (n < 1 || n > D3DP_TN_MAX || Z < 1 || Tp % (XBK * Z) != 0 || (passes != 1 && passes != 3) || (rows_hi && passes != 1)) return -1;
   D3dpTnTable tb{};
   tb.n = n;
   int tiles = 0;
@@ -1025,29 +1090,31 @@ int d3dp_launch_linear_f16x2_tn_many(const D3dpTnProduct* prods, int n, int Tp, 
     tiles += (tb.p[i].N / XBM) * tb.p[i].tiles_k;
   }
   const int NKz = Tp / XBK / Z;
-  static PerDeviceOnce once, once1;
-  const auto kern = passes == 1 ? gemm_f16x2_tn_kernel<1> : gemm_f16x2_tn_kernel<3>;
-  const int cus = (passes == 1 ? once1 : once).get([&](int dev) {
-    return d3dp_lds_opt_in(reinterpret_cast<const void*>(kern), XNSTAGE * XSTAGE) < 0 ? -3 : d3dp_cu_count(dev);
+  static PerDeviceOnce once, once1, once_hi;
+  const auto kern = rows_hi ? gemm_f16x2_tn_kernel<1, true> : passes == 1 ? gemm_f16x2_tn_kernel<1> : gemm_f16x2_tn_kernel<3>;
+  const int lds = XNSTAGE * (rows_hi ? XTN_HI_STAGE : XSTAGE);
+  const int cus = (rows_hi ? once_hi : passes == 1 ? once1 : once).get([&](int dev) {
+    return d3dp_lds_opt_in(reinterpret_cast<const void*>(kern), lds) < 0 ? -3 : d3dp_cu_count(dev);
   });
   if (cus < 0) return -3;
   const int items = tiles * Z, grid = items < cus ? items : cus;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3((XNCW + 4) * 64), XNSTAGE * XSTAGE, st, tb, NKz, tiles, items);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3((XNCW + 4) * 64), lds, st, tb, NKz, tiles, items);
   return 0;
 }
 int d3dp_launch_linear_f16x2_tn(const void* A2, const void* W2, const float* dynA, const float* dynW, float* out, int N, int K,
-                                int Tp, int Z, hipStream_t st, int passes) {
+                                int Tp, int Z, hipStream_t st, int passes, int rows_hi) {
   const D3dpTnProduct one{A2, W2, dynA, dynW, out, N, K, 0, 0};
-  return d3dp_launch_linear_f16x2_tn_many(&one, 1, Tp, Z, st, passes);
+  return d3dp_launch_linear_f16x2_tn_many(&one, 1, Tp, Z, st, passes, rows_hi);
 }
 
-int d3dp_launch_wprep(const D3dpWPrepTable& tb, void* rows_base, void* cols_base, unsigned* amax, float* unscale, hipStream_t st) {
+int d3dp_launch_wprep(const D3dpWPrepTable& tb, void* rows_base, void* cols_base, unsigned* amax, float* unscale, hipStream_t st,
+                      int rows_hi) {
   if (tb.n < 1 || tb.n > D3DP_WPREP_MAX) return -1;
   for (int i = 0; i < tb.n; ++i)
     if (tb.it[i].N % 32 != 0 || tb.it[i].K % 32 != 0) return -1;
   hipLaunchKernelGGL(wprep_absmax_kernel, dim3(16, tb.n), dim3(256), 0, st, tb, amax);
-  hipLaunchKernelGGL(wprep_rows_kernel, dim3(32, tb.n), dim3(256), 0, st, tb, (f16*)rows_base, (const unsigned*)amax, unscale);
-  hipLaunchKernelGGL(wprep_cols_kernel, dim3(32, tb.n), dim3(256), 0, st, tb, (f16*)cols_base, (const unsigned*)amax);
+  hipLaunchKernelGGL((rows_hi ? wprep_rows_kernel<true> : wprep_rows_kernel<false>), dim3(32, tb.n), dim3(256), 0, st, tb, (f16*)rows_base, (const unsigned*)amax, unscale);
+  hipLaunchKernelGGL((rows_hi ? wprep_cols_kernel<true> : wprep_cols_kernel<false>), dim3(32, tb.n), dim3(256), 0, st, tb, (f16*)cols_base, (const unsigned*)amax);
   return 0;
 }
 

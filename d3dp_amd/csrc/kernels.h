@@ -110,17 +110,20 @@ void d3dp_launch_nonfinite_flag(const float* x, size_t n, unsigned* flag, hipStr
 //  all workgroups instead of a last row of mostly empty 256 x 128 tiles; ignored where the conditions do not hold)
 // (passes: 3 = the split scheme; 1 = the hi x hi pass alone -- D3DP_TRAIN_PASSES=1: fp16 operands at their own scale, fp32
 //  accumulation; the same operand rows, of which the lo halves are not read.  Also of the two TN launchers below.)
+// (rows_hi: D3DP_TRAIN_ROWS=hi -- the operand rows are hi-only, "h1": [.][K] plain fp16, column c at offset c; passes = 1 alone,
+//  Kfull % (64 Z) == 0, else refused.  The operand launchers below take the same flag and then write such rows: the hi value of
+//  split2h_scaled at the same scale, no lo value.  Also of the two TN launchers.)
 int d3dp_launch_linear_f16x2_dyn(const void* A2, const void* W2, const float* bias, const float* dynA, const float* dynW,
                                  float* out, int M, int N, int Kfull, int Z, hipStream_t st, unsigned* amax_out = nullptr,
-                                 int amax_pos = 0, int rem_blocks = 0, int passes = 3);
+                                 int amax_pos = 0, int rem_blocks = 0, int passes = 3, int rows_hi = 0);
 // drow [Rpad][2 C] = split(GELU(src [R][C])) (rows R .. Rpad - 1 zero) at the scale max(GELU(pmax), 0.17) asks for (pmax: the
 // largest positive value of src, left by the Linear that produced it); writes that bound to amax_out[0] and 1 / scale to unscale[0]
 int d3dp_launch_gelu_rowprep(const float* src, void* drow, int R, int Rpad, int C, const unsigned* pmax, unsigned* amax_out,
-                             float* unscale, hipStream_t st);
+                             float* unscale, hipStream_t st, int rows_hi = 0);
 // src [R][C] fp32 -> h2i [R][2 Cpad] (zero columns behind C) at the power of two the tensor's absmax (amax[0], bits of a
 // float >= 0, d3dp_launch_absmax) asks for; unscale[0] = 1 / that scale
 void d3dp_launch_split2_dyn(const float* src, void* dst, int R, int C, int Cpad, const unsigned* amax, float* unscale,
-                            hipStream_t st);
+                            hipStream_t st, int rows_hi = 0);
 // the TRANSPOSE as a split operand: src [R][C] -> h2i [C][2 Rpad] (zero behind R; Rpad % 32 == 0)
 void d3dp_launch_split2_t_dyn(const float* src, void* dst, int R, int C, int Rpad, const unsigned* amax, float* unscale,
                               hipStream_t st);
@@ -134,15 +137,15 @@ int d3dp_launch_dyprep(const float* src, void* drow, void* dcol, float* colpart,
 // (gelu_pre: optional [R][C]; the operand is src x gelu'(gelu_pre) and amax[0] holds the absmax of SRC, see rowprep_kernel)
 int d3dp_launch_rowprep(const float* src, void* drow, float* colpart, int* rows, int R, int Rpad, int C, const unsigned* amax,
                         float* unscale, hipStream_t st, const float* mask = nullptr, int axis = 0, int F = 1, int J = 1,
-                        const float* gelu_pre = nullptr);
+                        const float* gelu_pre = nullptr, int rows_hi = 0);
 // drow = split(LayerNorm(src; w, b, eps)): the operand of a Linear fed by a LayerNorm, from the LayerNorm's INPUT (amax: the
 // absmax of the LayerNorm's output, left by the kernel that produced src); C <= 512
 int d3dp_launch_rowprep_ln(const float* src, const float* w, const float* b, float eps, void* drow, int R, int Rpad, int C,
-                           const unsigned* amax, float* unscale, hipStream_t st);
+                           const unsigned* amax, float* unscale, hipStream_t st, int rows_hi = 0);
 // wgrad straight from the ROW forms (gemm_f16x2_tn_kernel): out_z[N, K] = sum_{t in chunk z} A2[t][n] W2[t][k] x dynA x dynW,
 // Tp = Z NKz 32 rows per operand (rows beyond the real ones zero).  d3dp_tn_applies: N % 256 == 0 and K % 128 == 0.
 int d3dp_launch_linear_f16x2_tn(const void* A2, const void* W2, const float* dynA, const float* dynW, float* out, int N, int K,
-                                int Tp, int Z, hipStream_t st, int passes = 3);
+                                int Tp, int Z, hipStream_t st, int passes = 3, int rows_hi = 0);
 // ... several such products over the same Tp rows in one launch (the weight gradients of a block): one merged tile list, one Z
 struct D3dpTnProduct {
   const void* A2; const void* W2;                      // [Tp][2 N] and [Tp][2 K] row forms
@@ -152,14 +155,16 @@ struct D3dpTnProduct {
   int tiles_k, tile0;                                  // (filled by the launcher)
 };
 struct D3dpTnTable { D3dpTnProduct p[D3DP_TN_MAX]; int n; };
-int d3dp_launch_linear_f16x2_tn_many(const D3dpTnProduct* prods, int n, int Tp, int Z, hipStream_t st, int passes = 3);
+int d3dp_launch_linear_f16x2_tn_many(const D3dpTnProduct* prods, int n, int Tp, int Z, hipStream_t st, int passes = 3, int rows_hi = 0);
 struct D3dpSumTable { const float* part[D3DP_TN_MAX]; float* out[D3DP_TN_MAX]; size_t n4[D3DP_TN_MAX]; int Z; int n; };
 void d3dp_launch_sum_partials_many(const D3dpSumTable& tb, hipStream_t st);   // out_p[i] = sum_z part_p[z n_p + i], z ascending
 // the training step's weight operands in three launches: absmax -> slot, rows form [N][2 K] at rows_base + 2 off
 // halves, transposed form [K][2 N] at cols_base + 2 off halves, unscale[slot] = 1 / scale
 struct D3dpWPrepItem { const float* w; int N, K, slot, pad; size_t off; };
 struct D3dpWPrepTable { D3dpWPrepItem it[D3DP_WPREP_MAX]; int n; };
-int d3dp_launch_wprep(const D3dpWPrepTable& tb, void* rows_base, void* cols_base, unsigned* amax, float* unscale, hipStream_t st);
+// (rows_hi: both forms hi-only, [N][K] and [K][N], at the same rows_base / cols_base + 2 off halves -- the first half of each weight's region)
+int d3dp_launch_wprep(const D3dpWPrepTable& tb, void* rows_base, void* cols_base, unsigned* amax, float* unscale, hipStream_t st,
+                      int rows_hi = 0);
 // out[i] = sum over z of part[z n + i], z ascending
 void d3dp_launch_sum_partials(const float* part, float* out, size_t n, int Z, hipStream_t st);
 void d3dp_launch_sum_partials_bias(const float* part, const float* bias, float* out, size_t n, int N, int Z, hipStream_t st,
@@ -292,13 +297,14 @@ extern "C" int d3dp_clip_count(int32_t n, int32_t F);
 // x_out = x_in + mask[sample] y ; xn = LN(x_out)  (xn may be null: only amax, the absmax of LN(x_out), is produced)
 int d3dp_train_add_mask_ln(const float* x_in, const float* y, const float* mask, int axis, int F, int J, const float* w,
                            const float* b, float eps, float* x_out, float* xn, unsigned* amax, int T, int C, hipStream_t st,
-                           void* op = nullptr, int Tp = 0, float* op_unscale = nullptr);
+                           void* op = nullptr, int Tp = 0, float* op_unscale = nullptr, int op_hi = 0);
+// (op_hi, also below: the operand rows are hi-only [Tp][C] -- D3DP_TRAIN_ROWS=hi)
 // x_out = x_in + mask[sample] y ; x_next = LN_a(x_out) (+ pos[f]) ; xn = LN_b(x_next)  (wb null: no second norm; xn null with
 // wb given: LN_b's output is not stored, only its absmax)
 int d3dp_train_add_mask_ln2(const float* x_in, const float* y, const float* mask, int axis, int F, int J, const float* wa,
                             const float* ba, float eps_a, const float* pos, const float* wb, const float* bb, float eps_b,
                             float* x_out, float* x_next, float* xn, unsigned* amax, int T, int C, hipStream_t st, void* op = nullptr,
-                            int Tp = 0, float* op_unscale = nullptr);
+                            int Tp = 0, float* op_unscale = nullptr, int op_hi = 0);
 int d3dp_train_ln_pos(const float* x, const float* w, const float* b, float eps, const float* pos, int F, int J, float* y,
                       int T, int C, hipStream_t st);
 // LayerNorm backward, one (xa == null) or two chained LayerNorms (y = LN_b(xb), xb = LN_a(xa) (+ pos)) in one pass:
@@ -337,7 +343,7 @@ int d3dp_train_attn_bwd(const float* qkv, const float* o, const float* dout, flo
 // (optional): absmax slot of the result.
 int d3dp_train_attn_x2_fwd(const float* qkv, float* out, void* stats, int n_seq, SeqMap map, int C, int heads,
                            const unsigned* amax_qkv, unsigned* amax_out, hipStream_t st, void* op = nullptr, int T = 0, int Tp = 0,
-                           float* op_unscale = nullptr, int passes = 3);
+                           float* op_unscale = nullptr, int passes = 3, int op_hi = 0);
 int d3dp_train_attn_x2_bwd(const float* qkv, const float* o, const float* dout, float* dqkv, void* stats, int n_seq, SeqMap map,
                            int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
                            hipStream_t st, int part = 0, int passes = 3);
@@ -351,6 +357,10 @@ int d3dp_train_attn_x2_padded(int which, const float* qkv, const float* o, const
 int d3dp_train_attn_x2_1p(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats,
                           int n_seq, SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do,
                           unsigned* amax_out, hipStream_t st, void* op, int T, int Tp, float* op_unscale);
+// train_attn_hi.hip: the forward with the proj operand as hi-only rows [Tp][C] (D3DP_TRAIN_ROWS=hi; passes 1 | 3, head dims 64 / 32);
+// called by train_attn.hip only
+int d3dp_train_attn_x2_fwd_hi(int passes, const float* qkv, float* out, void* stats, int n_seq, SeqMap map, int C, int heads,
+                              const unsigned* amax_qkv, unsigned* amax_out, hipStream_t st, void* op, int T, int Tp, float* op_unscale);
 int d3dp_train_embed_bwd(const float* dx, const float* x2d, const float* x3d, float* part, int T, int C, hipStream_t st);
 int d3dp_train_head_linear(const float* z, const float* w, const float* b, float* out, int T, int C, hipStream_t st);
 int d3dp_train_head_bwd(const float* g, const float* z, const float* w, float* dz, float* part, int* rows, int T, int C,

@@ -99,23 +99,30 @@ __device__ __forceinline__ float ln_operand_scale(const float (&wl)[NV], const f
   return ldexpf(1.0f, 14 - e);
 }
 // a lane's NV values of row `op_row` (TRow<C>::V4 layout: float4 groups at columns (g 64 + lane) 4) -> h2i split rows [.][2 C]
-template <int C, int NV>
+// (HI, D3DP_TRAIN_ROWS=hi: hi-only rows [.][C] -- the same hi value at column c, no lo value; kOpRow<C, HI> = fp16 elements per row)
+template <int C, bool HI>
+constexpr int kOpRow = HI ? C : 2 * C;
+template <int C, int NV, bool HI = false>
 __device__ __forceinline__ void store_operand_row(f16* op_row, int lane, const float (&v)[NV], float sc) {
 #pragma unroll
   for (int g = 0; g < NV / 4; ++g) {
     f16x4 hi, lo;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { f16 h, l; split2h_scaled(v[g * 4 + e] * sc, h, l); hi[e] = h; lo[e] = l; }
-    f16* d = op_row + h2i_col((g * 64 + lane) * 4);
-    *reinterpret_cast<f16x4*>(d) = hi;
-    *reinterpret_cast<f16x4*>(d + kH2iLo) = lo;
+    if constexpr (HI) {
+      *reinterpret_cast<f16x4*>(op_row + (g * 64 + lane) * 4) = hi;
+    } else {
+      f16* d = op_row + h2i_col((g * 64 + lane) * 4);
+      *reinterpret_cast<f16x4*>(d) = hi;
+      *reinterpret_cast<f16x4*>(d + kH2iLo) = lo;
+    }
   }
 }
 
 // ---- x_out = x_in + m[sample] * y ; xn = LN(x_out)  (+ absmax of xn: the fc1 operand) ------------------------------
 // (op != null, C % 256 == 0: LN(x_out) as split operand rows [Tp][2 C] at the scale of ln_operand_scale, rows T .. Tp - 1 zero;
 //  op_unscale[0] = 1 / scale, amax[0] = the bound)
-template <int C>
+template <int C, bool HI = false>
 __global__ __launch_bounds__(256) void add_mask_ln_kernel(const float* __restrict__ x_in, const float* __restrict__ y,
                                                           const float* __restrict__ mask, int axis, int F, int J,
                                                           const float* __restrict__ w, const float* __restrict__ b,
@@ -157,7 +164,7 @@ __global__ __launch_bounds__(256) void add_mask_ln_kernel(const float* __restric
       for (int i = 0; i < NV; ++i) v[i] = 0.f;           // (the TN weight-gradient product wants zero rows behind T)
     }
     if constexpr (R::V4) {
-      if (op) store_operand_row<C, NV>(op + (size_t)tok * 2 * C, lane, v, sc);
+      if (op) store_operand_row<C, NV, HI>(op + (size_t)tok * kOpRow<C, HI>, lane, v, sc);
     }
   }
   if (!(R::V4 && op)) block_amax_commit(am, amax);
@@ -167,7 +174,7 @@ __global__ __launch_bounds__(256) void add_mask_ln_kernel(const float* __restric
 //   x_out = x_in + m[sample] * y ;  x_next = LN_a(x_out) (+ pos[f]) ;  xn = LN_b(x_next)  (+ absmax of xn)
 // LN_a = the shared Spatial / Temporal norm, LN_b = the next block's norm1 (the head's LayerNorm after the last block;
 // wb == nullptr: no second norm; xn == nullptr: LN_b's output is not stored, only its absmax).  As three kernels (add_mask_ln, ln_pos, ln_pos) the row was written and read back twice.
-template <int C>
+template <int C, bool HI = false>
 __global__ __launch_bounds__(256) void add_mask_ln2_kernel(const float* __restrict__ x_in, const float* __restrict__ y,
                                                            const float* __restrict__ mask, int axis, int F, int J,
                                                            const float* __restrict__ wa, const float* __restrict__ ba, float eps_a,
@@ -201,7 +208,7 @@ __global__ __launch_bounds__(256) void add_mask_ln2_kernel(const float* __restri
         float z[NV];
 #pragma unroll
         for (int i = 0; i < NV; ++i) z[i] = 0.f;
-        store_operand_row<C, NV>(op + (size_t)tok * 2 * C, lane, z, 1.0f);
+        store_operand_row<C, NV, HI>(op + (size_t)tok * kOpRow<C, HI>, lane, z, 1.0f);
       }
   }
   for (int tok = blockIdx.x * 4 + (threadIdx.x >> 6); tok < T; tok += gridDim.x * 4) {
@@ -230,7 +237,7 @@ __global__ __launch_bounds__(256) void add_mask_ln2_kernel(const float* __restri
       for (int i = 0; i < NV; ++i) { v[i] = fmaf((v[i] - mean) * rstd, wbl[i], bbl[i]); am = fmaxf(am, fabsf(v[i])); }
       if (xn) R::store(xn + (size_t)tok * C, lane, v);
       if constexpr (R::V4) {
-        if (to_op) store_operand_row<C, NV>(op + (size_t)tok * 2 * C, lane, v, sc);
+        if (to_op) store_operand_row<C, NV, HI>(op + (size_t)tok * kOpRow<C, HI>, lane, v, sc);
       }
     }
   }
@@ -1154,13 +1161,25 @@ __global__ __launch_bounds__(256) void time_mlp_bwd_kernel(const int64_t* __rest
     default: return -2;                             \
   }
 
+#define TRAIN_DISPATCH_C256(C, ...)                 \
+  switch (C) {                                      \
+    case 512: { constexpr int CC = 512; __VA_ARGS__; break; } \
+    case 256: { constexpr int CC = 256; __VA_ARGS__; break; } \
+    default: return -2;                             \
+  }
+
 static int row_blocks(int T) { return (T + 3) / 4 < kRowBlocks ? (T + 3) / 4 : kRowBlocks; }
 int d3dp_train_add_mask_ln(const float* x_in, const float* y, const float* mask, int axis, int F, int J, const float* w,
                            const float* b, float eps, float* x_out, float* xn, unsigned* amax, int T, int C, hipStream_t st,
-                           void* op, int Tp, float* op_unscale) {
+                           void* op, int Tp, float* op_unscale, int op_hi) {
   if (!d3dp_width_instantiated(C))                     // (a run-time width: no operand rows)
     return op ? -2 : d3dp_train_g_add_mask_ln(x_in, y, mask, axis, F, J, w, b, eps, x_out, xn, amax, T, C, st);
   if (!w || !b || (!xn && !amax && !op) || (op && (C % 256 != 0 || Tp < T || !op_unscale))) return -1;
+  if (op && op_hi) {                                   // (operand rows exist at C % 256 == 0: the two widths below)
+    TRAIN_DISPATCH_C256(C, hipLaunchKernelGGL((add_mask_ln_kernel<CC, true>), dim3(row_blocks(T)), dim3(256), 0, st, x_in, y, mask, axis,
+                                              F, J, w, b, eps, x_out, xn, amax, T, (f16*)op, Tp, op_unscale))
+    return 0;
+  }
   TRAIN_DISPATCH_C(C, hipLaunchKernelGGL((add_mask_ln_kernel<CC>), dim3(row_blocks(T)), dim3(256), 0, st, x_in, y, mask, axis,
                                          F, J, w, b, eps, x_out, xn, amax, T, (f16*)op, Tp, op_unscale))
   return 0;
@@ -1168,10 +1187,15 @@ int d3dp_train_add_mask_ln(const float* x_in, const float* y, const float* mask,
 int d3dp_train_add_mask_ln2(const float* x_in, const float* y, const float* mask, int axis, int F, int J, const float* wa,
                             const float* ba, float eps_a, const float* pos, const float* wb, const float* bb, float eps_b,
                             float* x_out, float* x_next, float* xn, unsigned* amax, int T, int C, hipStream_t st, void* op, int Tp,
-                            float* op_unscale) {
+                            float* op_unscale, int op_hi) {
   if (!d3dp_width_instantiated(C))
     return op ? -2 : d3dp_train_g_add_mask_ln2(x_in, y, mask, axis, F, J, wa, ba, eps_a, pos, wb, bb, eps_b, x_out, x_next, xn, amax, T, C, st);
   if (!wa || !ba || !x_out || !x_next || (xn && !wb) || (wb && !bb) || (op && (C % 256 != 0 || Tp < T || !op_unscale || !wb))) return -1;
+  if (op && op_hi) {
+    TRAIN_DISPATCH_C256(C, hipLaunchKernelGGL((add_mask_ln2_kernel<CC, true>), dim3(row_blocks(T)), dim3(256), 0, st, x_in, y, mask, axis,
+                                              F, J, wa, ba, eps_a, pos, wb, bb, eps_b, x_out, x_next, xn, amax, T, (f16*)op, Tp, op_unscale))
+    return 0;
+  }
   TRAIN_DISPATCH_C(C, hipLaunchKernelGGL((add_mask_ln2_kernel<CC>), dim3(row_blocks(T)), dim3(256), 0, st, x_in, y, mask, axis,
                                          F, J, wa, ba, eps_a, pos, wb, bb, eps_b, x_out, x_next, xn, amax, T, (f16*)op, Tp, op_unscale))
   return 0;

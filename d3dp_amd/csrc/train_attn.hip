@@ -57,7 +57,9 @@ __device__ __forceinline__ void ta_block_amax(float am, unsigned* amax, float* p
 // forward
 // (NKC: key tiles per LDS chunk.  Round 6: the images hold 128 keys at a time -- the online softmax runs over key pairs anyway --
 //  so a 243-frame problem needs 64 KiB instead of 128 and TWO workgroups share a CU: four waves per SIMD instead of two)
-template <int NKT, int NW, int NKC, int HD, bool PAD = false, int PASSES = 3>
+// (OPHI, D3DP_TRAIN_ROWS=hi: the operand rows `op` are hi-only [Tp][C] -- the same hi value at column c, no lo value.  The forward
+//  kernels alone write operand rows; instantiated in train_attn_hi.hip for head dims 64 / 32 at both pass counts)
+template <int NKT, int NW, int NKC, int HD, bool PAD = false, int PASSES = 3, bool OPHI = false>
 __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                            TAStat* __restrict__ stats, SeqMap map, int C, int heads, int groups,
                                                            int n_work, const unsigned* __restrict__ amax_qkv,
@@ -81,8 +83,8 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
   // scale, amax_out[0] = the bound.
   if (!PAD && op) {                                    // (padded heads: no operand rows, the launcher refuses them)
     if (blockIdx.x == 0 && tid == 0) { op_unscale[0] = 1.0f / sq; if (amax_out) amax_out[0] = amax_qkv[0]; }
-    const size_t n8 = (size_t)(Tp - T) * C / 4;        // 16-byte pieces of the pad rows (2 C fp16 each)
-    uint4* z = reinterpret_cast<uint4*>(op + (size_t)T * 2 * C);
+    const size_t n8 = (size_t)(Tp - T) * C / (OPHI ? 8 : 4);   // 16-byte pieces of the pad rows (2 C fp16 each; OPHI: C)
+    uint4* z = reinterpret_cast<uint4*>(op + (size_t)T * (OPHI ? 1 : 2) * C);
     for (size_t i = (size_t)blockIdx.x * (NW * 64) + tid; i < n8; i += (size_t)gridDim.x * (NW * 64)) z[i] = make_uint4(0u, 0u, 0u, 0u);
   }
   for (int unit = blockIdx.x; unit < n_work; unit += gridDim.x) {
@@ -174,9 +176,13 @@ __global__ __launch_bounds__(NW * 64, 4) void tattn_fwd_kernel(const float* __re
           f16x4 hi, lo;
 #pragma unroll
           for (int e = 0; e < 4; ++e) { const f16 hh = (f16)y[e]; hi[e] = hh; lo[e] = (f16)(y[e] - (float)hh); }
-          f16* d = op + tok * 2 * C + h2i_col(head * HD + dn * 16 + fg * 4);
-          *reinterpret_cast<f16x4*>(d) = hi;
-          *reinterpret_cast<f16x4*>(d + kH2iLo) = lo;
+          if constexpr (OPHI) {
+            *reinterpret_cast<f16x4*>(op + tok * C + head * HD + dn * 16 + fg * 4) = hi;
+          } else {
+            f16* d = op + tok * 2 * C + h2i_col(head * HD + dn * 16 + fg * 4);
+            *reinterpret_cast<f16x4*>(d) = hi;
+            *reinterpret_cast<f16x4*>(d + kH2iLo) = lo;
+          }
         }
       }
       if (fg == 0) stats[(size_t)prob * n + q].L = mrun + __builtin_amdgcn_logf(lrun) - 10.0f;   // log2(sum exp2(s))
@@ -615,7 +621,7 @@ __global__ __launch_bounds__(128) void tattn_bwd_small_kernel(const float* __res
 }
 
 struct TAOperand { f16* op; int T, Tp; float* unscale; };   // forward only: the output also as the next Linear's operand rows
-template <int NKT, int HD, bool PAD = false, int PASSES = 3>
+template <int NKT, int HD, bool PAD = false, int PASSES = 3, bool OPHI = false>
 int ta_launch(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats, int n_seq,
               SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
               hipStream_t st, TAOperand po = {nullptr, 0, 0, nullptr}) {
@@ -642,6 +648,19 @@ int ta_launch(int which, const float* qkv, const float* o, const float* dout, fl
   constexpr int NPL = ta_planes(PASSES);               // planes per image; two images per kernel
   const size_t lds = (size_t)2 * NPL * NKC * 16 * ROWB + 64, lds_kv = (size_t)2 * NPL * NKC_KV * 16 * ROWB + NKC_KV * 16 * 8 + 64, lds_fwd = lds;
   (void)NK;
+  if constexpr (OPHI) {                                // the forward with hi-only operand rows: nothing else has such a form
+    static_assert(!PAD, "padded heads write no operand rows");
+    if (which != 0 || !po.op) return -1;
+    static PerDeviceOnce once_hi;
+    if (once_hi.get([&](int) {
+          return d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_fwd_kernel<NKT, NW, NKC, HD, false, PASSES, true>), 160 * 1024);
+        }) < 0) return -3;
+    const int tiles = (map.n_tok + 15) / 16, groups = (tiles + NW - 1) / NW;
+    const int n_work = n_seq * heads * groups;
+    hipLaunchKernelGGL((tattn_fwd_kernel<NKT, NW, NKC, HD, false, PASSES, true>), dim3(n_work < 2048 ? n_work : 2048), dim3(NW * 64), lds_fwd, st, qkv, out,
+                       reinterpret_cast<TAStat*>(stats), map, C, heads, groups, n_work, amax_qkv, amax_out, po.op, po.T, po.Tp, po.unscale);
+    return 0;
+  } else {
   static PerDeviceOnce once;
   if (once.get([&](int) {
         return d3dp_lds_opt_in(reinterpret_cast<const void*>(tattn_fwd_kernel<NKT, NW, NKC, HD, PAD, PASSES>), 160 * 1024) < 0 ? -3
@@ -672,17 +691,23 @@ int ta_launch(int which, const float* qkv, const float* o, const float* dout, fl
                          n_work, amax_qkv, amax_do, amax_out);
   }
   return 0;
+  }
 }
 
 // The padded forms are compiled in a translation unit of their own (train_attn_pad.hip includes this file with D3DP_TA_PAD_TU
 // defined): beside them in one module the compiler allocated registers differently in 15 of the 57 existing instantiations; apart,
 // every one of those keeps its device code instruction for instruction (profiles/train_widths.md).
 // The one-pass forms (PASSES = 1, head dims 64 / 32 / 16) likewise: train_attn_1p.hip includes this file with D3DP_TA_1P_TU defined.
-#ifdef D3DP_TA_PAD_TU
+// The forward kernels with hi-only operand rows (OPHI; head dims 64 / 32, both pass counts) likewise: train_attn_hi.hip, D3DP_TA_HI_TU.
+#ifdef D3DP_TA_HI_TU
+#define TA_CASE(NKT_, HD_)                                                                                                                      \
+  return passes == 1 ? ta_launch<NKT_, HD_, false, 1, true>(0, qkv, nullptr, nullptr, out, nullptr, stats, n_seq, map, C, heads, amax_qkv, nullptr, amax_out, st, po) \
+                     : ta_launch<NKT_, HD_, false, 3, true>(0, qkv, nullptr, nullptr, out, nullptr, stats, n_seq, map, C, heads, amax_qkv, nullptr, amax_out, st, po);
+#elif defined(D3DP_TA_PAD_TU)
 #define TA_CASE(NKT_, HD_) return ta_launch<NKT_, HD_, true>(which, qkv, o, dout, out, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st);
 #elif defined(D3DP_TA_1P_TU)
 #define TA_CASE(NKT_, HD_) return ta_launch<NKT_, HD_, false, 1>(which, qkv, o, dout, out, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st, po);
-#else
+#else  // (train_attn.hip itself)
 #define TA_CASE(NKT_, HD_) return ta_launch<NKT_, HD_>(which, qkv, o, dout, out, dqkv, stats, n_seq, map, C, heads, amax_qkv, amax_do, amax_out, st, po);
 #endif
 #define TA_LENGTHS(HD_)              \
@@ -693,14 +718,18 @@ int ta_launch(int which, const float* qkv, const float* o, const float* dout, fl
   if (n <= 512) { TA_CASE(32, HD_) } \
   TA_CASE(64, HD_)
 
-#if !defined(D3DP_TA_PAD_TU) && !defined(D3DP_TA_1P_TU)
+#if !defined(D3DP_TA_PAD_TU) && !defined(D3DP_TA_1P_TU) && !defined(D3DP_TA_HI_TU)
 int ta_dispatch(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats, int n_seq,
                 SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do, unsigned* amax_out,
-                hipStream_t st, int passes, TAOperand po = {nullptr, 0, 0, nullptr}) {
+                hipStream_t st, int passes, TAOperand po = {nullptr, 0, 0, nullptr}, int op_hi = 0) {
   const int n = map.n_tok;
   if (passes != 1 && passes != 3) return -1;
   if (heads < 1 || C % heads != 0 || C % 4 != 0 || n < 1 || n > 1024 || !amax_qkv || !stats) return -2;
   if (po.op && (po.Tp < po.T || !po.unscale || C % 32 != 0)) return -1;
+  if (po.op && op_hi) {                                // (the forward alone; head dims 64 / 32: plan_context lets no other through)
+    if (which != 0) return -1;
+    return d3dp_train_attn_x2_fwd_hi(passes, qkv, out, stats, n_seq, map, C, heads, amax_qkv, amax_out, st, po.op, po.T, po.Tp, po.unscale);
+  }
   if (passes == 1) {                                   // (head dims 64 / 32 / 16 alone: -2 for the padded ones too, plan_context refuses them)
     const int hd1 = C / heads;
     if (hd1 != 64 && hd1 != 32 && hd1 != 16) return -2;
@@ -722,7 +751,18 @@ int ta_dispatch(int which, const float* qkv, const float* o, const float* dout, 
 
 }  // namespace
 
-#ifdef D3DP_TA_PAD_TU
+#ifdef D3DP_TA_HI_TU
+// the forward with hi-only operand rows [Tp][C] (passes: 1 | 3; ta_dispatch has checked everything else); head dims 64 / 32, else -2
+int d3dp_train_attn_x2_fwd_hi(int passes, const float* qkv, float* out, void* stats, int n_seq, SeqMap map, int C, int heads,
+                              const unsigned* amax_qkv, unsigned* amax_out, hipStream_t st, void* op, int T, int Tp, float* op_unscale) {
+  const int n = map.n_tok, hd = heads > 0 ? C / heads : 0;
+  if (heads < 1 || hd * heads != C || n < 1 || n > 1024 || !amax_qkv || !stats || !op || (passes != 1 && passes != 3)) return -2;
+  const TAOperand po{(f16*)op, T, Tp, op_unscale};
+  if (hd == 64) { TA_LENGTHS(64) }
+  if (hd == 32) { TA_LENGTHS(32) }
+  return -2;
+}
+#elif defined(D3DP_TA_PAD_TU)
 // which: 0 = forward, 1 = both backward passes, 2 = pass Q alone, 3 = pass KV alone (ta_dispatch has checked everything else)
 int d3dp_train_attn_x2_padded(int which, const float* qkv, const float* o, const float* dout, float* out, float* dqkv, void* stats,
                               int n_seq, SeqMap map, int C, int heads, const unsigned* amax_qkv, const unsigned* amax_do,
@@ -763,12 +803,13 @@ static_assert(sizeof(TAStat) == D3DP_TRAIN_ATTN_X2_STAT_BYTES, "train_plan.h: d3
 // amax_qkv: absmax slot of the whole qkv tensor (the qkv Linear's epilogue); amax_out (optional): absmax slot of `out`
 // op (optional): the output also as split operand rows [Tp][2 C] (rows T .. Tp - 1 zero; T = all token rows of the batch) at the
 // scale of q / k / v, op_unscale[0] = 1 / scale, amax_out[0] = the bound (the qkv absmax) -- see tattn_fwd_kernel
+// (op_hi: the operand rows are hi-only [Tp][C], D3DP_TRAIN_ROWS=hi -- train_attn_hi.hip; head dims 64 / 32 alone, else -2)
 int d3dp_train_attn_x2_fwd(const float* qkv, float* out, void* stats, int n_seq, SeqMap map, int C, int heads,
                            const unsigned* amax_qkv, unsigned* amax_out, hipStream_t st, void* op, int T, int Tp,
-                           float* op_unscale, int passes) {
+                           float* op_unscale, int passes, int op_hi) {
   if (!qkv || !out) return -1;
   return ta_dispatch(0, qkv, nullptr, nullptr, out, nullptr, stats, n_seq, map, C, heads, amax_qkv, nullptr, amax_out, st, passes,
-                     TAOperand{(f16*)op, T, Tp, op_unscale});
+                     TAOperand{(f16*)op, T, Tp, op_unscale}, op_hi);
 }
 // dqkv [T, 3C] = the gradient of (q | k | v) given dout [T, C]; o: the forward output; amax_do: absmax slot of dout;
 // amax_out (optional): absmax slot of dqkv (both passes add to it)

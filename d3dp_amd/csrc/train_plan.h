@@ -14,13 +14,10 @@ constexpr int D3DP_DYPREP_ROWS = 96;        // partial rows of column sums d3dp_
 constexpr int D3DP_ROWPREP_ROWS = 512;      // ... at most, d3dp_launch_rowprep
 constexpr int D3DP_LN_BWD_BLOCKS = 512;     // workgroups of a LayerNorm-backward call: one [dgamma | dbeta] partial row each (train.hip)
 constexpr int D3DP_EMBED_BWD_ROWS = 64;     // partial tables of d3dp_train_embed_bwd
-constexpr int D3DP_WPREP_MAX = 64;          // weights d3dp_launch_wprep prepares in one call
 constexpr int D3DP_TN_MAX = 4;              // products of one d3dp_launch_linear_f16x2_tn_many launch
-constexpr int D3DP_TN_TILE_N = 256, D3DP_TN_TILE_K = 128;   // the tile of the product kernels (gemm_x2_tile.h XBM x XBN)
 constexpr size_t D3DP_TRAIN_ATTN_STAT_BYTES = 12;           // per query: train.hip AttnStats
 constexpr size_t D3DP_TRAIN_ATTN_X2_STAT_BYTES = 8;         // per query: train_attn.hip TAStat
-// the weight gradient dW[N, K] straight from the row forms of its two operands (gemm_f16x2_tn_kernel): whole tiles only
-inline bool d3dp_tn_applies(int N, int K) { return N % D3DP_TN_TILE_N == 0 && K % D3DP_TN_TILE_K == 0; }
+// (D3DP_WPREP_MAX, D3DP_TN_TILE_N / _K and d3dp_tn_applies: ctx_plan.h -- plan_context's step 7b asks them too)
 // partial rows one LayerNorm-backward call over T tokens leaves
 inline int d3dp_train_ln_bwd_blocks(int T) { return (T + 3) / 4 < D3DP_LN_BWD_BLOCKS ? (T + 3) / 4 : D3DP_LN_BWD_BLOCKS; }
 inline size_t d3dp_train_attn_stats_bytes(int n_seq, int n_tok, int heads) { return (size_t)n_seq * heads * n_tok * D3DP_TRAIN_ATTN_STAT_BYTES; }
@@ -199,6 +196,9 @@ struct TrainPlan {
   // D3DP_TRAIN_ATTN_PASSES (CtxPlan::train_attn_passes): the fp16-MFMA passes per product of every attention that runs on
   // train_attn.hip (path.attn_x2); 1 = its one-pass kernels (train_attn_1p.hip).  The fp32 attention of an axis does not read it.
   int attn_passes;
+  // D3DP_TRAIN_ROWS=hi (CtxPlan::train_rows_hi): every operand row of X2Train's Linears is K plain fp16 values (half the stride of the
+  // split rows; train_layout's regions are unchanged and half used) and the products run the whole-line one-pass kernels
+  bool rows_hi;
   // D3DP_TRAIN_LONG_ATTN=chunked (CtxPlan::train_long_attn): an axis on the fp32 attention runs the chunked VALU backward of train.hip
   // wherever the whole-sequence VALU pair ran or refused, so the forward pass takes clips beyond 256 frames there too
   bool attn_bwd_chunked;
@@ -244,6 +244,7 @@ inline TrainPlan plan_train_step(const CtxPlan& c, const d3dp_cfg& g, int B, int
   P.T = T; P.passes = c.train_passes; P.overlap_sets = c.train_overlap_sets;
   P.attn_passes = c.train_attn_passes;
   P.attn_bwd_chunked = c.train_long_attn;
+  P.rows_hi = c.train_rows_hi && P.path.use_x2;
   const int shape[4][2] = {{3 * C, C}, {C, C}, {Hd, C}, {C, Hd}};       // [N, K] by TrainLinearId
   for (int j = 0; j < 4; ++j) { P.lin[j].N = shape[j][0]; P.lin[j].K = shape[j][1]; }
   if (!P.use_x2) return P;                                              // (the fp32 path: four plain products per block, nothing to route)

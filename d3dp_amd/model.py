@@ -541,7 +541,23 @@ class MixSTE2(nn.Module):
                      "-- S, O, dP, dQ, dK, dV -- as one fp16-MFMA pass from one-plane LDS images (q, k, v at the qkv scale, dO at its "
                      "own, P x 2^10 and dS at its running power of two each rounded once to fp16; fp32 accumulate, softmax "
                      "denominator, L and D in fp32)")
+        # D3DP_TRAIN_ROWS=hi (ctx_plan.h plan_context, step 7b): named behind the unchanged text where a context takes it
+        if os.environ.get("D3DP_TRAIN_ROWS") == "hi" and self._train_rows_hi():
+            text += ("; D3DP_TRAIN_ROWS=hi: every operand of the one-pass Linears -- activations, both forms of the weights, every dY -- "
+                     "stored as plain fp16 rows (the hi value alone, half the row stride) and read by the products in whole 128-byte "
+                     "lines of 64 columns: the same values in the same MFMAs in the same order, bit-equal to D3DP_TRAIN_PASSES=1")
         return text
+
+    def _train_rows_hi(self) -> bool:
+        """Whether a context of this shape under the environment's other switches takes D3DP_TRAIN_ROWS=hi (plan_context step 7b
+        refuses every other): the one-pass Linears at `-cs` 256 / 512 with a hidden width that is a multiple of 256, depth <= 8."""
+        C, Hd, hd = self.embed_dim, self.hidden, self.embed_dim // self.num_heads
+        env = os.environ.get
+        superseded = (env("D3DP_TRAIN_WGRAD") == "each" or env("D3DP_TRAIN_TAIL") == "split" or env("D3DP_TRAIN_GELU") == "pass"
+                      or env("D3DP_TRAIN_LN_OPERAND") == "pass")
+        return (C in (256, 512) and hd in (8, 16, 32, 64) and Hd >= 256 and Hd % 256 == 0 and self.block_depth <= 8
+                and env("D3DP_TRAIN_PASSES") == "1" and env("D3DP_TRAIN_IMPL") != "f32" and not superseded
+                and not (hd == 16 and env("D3DP_TRAIN_ATTN", "") != "f32"))
 
     def _train_attn_one_pass_axes(self) -> str:
         """Which attention D3DP_TRAIN_ATTN_PASSES=1 applies to in a context of this shape under the environment's other switches

@@ -254,6 +254,20 @@ D3DP_API const char* d3dp_last_error(void);
  *                         beside D3DP_TRAIN_ATTN=f32, and at head dims 24 / 40 / 48 / 56 under D3DP_TRAIN_IMPL=f16x2 (the padded
  *                         kernels have no one-pass form).  D3DP_TRAIN_PASSES, D3DP_TRAIN_OVERLAP, D3DP_TRAIN_LONG_ATTN and
  *                         D3DP_TRAIN_ATTN_BWD compose with it.  Contexts of the other modes do not read it.
+ *   D3DP_TRAIN_ROWS=hi in the environment of d3dp_create (OPT-IN; read for D3DP_MODE_TRAIN contexts alone; unset or =split: every
+ *                         context plans, refuses and launches as in the lines above, bit for bit): beside D3DP_TRAIN_PASSES=1 every
+ *                         operand of the training Linears -- activations, both forms of the weights, every dY -- is stored as plain
+ *                         fp16 rows (the hi value alone: column c at offset c, half the row stride, the workspace regions unchanged
+ *                         and half used) and the one-pass products read whole 128-byte lines of 64 columns.  The same values reach
+ *                         the same MFMAs in the same order and the partial sums group the same k-steps: predictions and gradients
+ *                         are BIT-EQUAL to D3DP_TRAIN_PASSES=1 alone; launches, streams, slots and the workspace size are unchanged.
+ *                         The route exists where no operand of the step is transposed and every producer writes rows itself:
+ *                         channels 256 or 512, hidden a multiple of 256, depth <= 8.  D3DP_ENOTSUP, decided before the device is
+ *                         looked for and naming the switch: any other value; =hi without D3DP_TRAIN_PASSES=1, on the fp32 path, at
+ *                         channels 64 / 128, at the padded widths of D3DP_TRAIN_IMPL=f16x2, at depth > 8, at head dim 16 unless
+ *                         D3DP_TRAIN_ATTN=f32, and beside the variants-only launch forms.  D3DP_TRAIN_ATTN_PASSES, D3DP_TRAIN_ATTN,
+ *                         D3DP_TRAIN_ATTN_BWD, D3DP_TRAIN_OVERLAP and D3DP_TRAIN_LONG_ATTN compose with it.  Contexts of the other
+ *                         modes do not read it.
  *   D3DP_TRAIN_LONG_ATTN=chunked in the environment of d3dp_create (OPT-IN; read for D3DP_MODE_TRAIN contexts alone; unset: every
  *                         context plans, refuses and launches as in the lines above, bit for bit): every fp32 attention backward
  *                         of the step that runs on the VALU kernels -- head dim 8, a width on the fp32 path, the cross-check
@@ -558,7 +572,8 @@ D3DP_API const char* d3dp_profile_class_name(int32_t cls);
  * d3dp_debug_train_linear: the training step's split-fp16 Linear alone, out[M, N] = A[M, K] W[N, K]^T + bias on fp32 device
  *   operands -- absmax, operand split and gemm_f16x2_dyn_kernel exactly as d3dp_train_forward launches them.  tail: 0 = the rows
  *   behind the last whole 256-row tile as one more row of tiles, 1 = as 16 x 64 blocks inside the same launch; tail | 16: the one-pass instantiation
- *   of the kernel (what D3DP_TRAIN_PASSES=1 launches); any other bit: D3DP_EINVAL; amax_out:
+ *   of the kernel (what D3DP_TRAIN_PASSES=1 launches); tail | 16 | 32: that product on hi-only operand rows (what D3DP_TRAIN_ROWS=hi
+ *   launches; K % 64 == 0, else D3DP_EINVAL naming K); 32 without 16 and any other bit: D3DP_EINVAL; amax_out:
  *   optional pre-zeroed device word receiving the output's absmax (amax_pos = 1: its largest positive value).  Allocates its
  *   operand buffers and synchronises `stream`. */
 D3DP_API int d3dp_debug_x2_variants(void);
