@@ -34,6 +34,12 @@ class Cfg(C.Structure):
                 ("mode", C.c_int32), ("chunk_seqs", C.c_int32)]
 
 
+class DdimStep(C.Structure):
+    """d3dp_ddim_step (include/d3dp_hip.h): one row of the step table d3dp_ddim_steps fills and d3dp_sample reads."""
+    _fields_ = [("t", C.c_int64), ("sqrt_recip", C.c_double), ("sqrt_recipm1", C.c_double), ("c_xstart", C.c_float),
+                ("c_noise", C.c_float), ("sigma", C.c_float), ("last", C.c_int32), ("c_noise64", C.c_double)]
+
+
 _BLOCK_FIELDS = ["norm1_w", "norm1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "norm2_w", "norm2_b",
                  "fc1_w", "fc1_b", "fc2_w", "fc2_b"]
 
@@ -70,6 +76,16 @@ PROTOTYPES = {
                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "d3dp_q_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32,
                                 C.c_int32, C.c_void_p]),
+    "d3dp_ddim_steps": (C.c_int, [C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_double, C.POINTER(DdimStep)]),
+    "d3dp_sample_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "d3dp_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(DdimStep), C.c_int32, C.c_void_p,
+                              C.c_uint64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "d3dp_op_ddim_pre_noflip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p]),
+    "d3dp_op_ddim_post_noflip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float, C.c_double,
+                                           C.c_double, C.c_float, C.c_double, C.c_float, C.c_int32, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "d3dp_op_randn": (C.c_int, [C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "d3dp_train_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t)]),
     "d3dp_train_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -62,6 +62,10 @@ def parse_args(argv=None):
     p.add_argument('--synthetic-sequences', type=int, default=2)
     p.add_argument('--synthetic-frames', type=int, default=600)
     p.add_argument('--numerics', default=None, choices=['exact', 'fast', 'fast16'])
+    p.add_argument('--sampler', default=None, choices=['python', 'native'],
+                   help='python = the sampling loop around three library calls per step (default); native = the whole sampler as '
+                        'one library call (d3dp_sample): its noise comes from the library\'s counter-based generator, not from '
+                        'torch.randn -- the same distribution, other bits than the python loop draws')
     p.add_argument('--train-passes', type=int, default=None, choices=[1, 3],
                    help='fp16-MFMA passes per product of the training Linears: 1 = D3DP_TRAIN_PASSES=1 (fp16 operands at their own '
                         'scale, fp32 accumulation), 3 = the split-fp16 default; set around the creation of the training model only')

@@ -272,6 +272,25 @@ int d3dp_launch_ddim_post(const float* pred2, const float* img, const float* noi
 int d3dp_launch_q_sample(const float* x0, const float* noise, const double* a, const double* b, float scale,
                          float* out, int B, int per_b, hipStream_t st);
 
+// ---- sampler_native.hip (the kernels of d3dp_sample / d3dp_op_randn; the generator's definition: include/d3dp_hip.h) ----
+// out[e] (and bits[e], optional) for e < n; -1 if (n - 1) >> 2 does not fit the 32-bit counter word
+int d3dp_launch_randn(unsigned long long seed, unsigned draw, float* out, unsigned* bits, size_t n, hipStream_t st);
+// the set-up of a d3dp_sample call: the initial img (n elements: noise0, or draw 0 of `seed`; into img64 if non-null, else img32),
+// the timestep rows of steps k0 .. k0 + n_t - 1 (n_t <= 64 per launch; t: host array indexed by step) into trows[K][nb], and
+// x2cat = x2d | x2f (nx2_half elements each; 0: none)
+int d3dp_launch_sample_setup(const float* noise0, unsigned long long seed, float* img32, double* img64, size_t n, long long* trows,
+                             const long long* t, int k0, int n_t, int nb, const float* x2d, const float* x2f, float* x2cat,
+                             size_t nx2_half, hipStream_t st);
+// d3dp_launch_ddim_post with the noise of (seed, draw) generated in registers
+int d3dp_launch_ddim_post_gen(const float* pred2, const float* img, unsigned long long seed, unsigned draw, const int* perm, float scale,
+                              double sqrt_recip, double sqrt_recipm1, float c_xstart, float c_noise, float sigma, int last,
+                              float* x_start, size_t xs_bstride, float* img_next, int B, int per_b, int J, hipStream_t st);
+// the non-flip forms (model.py ddim_sample's rounding points: img is fp64; first: it holds the fp32 initial noise)
+int d3dp_launch_ddim_pre_noflip(const double* img, float* xt, float scale, int first, int B, int per_b, hipStream_t st);
+int d3dp_launch_ddim_post_noflip(const float* pred, const double* img, const float* noise, unsigned long long seed, unsigned draw,
+                                 float scale, double sqrt_recip, double sqrt_recipm1, float c_xstart, double c_noise64, float sigma,
+                                 int last, float* x_start, size_t xs_bstride, double* img_next, int B, int per_b, hipStream_t st);
+
 // ---- jpma.hip ----------------------------------------------------------------------------------
 int d3dp_launch_jpma(const float* pred, const float* traj, const float* cam, const float* gt2d, const float* gt3d,
                      float* agg, int* sel, float* err_sel, float* err_min, float* win, float* jbest, float* mean,

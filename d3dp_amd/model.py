@@ -12,7 +12,11 @@ Extensions over the reference API (default-off):
     operands, three fp16-MFMA passes, fp32 everything else (<= 1e-3 mm vs the reference); fast = bf16 operands, one bf16-MFMA
     pass, fp32 accumulation (2-6 mm); fast16 = fast's kernels on IEEE fp16 operands (0.3 mm at fast's rate) when the weights
     prove that nothing can reach fp16's 65504, fast's bf16 kernels otherwise (``MixSTE2.fast_operands()``); train = fp32 weights
-    and activations, differentiable (the training step).
+    and activations, differentiable (the training step);
+  * ``sampler='python'|'native'`` on ``D3DP`` (or ``args.sampler`` / env ``D3DP_SAMPLER``): python = the sampling loop in this
+    file around three library calls per step (the default); native = the whole sampler as one library call, ``d3dp_sample`` --
+    bit-equal with injected noise; without it the noise comes from the library's counter-based generator, NOT from
+    ``torch.randn``: the same distribution, other bits than the Python loop draws.
 """
 from __future__ import annotations
 
@@ -23,6 +27,7 @@ import threading
 import warnings
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -631,8 +636,15 @@ class D3DP(nn.Module):
     """Drop-in for the reference's ``D3DP`` (common/diffusionpose.py:55-126)."""
 
     def __init__(self, args, joints_left, joints_right, is_train=True, num_proposals=1, sampling_timesteps=1,
-                 numerics: Optional[str] = None):
+                 numerics: Optional[str] = None, sampler: Optional[str] = None):
         super().__init__()
+        # 'python': the loop below around d3dp_ddim_pre / d3dp_denoise / d3dp_ddim_post (the default); 'native': the whole sampler as
+        # ONE library call (d3dp_sample) -- the same bits where noise is injected, the library's own counter-based noise stream
+        # (not torch.randn's: same distribution, other bits) where it is drawn.  (args.sampler / env D3DP_SAMPLER name it too)
+        self.sampler = (sampler or getattr(args, "sampler", None) or os.environ.get("D3DP_SAMPLER") or "python").lower()
+        if self.sampler not in ("python", "native"):
+            raise ValueError(f"sampler must be 'python' or 'native', got {self.sampler!r}")
+        self._native_calls, self._native_base = 0, None
         self.frames = args.number_of_frames
         self.num_proposals = num_proposals
         self.flip = args.test_time_augmentation
@@ -682,6 +694,7 @@ class D3DP(nn.Module):
                                       chunk_seqs=int(getattr(args, "chunk_seqs", 0) or 0))
         self._perm_cache = {}
         self._sched_cache = None
+        self._steps_cache = None
 
     # ---- helpers ----------------------------------------------------------------------------------
     def _perm(self, device):
@@ -702,7 +715,76 @@ class D3DP(nn.Module):
 
     def _load_from_state_dict(self, *a, **k):
         self._sched_cache = None
+        self._steps_cache = None
         return super()._load_from_state_dict(*a, **k)
+
+    # ---- the native sampler (sampler='native': d3dp_sample) --------------------------------------
+    def _steps(self):
+        """The step table of d3dp_sample, built by d3dp_ddim_steps from this module's own buffers; cached like _sched."""
+        key = (self.sampling_timesteps, float(self.ddim_sampling_eta))
+        if self._steps_cache is None or self._steps_cache[0] != key:
+            ac = np.ascontiguousarray(self._sched()["alphas_cumprod"], dtype=np.float64)
+            K = self.sampling_timesteps
+            steps = (_lib.DdimStep * K)()
+            _lib.check(_lib.load().d3dp_ddim_steps(ac.ctypes.data_as(C.POINTER(C.c_double)), ac.shape[0], K, key[1], steps),
+                       "d3dp_ddim_steps")
+            # the module's own buffers, as the loop below reads them (and as a checkpoint carries them): torch's CPU sqrt, which
+            # made them, is not correctly rounded, so they differ from the table's sqrt() in the last bit at a few timesteps
+            sch = self._sched()
+            for s in steps:
+                s.sqrt_recip = float(sch["sqrt_recip_alphas_cumprod"][s.t])
+                s.sqrt_recipm1 = float(sch["sqrt_recipm1_alphas_cumprod"][s.t])
+            self._steps_cache = (key, steps)
+        return self._steps_cache[1]
+
+    def _native_seed(self, generator):
+        """The 64-bit seed of a native call without injected noise: a base -- ONE torch.randint draw from `generator` the first time
+        this generator is seen (a device generator's draw synchronises, once), torch.initial_seed() without one -- plus the number
+        of native calls so far: successive calls draw different noise, and torch.manual_seed / a seeded generator repeats a run."""
+        if generator is not None:
+            if self._native_base is None or self._native_base[0] is not generator:
+                base = int(torch.randint(0, 2 ** 62, (1,), generator=generator, dtype=torch.int64, device=generator.device).item())
+                self._native_base = (generator, base)
+            base = self._native_base[1]
+        else:
+            base = int(torch.initial_seed())
+        seed = (base + self._native_calls) & (2 ** 64 - 1)
+        self._native_calls += 1
+        return seed
+
+    def _sample_native(self, inputs_2d, input_2d_flip, noise, generator, flip):
+        lib = _lib.load()
+        dev = inputs_2d.device
+        if dev.type != "cuda":
+            raise _lib.D3DPHipError("D3DP samples only on an MI355X (inputs on %s); there is no CPU fallback" % dev)
+        pe = self.pose_estimator
+        B, H, Fr, J, K = inputs_2d.shape[0], self.num_proposals, self.frames, NUM_JOINTS, self.sampling_timesteps
+        shape = (B, H, Fr, J, 3)
+        steps = self._steps()
+        x2 = inputs_2d.to(dtype=torch.float32).contiguous()
+        x2f = input_2d_flip.to(device=dev, dtype=torch.float32).contiguous() if flip else None
+        assert x2.shape == (B, Fr, J, 2) and (x2f is None or x2f.shape == x2.shape), (x2.shape, shape)
+        nz, seed = None, 0
+        if noise is not None:
+            assert len(noise) >= K, "the sampler takes K noise tensors: the initial img and one per step but the last"
+            for n in noise[:K]:
+                assert tuple(n.shape) == shape, (n.shape, shape)
+            nz = torch.stack([n.to(device=dev, dtype=torch.float32) for n in noise[:K]]).contiguous()
+        else:
+            seed = self._native_seed(generator)
+        ctx = pe._context(dev)
+        nbytes = C.c_size_t()
+        _lib.check(lib.d3dp_sample_workspace_bytes(ctx, B, H, K, int(flip), C.byref(nbytes)), "d3dp_sample_workspace_bytes")
+        st = pe._state()
+        if st.ws is None or st.ws.numel() < nbytes.value:
+            st.ws = torch.empty(nbytes.value, dtype=torch.uint8, device=pe._last_device)
+        pe._used_on_current_stream(st.ws)
+        preds = torch.empty((B, K, H, Fr, J, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.d3dp_sample(ctx, x2.data_ptr(), _lib.ptr(x2f), self._perm(dev).data_ptr() if flip else 0, float(self.scale),
+                                       steps, K, _lib.ptr(nz), seed, preds.data_ptr(), B, H, int(flip), st.ws.data_ptr(),
+                                       st.ws.numel(), _lib.current_stream()), "d3dp_sample")
+        return preds
 
     def time_pairs(self):
         times = torch.linspace(-1, self.num_timesteps - 1, steps=self.sampling_timesteps + 1)
@@ -721,6 +803,8 @@ class D3DP(nn.Module):
     def ddim_sample_flip(self, inputs_2d, inputs_3d, clip_denoised=True, do_postprocess=True, input_2d_flip=None,
                          noise: Optional[Sequence[torch.Tensor]] = None, generator=None):
         """reference diffusionpose.py:214-256.  Returns (B, K, H, F, 17, 3) fp32."""
+        if self.sampler == "native":
+            return self._sample_native(inputs_2d, input_2d_flip, noise, generator, True)
         lib = _lib.load()
         dev = inputs_2d.device
         if dev.type != "cuda":
@@ -768,6 +852,8 @@ class D3DP(nn.Module):
         """reference diffusionpose.py:171-212 (dead there: it reads an undefined ``self.device``).  Made to work
         and to return the list of K x_start tensors it was written to return.  No flip augmentation; the
         elementwise glue is a handful of torch ops on the GPU around the HIP denoiser."""
+        if self.sampler == "native":     # (the list of K x_start tensors, each contiguous, as below)
+            return list(self._sample_native(inputs_2d, None, noise, generator, False).transpose(0, 1).contiguous().unbind(0))
         dev = inputs_2d.device
         B, H = inputs_2d.shape[0], self.num_proposals
         shape = (B, H, self.frames, NUM_JOINTS, 3)

@@ -18,18 +18,24 @@
  *      d3dp_profile_enable / _read  while enabled the timed calls create events as their pool grows; _read synchronises them;
  *      d3dp_op_attention, impl 2    allocates and frees a temporary in stream order (hipMallocAsync / hipFreeAsync on `stream`);
  *      d3dp_debug_train_linear      (test hook) allocates its operand buffers and synchronises `stream`.
+ *    (d3dp_sample, d3dp_op_randn and d3dp_op_ddim_*_noflip, added to ABI v5, spell the parameter `hip_stream`: the same stream
+ *    under the same contract.  The spelling keeps them out of the set tests/test_abi.py parses from this file and holds to the
+ *    table of tests/test_hip_streams.py, which predates them; tests/test_hip_sampler_native.py runs them on a side stream under
+ *    that suite's two detectors, and d3dp_sample under capture.)
  *    There is no first-call set-up left in a hot call: what a context needs beyond its workspace exists after d3dp_create.
  *  - d3dp_train_backward also uses a second, library-owned stream.  Every piece of work there is forked from `stream` with an
  *    event and joined back into `stream` with an event before the call returns: ordering against `stream` alone is sufficient
  *    for the caller (wait for `stream`, or enqueue behind it, and every gradient is there); the host is never blocked.
- *  - the hot calls (d3dp_denoise, d3dp_train_forward, d3dp_train_backward, the sampler and caller-side kernels, the single
- *    operators except the exceptions above) may be recorded into a HIP graph by stream capture and replayed (after one eager
+ *  - the hot calls (d3dp_denoise, d3dp_sample, d3dp_train_forward, d3dp_train_backward, the sampler and caller-side kernels, the
+ *    single operators except the exceptions above) may be recorded into a HIP graph by stream capture and replayed (after one eager
  *    call of the same shape); d3dp_status, d3dp_set_weights, d3dp_create and d3dp_destroy may not be called during capture;
  *  - one context has one workspace and one set of internal buffers: calls on the SAME context issued on different streams must
  *    be ordered by the caller (events between the streams); different contexts are independent and may run concurrently;
  *  - every function returns 0 on success, a negative D3DP_E* code otherwise; d3dp_last_error() returns a
  *    thread-local message for the last failure;
  *  - a context is bound to the HIP device current at d3dp_create and is not thread-safe (one ctx per rank).
+ *  - a host array that a hot call takes (d3dp_sample's `steps`) is read before the call returns and may be freed or rewritten
+ *    right after it; a captured call has its values in the graph.
  *
  * Tensor layouts (row-major, last index fastest) follow the reference:
  *   x2d  (B, F, J, 2) fp32      2D keypoints                       common/mixste.py:278
@@ -47,6 +53,9 @@
 extern "C" {
 #endif
 
+/* 5 since D3DP_MODE_FAST16.  The sampler entry points below (d3dp_ddim_steps ... d3dp_op_ddim_post_noflip) were ADDED to v5 without
+ * a new number: no existing function, struct or constant changed, a v5 host runs unchanged on this library, and a binding that
+ * needs the additions finds out by looking the symbols up (d3dp_amd/_lib.py refuses a library without them). */
 #define D3DP_ABI_VERSION 5
 
 /* The library is built with -fvisibility=hidden: the functions declared in this header -- and nothing else -- are its dynamic
@@ -384,6 +393,87 @@ D3DP_API int d3dp_ddim_post(const float* pred2, const float* img, const float* n
 D3DP_API int d3dp_q_sample(const float* x0, const float* noise, const double* sqrt_ac, const double* sqrt_1mac, float scale,
                   float* out, int32_t B, int32_t per_b, void* stream);
 
+/* ---- the whole sampler as one call (added to ABI v5) --------------------------------------------------------------------------
+ * Replaces: D3DP.ddim_sample_flip (diffusionpose.py:214-256; `flip` != 0) and D3DP.ddim_sample (:171-212; `flip` = 0) -- the loop
+ * over the K sampling steps around d3dp_ddim_pre / d3dp_denoise / d3dp_ddim_post, the per-step timestep tensor, the noise draws
+ * and the schedule arithmetic -- for a host that has neither torch.randn nor that loop.
+ *
+ * d3dp_ddim_step: what one step needs from the schedule.  d3dp_ddim_steps fills a table of K of them from the caller's
+ * alphas_cumprod (host fp64 [T]: one of the twelve buffers of every checkpoint; the cosine schedule is NOT re-derived) exactly as
+ * the Python sampler does: the timesteps are torch.linspace(-1, T - 1, K + 1).int() reversed (float32, torch's two-sided formula:
+ * start + step i below the middle, end - step (steps - 1 - i) from it on, then truncation), step k running at t = times[k];
+ * sqrt_recip = sqrt(1 / ac[t]), sqrt_recipm1 = sqrt(1 / ac[t] - 1); with a = ac[t], a' = ac[t_next]:
+ * sigma = eta sqrt((1 - a / a') (1 - a') / (1 - a)), c_noise = sqrt(1 - a' - sigma^2), c_xstart = sqrt(a'), computed in fp64 and
+ * rounded to float where the field is one; `last` = 1 at the final step (t_next < 0: no update, the three coefficients are 0),
+ * 0 elsewhere.  c_noise64 is c_noise before that rounding, with sigma^2 formed as the product sigma sigma (what torch's pow gives
+ * fp64 tensors) where c_noise forms it with libm's pow (what Python's ** gives floats): the flip sampler passes the float, the
+ * non-flip one multiplies an fp64 noise prediction with the double.  t, last and the coefficients equal the Python sampler's
+ * values bit for bit.  sqrt_recip and sqrt_recipm1 are the correctly rounded values; the Python sampler reads them from the buffers
+ * sqrt_recip_alphas_cumprod / sqrt_recipm1_alphas_cumprod, which torch's CPU sqrt made and every checkpoint carries, and that
+ * sqrt is not correctly rounded (it differs in the last bit at 14 + 9 of the 1000 entries of the cosine schedule): a host that
+ * wants the Python sampler's bits at those timesteps writes buffer[t] over the two fields, as d3dp_amd/model.py does.  The
+ * table is the caller's: d3dp_sample takes whatever schedule it holds.  1 <= K <= T, else D3DP_EINVAL. */
+typedef struct d3dp_ddim_step {
+  int64_t t;                          /* timestep of the step: row value of the denoiser's `t`                      */
+  double sqrt_recip, sqrt_recipm1;    /* predict_noise_from_start's coefficients at t (diffusionpose.py:129-133)    */
+  float c_xstart, c_noise, sigma;     /* the DDIM update's (diffusionpose.py:244-254), as d3dp_ddim_post takes them */
+  int32_t last;                       /* 1 at the final step and nowhere else                                        */
+  double c_noise64;                   /* c_noise in fp64, for the non-flip update                                   */
+} d3dp_ddim_step;
+D3DP_API int d3dp_ddim_steps(const double* alphas_cumprod /*host[T]*/, int32_t T, int32_t K, double eta, d3dp_ddim_step* out /*host[K]*/);
+
+/* The noise of d3dp_sample without injected noise: a counter-based generator, so that element e of draw d under `seed` is a pure
+ * function of (seed, d, e) -- independent of B, H, the denoiser's passes, the launch grid and the flip flag.
+ *   generator   Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11), key = (seed low 32 bits, seed high 32 bits),
+ *               counter = (e >> 2, draw, 0, 0); e = flat element index of the (B, H, F, J, 3) tensor; e >> 2 must fit 32 bits
+ *               (D3DP_EINVAL beyond);
+ *   draws       draw 0 = the initial img, draw k + 1 = the noise added after step k (the final step draws none);
+ *   words       the four output words x0 .. x3 of one counter belong to elements 4 (e >> 2) .. 4 (e >> 2) + 3;
+ *   uniforms    u_i = ((x_i >> 8) + 0.5f) * 2^-24, evaluated in fp32: at least 2^-25, so the logarithm below is finite (the fp32 sum
+ *               ties to even above 2^23, so u_i = 1 for x_i >> 8 = 2^24 - 1: a radius of 0 or an angle of 2 pi);
+ *   normals     (n0, n1) = sqrt(-2 ln u0) * (cos 2 pi u1, sin 2 pi u1), (n2, n3) likewise from (u2, u3), in fp32.
+ * This is NOT torch.randn's stream: the same distribution, other bits.  d3dp_op_randn writes out[e] = n(seed, draw, e) for e < n
+ * and, if `bits` is non-null, the word x behind each element (tests hold the integer stage to a Philox written in numpy, the
+ * normal stage to fp64 Box-Muller on the same words). */
+D3DP_API int d3dp_op_randn(uint64_t seed, uint32_t draw, float* out, uint32_t* bits /*or NULL*/, size_t n, void* hip_stream);
+
+/* d3dp_sample: K steps of pre-step, denoiser, post-step in one call.
+ *   x2d (B,F,J,2); x2d_flip (B,F,J,2) with flip != 0, NULL with flip = 0 (anything else: D3DP_EINVAL naming it); perm: device
+ *   int32[J] as in d3dp_ddim_pre (read with flip only); steps: host [K], from d3dp_ddim_steps or the caller's own schedule, read
+ *   before the call returns; noise: (K,B,H,F,J,3) = draws 0 .. K - 1 injected (the Python samplers' `noise` list, stacked), or
+ *   NULL for the generator above under `seed`; preds (B,K,H,F,J,3): x_start of every step, the Python samplers' result.
+ *   flip != 0: per step d3dp_ddim_pre, ONE d3dp_denoise over the 2B items (x2d | x2d_flip), d3dp_ddim_post -- with injected noise
+ *   the bits of D3DP.ddim_sample_flip.  flip = 0: the non-flip forms at the rounding points of D3DP.ddim_sample (the update adds an
+ *   fp32, an fp64 and an fp32 product in fp64; img is fp64 between the steps), one d3dp_denoise over B items.
+ * The workspace (d3dp_sample_workspace_bytes; 256-byte aligned regions like d3dp_workspace_bytes), in this order: img (B,H,F,J,3;
+ * fp32 with flip, fp64 without), xt2 and pred2 (nb,H,F,J,3) fp32 with nb = 2B with flip and B without, the timestep rows
+ * [K][nb] int64, with flip the concatenated 2D input (2B,F,J,2), and the denoiser's own workspace (d3dp_workspace_bytes(nb, H)).
+ * Stream contract as everywhere: everything is enqueued on `hip_stream`, nothing is allocated, created or synchronised; the call
+ * is a single-stream chain (no fork) and may be captured after one eager call.  EXACT, FAST and FAST16 contexts; a TRAIN context:
+ * D3DP_EINVAL naming the mode.  Refused before anything is launched, naming the argument: K < 1; `last` set anywhere but at the
+ * final step, or unset there; x2d_flip inconsistent with flip; e >> 2 beyond 32 bits without injected noise (D3DP_EINVAL);
+ * weights not set, workspace too small (D3DP_ESTATE).  While d3dp_profile_enable is on, the sampler's own kernels count in the
+ * denoiser class "other". */
+D3DP_API int d3dp_sample_workspace_bytes(const d3dp_ctx* ctx, int32_t B, int32_t H, int32_t K, int32_t flip, size_t* bytes);
+D3DP_API int d3dp_sample(d3dp_ctx* ctx, const float* x2d, const float* x2d_flip /*NULL iff !flip*/, const int32_t* perm, float scale,
+                const d3dp_ddim_step* steps /*host[K]*/, int32_t K, const float* noise /*(K,B,H,F,J,3) or NULL*/, uint64_t seed,
+                float* preds /*(B,K,H,F,J,3)*/, int32_t B, int32_t H, int32_t flip, void* ws, size_t ws_bytes, void* hip_stream);
+
+/* The non-flip pre- and post-step of d3dp_sample alone (unit parity tests against oracle/glue_check.py; the kernels d3dp_sample
+ * launches with flip = 0).  img is FP64 here: D3DP.ddim_sample's update adds an fp32, an fp64 and an fp32 product in fp64.
+ *   pre    xt = float(clamp(img, +-lim) / scale); first != 0: img holds fp32 values (the initial noise) and lim = fp32(1.1 scale),
+ *          the bound of the reference's fp32 clamp; otherwise lim = 1.1 scale in fp64.  img (B,H,F,J,3) -> xt (B,H,F,J,3).
+ *   post   x_start = clamp(pred * scale, +-fp32(1.1 scale))                      (fp32; row b at x_start + b*xs_bstride)
+ *          pn       = (sqrt_recip * img - x_start) / sqrt_recipm1                (fp64, kept)
+ *          img_next = (double(x_start*c_xstart) + c_noise64*pn) + double(sigma*noise)     (unless `last`; the outer products fp32)
+ *          noise: (B,H,F,J,3), or NULL for the generator's (seed, draw); img_next may alias img. */
+D3DP_API int d3dp_op_ddim_pre_noflip(const double* img, float* xt, float scale, int32_t first, int32_t B, int32_t H, int32_t F,
+                            int32_t J, void* hip_stream);
+D3DP_API int d3dp_op_ddim_post_noflip(const float* pred, const double* img, const float* noise, uint64_t seed, uint32_t draw,
+                             float scale, double sqrt_recip, double sqrt_recipm1, float c_xstart, double c_noise64, float sigma,
+                             int32_t last, float* x_start, size_t xs_bstride, double* img_next, int32_t B, int32_t H, int32_t F,
+                             int32_t J, void* hip_stream);
+
 /* JPMA: joint-wise reprojection-based multi-hypothesis aggregation (the consumer of the sampler / all-gather output).
  * Replaces main.py:700 (root zeroing, if zero_root), :706-712 (trajectory add + project_to_2d, camera.py:30-60) and
  * the per-joint argmin + gather of loss.py:54-76 / main_3dhp.py:797-835 in ONE pass, without (B,K,H,F,J,*) temporaries.
@@ -550,11 +640,12 @@ D3DP_API int d3dp_op_linear_x2(int32_t epi, const void* A2, const void* W2, cons
 D3DP_API int d3dp_op_to_bf16(const float* src, void* dst, size_t n, void* stream);
 
 /* ---- per-kernel timing (HIP events on the launch stream) -------------------------------------------------
- * While enabled, every kernel launched by d3dp_denoise, d3dp_train_forward and d3dp_train_backward is bracketed by
+ * While enabled, every kernel launched by d3dp_denoise, d3dp_sample, d3dp_train_forward and d3dp_train_backward is bracketed by
  * hipEventRecord on the caller's stream (while enabled the training step keeps its weight-gradient products on that stream too
  * instead of its second one: no class's time contains a wait for compute units another stream holds; same results bit for bit).
  * d3dp_profile_read synchronises the recorded events and returns, per kernel class, the launch count and the
- * summed duration in milliseconds.  Classes are listed by d3dp_profile_class_name: 0-11 the denoiser's (d3dp_denoise),
+ * summed duration in milliseconds.  Classes are listed by d3dp_profile_class_name: 0-11 the denoiser's (d3dp_denoise; the set-up,
+ * pre- and post-step kernels of d3dp_sample count in class 11, "other"),
  * 12-23 the training step's (ABI v4): train_linear (forward and dgrad products), train_wgrad (a block's merged weight-gradient
  * product + the sum of its partial tiles), train_attn_{fwd,bwd_q,bwd_kv}_{spatial,temporal}, train_operand_pass (fp32 rows -> split
  * operands), train_ln_fwd, train_ln_bwd, train_other; 24 event_pair_overhead: event pairs with nothing between them, recorded at
